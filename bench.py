@@ -8,12 +8,14 @@ structured normal equations, with the state and all measurement arrays already r
 N > 1: one independent calibration sequence per GPU (weak scaling, seed 40 + rank), no data-path collective;
 the only exchange is one RCCL all-reduce per step of the shared-calibration block of the normal equations.
 
-The second half of BASELINE.json's metric — surfel association Mpts/s at 1/2/4/8 GPUs — is measured in the same run (`secondary.surfel_assoc`):
-every rank associates its own shard of scans against the same surfel map (lvx_surfel_assoc_batch_d) and the per-point flags are all-gathered.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times exactly --steps steps and prints the line (`value`, `ms_per_step`);
+--dump-outputs DIR also writes what the last timed step left for its caller as DIR/*.npy (dump_outputs).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the time-dominant kernel
-(measured with HIP events on the library's own stream) plus every family's and the whole pass's fraction, and `cpu_baseline`
-(the oracle — a restatement of the reference's per-block autodiff evaluator — timed on a bounded sample on the host cores).
+--full adds every side measurement: `roofline` for the time-dominant kernel (measured with HIP events on the library's own stream) plus every
+family's and the whole pass's fraction, `secondary` (the second half of BASELINE.json's metric — surfel association Mpts/s, every rank
+associating its own shard of scans against the same surfel map (lvx_surfel_assoc_batch_d), flags all-gathered — the LM iteration, the
+upstream kernels, BASELINE config 3, and for N > 1 the joint LM and the other shard size), and `cpu_baseline` (the oracle — a restatement
+of the reference's per-block autodiff evaluator — timed on a bounded sample on the host cores).
 """
 import argparse
 import json
@@ -358,6 +360,25 @@ def secondary_metrics(ctx, P, lo):
     return sec
 
 
+def dump_outputs(ctx, red, d):
+    """What the last timed step left on the device for its caller, as float64 .npy files under `d`: J^T r and diag(J^T J) in the tangent layout
+    (lvx_get_gradient), the dense border block of J^T J (lower triangle) with its gradient, and the cost (lvx_export_border_d).  N > 1: `red` is the
+    border buffer after the step's all-reduce over the ranks, so the border block, its gradient and the cost are sums over the ranks."""
+    import torch
+    g, diag = ctx.gradient()      # also returns the device error of the last evaluation
+    n = ctx.layout()["border_ld"]
+    if red is None:
+        red = torch.zeros(n * n + n + 2, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()  # the fill is on torch's stream, the export on the context's
+        ctx.export_border(red.data_ptr())
+        ctx.synchronize()
+    b = red.cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    for name, a in (("gradient", g), ("hessian_diag", diag), ("border_block", np.tril(b[:n * n].reshape(n, n))), ("border_gradient", b[n * n:n * n + n]),
+                    ("cost", b[n * n + n:n * n + n + 1])):
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def usable_cores():
     """Cores this process may actually use: affinity mask capped by the cgroup CPU quota (os.cpu_count() reports the host)."""
     n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -458,11 +479,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--small", action="store_true", help="1/10 size problem (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the LM-iteration and upstream-kernel side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement: roofline and per-kernel durations, secondary metrics, the CPU baseline (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the LM-iteration and upstream-kernel side measurements")
     ap.add_argument("--shard-size", choices=("full", "eighth"), default="full",
-                    help="N > 1 (SURVEY 8d config 5): every rank's sequence at full config-4 size (default, weak scaling) or at 1/8 size; the other variant is reported under secondary")
+                    help="N > 1 (SURVEY 8d config 5): every rank's sequence at full config-4 size (default, weak scaling) or at 1/8 size; with --full the other variant is reported under secondary")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -519,9 +545,9 @@ def main():
     for _ in range(args.warmup):
         step()
     ctx.synchronize()
-    # live HIP-event timing of the dominant kernel (surfel) over the timed region; the other kernels' durations come from a separate
-    # profiled run below (an event pair around every launch costs ~5 % of a pass).  LVX_BENCH_NOPROF=1: no events at all (replayed graph).
-    live = not os.environ.get("LVX_BENCH_NOPROF")
+    # --full: live HIP-event timing of the dominant kernel (surfel) over the timed region for the roofline; the other kernels' durations come from a separate
+    # profiled run below (an event pair around every launch costs ~5 % of a pass).  A plain run, or LVX_BENCH_NOPROF=1: no events at all.
+    live = args.full and not os.environ.get("LVX_BENCH_NOPROF")
     # which kernel is time-dominant: a short run with an event pair around every launch (untimed), then the timed region carries events around that kernel only
     live_k = lvx.FAM_SURFEL
     if live:
@@ -556,11 +582,13 @@ def main():
         return dt
 
     elapsed = timed_region()
+    if dist_on and float(red[-1].item()) != 0.0:     # summed device error words of the last step: some rank's sums were incomplete
+        raise SystemExit("a rank reported a device-side evaluation error (range / non-unit quaternion / fallback)")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, red, args.dump_outputs)
     ms, launches = ctx.kernel_ms()
     ctx.set_profiling(False)
     cost = ctx.evaluate_resident(lvx.EVAL_COST, want_cost=True)
-    if dist_on and float(red[-1].item()) != 0.0:     # summed device error words of the last step: some rank's sums were incomplete
-        raise SystemExit("a rank reported a device-side evaluation error (range / non-unit quaternion / fallback)")
     blocks = lo["n_blocks"]
     value = blocks * world * args.steps / elapsed / 1e6
     out = {
@@ -618,7 +646,9 @@ def main():
             except Exception as e:   # noqa: BLE001
                 out.setdefault("secondary", {})["inlib_rccl_step_error"] = str(e)[:300]
             transport["inlib"] = False
-    if rank == 0:
+            if args.dump_outputs and rank == 0 and "headline_transports" in out["secondary"]:
+                dump_outputs(ctx, red, args.dump_outputs)   # this timed region is the headline now: its last step
+    if rank == 0 and args.full:
         k = live_k
         surf_ms = ms[k] / max(1, launches[k])   # the live-timed (dominant) kernel's mean launch duration inside the timed region
         # durations of every kernel family in the pass's own schedule: a separate run with an event pair around every launch (outside the timed region);
@@ -686,7 +716,7 @@ def main():
                                    "(hoisted hub pose, precomputed control-point pairs); FP64 matrix = FP64 vector peak = 78.6 TFLOP/s on MI355X; `families` has every family's fraction, "
                                    "`whole_pass` the sum over the step time"}
     # ---- side measurements that involve every rank ----
-    if dist_on and not args.no_secondary:
+    if dist_on and args.full and not args.no_secondary:
         # LM iterations of the JOINT problem — shared rig extrinsics, one sequence per GPU (lvx_lm_solve_shared).  Transport: RCCL inside the library on the context's
         # stream when the job runs on RCCL (no host round trip); the host callback over torch.distributed otherwise, and as the fallback when a second communicator next
         # to torch's cannot be created.  Which one ran is recorded.
@@ -769,7 +799,7 @@ def main():
             c2.close()
         except Exception as e:   # noqa: BLE001
             sec_all["other_shard_size"] = {"error": str(e)[:300]}
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         try:
             assoc = assoc_metric(ctx, world, rank)      # every rank takes part (all-gather of the flags)
         except Exception as e:   # noqa: BLE001
@@ -782,7 +812,7 @@ def main():
             ctx.rccl_finalize()
         except Exception:   # noqa: BLE001
             pass
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not dist_on and not args.no_secondary:
             sec = secondary_metrics(ctx, P, lo)
             sec.update(out.get("secondary", {}))
