@@ -65,6 +65,7 @@ typedef struct lvx_ctx lvx_ctx;
 #define LVX_EVAL_RESIDUALS (1u << 1)
 #define LVX_EVAL_NORMAL_EQ (1u << 2)
 #define LVX_EVAL_JACOBIAN (1u << 3)   /* debug: per-row (cols, vals) in tangent coordinates, see lvx_get_jacobian */
+#define LVX_EVAL_JACOBIAN_BLOCKS (1u << 4)   /* per-block Jacobians in the family's compact record, from the fused kernels: lvx_get_jacobian_blocks */
 
 /* residual families, in the order residual rows are laid out */
 #define LVX_FAM_GYRO 0
@@ -157,6 +158,34 @@ int lvx_get_normal_eq_dense(lvx_ctx* ctx, double* H, double* g);
 int lvx_get_gradient(lvx_ctx* ctx, double* g, double* diag);
 /* debug / parity: rows of the last LVX_EVAL_JACOBIAN evaluation: cols[n_residuals][LVX_JAC_WIDTH] (-1 = unused), vals likewise (pre-loss) */
 int lvx_get_jacobian(lvx_ctx* ctx, int32_t* cols, double* vals);
+/* Per-block Jacobians (LVX_EVAL_JACOBIAN_BLOCKS; not together with LVX_EVAL_JACOBIAN: LVX_E_ARG; combines with COST, RESIDUALS, NORMAL_EQ).
+ * One record per residual block of a family, in INPUT order (block i = the i-th lvx_set_* entry, as residual rows are):
+ *   keys[i][3] = k0, k1, landmark (-1 where a family has none; (-1, -1, -1): the block was not evaluated)
+ *   vals[i][rows_per_block][width] = the raw weighted rows (pre-loss) in tangent coordinates, 0.0 at constant columns.
+ * Column c of a record is the per-segment kernel's own local column c; its tangent index is lvx_jacobian_block_cols:
+ *   family        NR  width (locked / free offset)  k0                         k1                          landmark
+ *   gyro           3  15                            interval                   -                           -
+ *   accel          3  29                            interval                   -                           -
+ *   prior          1  12                            interval                   -                           -
+ *   surfel         1  54 / 55 (54: LiDAR offset)    map-time (hub) interval    point-time interval         -
+ *   reprojection   2  55 / 56 (55: camera offset)   reference view's interval  observation's interval      landmark (column 54: rho)
+ *   camera-surfel  1  60 / 61 (60: camera offset)   map-time interval          landmark's reference pose   -
+ *   knot columns: 6 per knot (3 position | 3 rotation) of the 4 knots from k0 (then k1); gyro / prior: the 3 rotation scalars of each knot.
+ * When the two poses of a block share knots (merged segments), two columns map to the same tangent index: add them.
+ * The arrays are views into context-owned memory (host: pinned) of the last LVX_EVAL_JACOBIAN_BLOCKS evaluation; the call waits for their
+ * copies; they stay valid until the next evaluation or lvx_destroy.  No blocks: n_blocks = 0.  Last evaluation without the bit, or failed: LVX_E_STATE. */
+typedef struct lvx_jacobian_blocks {
+  int64_t n_blocks;
+  int32_t rows_per_block;
+  int32_t width;
+  const int32_t* keys;
+  const double* vals;
+  const int32_t* keys_d;
+  const double* vals_d;
+} lvx_jacobian_blocks;
+int lvx_get_jacobian_blocks(lvx_ctx* ctx, int family, lvx_jacobian_blocks* out);
+/* tangent index of each of the `width` columns of a record with keys key[3] (needs no context and no device); LVX_E_ARG for an unknown family / width */
+int lvx_jacobian_block_cols(int family, int n_knots, int width, const int32_t key[3], int32_t* cols);
 /* run on a caller-owned HIP stream (e.g. torch's current stream) instead of the context's own; NULL restores the own stream */
 int lvx_set_stream(lvx_ctx* ctx, void* hip_stream);
 /* multi-GPU (one calibration sequence per GPU): copy the dense border block of the last normal equations —

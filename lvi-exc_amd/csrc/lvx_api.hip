@@ -98,6 +98,10 @@ void lvx_destroy(lvx_ctx* c) {
   if (c->vox.h_info) (void)hipHostFree(c->vox.h_info);
   if (c->da_pinned) (void)hipHostFree(c->da_pinned);
   if (c->pin) (void)hipHostFree(c->pin);
+  for (int f = 0; f < LVX_NUM_FAM; ++f) if (c->ev_xb[f]) { (void)hipEventSynchronize(c->ev_xb[f]); (void)hipEventDestroy(c->ev_xb[f]); }   // (record copies in flight into the pinned buffers)
+  if (c->h_xkeys) (void)hipHostFree(c->h_xkeys);
+  if (c->h_xvals) (void)hipHostFree(c->h_xvals);
+  for (DevBuf* b : {&c->d_xkeys, &c->d_xvals}) if (b->p) (void)hipFree(b->p);
   for (DevBuf* b : {&c->vox.misc, &c->vox.keys, &c->vox.vals, &c->vox.runs, &c->vox.cells, &c->vox.tmp, &c->vox.leaf_i, &c->vox.leaf_d, &c->vox.leaf_f}) if (b->p) (void)hipFree(b->p);
   (void)lvx_rccl_finalize(c);
   if (c->d_comm.p) (void)hipFree(c->d_comm.p);
@@ -316,6 +320,28 @@ int lvx_get_jacobian(lvx_ctx* c, int32_t* cols, double* vals) {
   const size_t n = (size_t)c->n_residuals * LVX_JAC_WIDTH;
   LVX_HIP(c, hipMemcpy(cols, c->d_jcols.p, n * 4, hipMemcpyDeviceToHost));
   LVX_HIP(c, hipMemcpy(vals, c->d_jvals.p, n * 8, hipMemcpyDeviceToHost));
+  return LVX_OK;
+}
+
+int lvx_get_jacobian_blocks(lvx_ctx* c, int family, lvx_jacobian_blocks* out) {
+  if (!c || !out || family < 0 || family >= LVX_NUM_FAM) return LVX_E_ARG;
+  if (!(c->last_what & LVX_EVAL_JACOBIAN_BLOCKS) || !c->xb_valid) return fail(c, LVX_E_STATE, "last evaluation did not request LVX_EVAL_JACOBIAN_BLOCKS, or failed");
+  LVX_HIP(c, hipSetDevice(c->device));
+  { const int rce = check_last_eval(c); if (rce) { c->xb_valid = false; return rce; } }   // (a pass queued without a cost pointer that met the exact fallback is repeated here)
+  if (!c->xb_valid) return fail(c, LVX_E_STATE, "last evaluation did not request LVX_EVAL_JACOBIAN_BLOCKS, or failed");
+  const int f = family;
+  out->n_blocks = c->xb_n[f]; out->rows_per_block = c->xb_nr[f]; out->width = c->xb_w[f];
+  out->keys = c->h_xkeys ? c->h_xkeys + 3 * c->xb_off[f] : nullptr;
+  out->vals = c->h_xvals ? c->h_xvals + c->xb_voff[f] : nullptr;
+  out->keys_d = (const int32_t*)c->d_xkeys.p + 3 * c->xb_off[f];
+  out->vals_d = (const double*)c->d_xvals.p + c->xb_voff[f];
+  if (c->xb_n[f] > 0 && c->ev_xb[f]) LVX_HIP(c, hipEventSynchronize(c->ev_xb[f]));   // this family's copy only
+  return LVX_OK;
+}
+int lvx_jacobian_block_cols(int family, int n_knots, int width, const int32_t key[3], int32_t* cols) {
+  if (family < 0 || family >= LVX_NUM_FAM || !key || !cols || n_knots < 4) return LVX_E_ARG;
+  if (width != lvx::block_width(family, false) && width != lvx::block_width(family, true)) return LVX_E_ARG;
+  for (int c = 0; c < width; ++c) cols[c] = lvx::block_col(family, c, key[0], key[1], key[2], n_knots);
   return LVX_OK;
 }
 

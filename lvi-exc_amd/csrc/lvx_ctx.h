@@ -19,6 +19,8 @@
 namespace lvx {
 
 // device view handed to every kernel
+// per-block Jacobian records (LVX_EVAL_JACOBIAN_BLOCKS): family f's keys [n][3] and rows [n][NR][width], input order (device memory of the context)
+struct XbTab { int32_t* keys[LVX_NUM_FAM]; double* vals[LVX_NUM_FAM]; };
 struct DevCommon {
   const double* state;
   int N, L;
@@ -51,7 +53,10 @@ struct DevCommon {
   // outputs (may be null)
   double* residuals;
   int32_t* jcols;
-  double* jvals;
+  union {
+    double* jvals;
+    const XbTab* xb;   // LVX_EVAL_JACOBIAN_BLOCKS (exclusive with the debug rows): the record table, read by the export instantiations only
+  };
 };
 
 struct DevBuf {
@@ -144,6 +149,13 @@ struct lvx_ctx {
   int64_t n_blocks = 0, n_residuals = 0;
   int64_t fam_row0[LVX_NUM_FAM + 1] = {0};
   uint32_t last_what = 0;
+  // per-block Jacobian records (LVX_EVAL_JACOBIAN_BLOCKS): one device buffer per kind, family f at offset xb_off[f] blocks (keys) / xb_voff[f] doubles (rows);
+  // pinned host mirrors (grown, kept until lvx_destroy) and one event per family behind its device -> host copy
+  lvx::DevBuf d_xkeys, d_xvals, d_xtab; lvx::XbTab h_xtab{};   // d_xtab: the device copy of h_xtab (DevCommon::xb)
+  int32_t* h_xkeys = nullptr; double* h_xvals = nullptr; size_t h_xkeys_cap = 0, h_xvals_cap = 0;
+  int64_t xb_n[LVX_NUM_FAM] = {0}, xb_off[LVX_NUM_FAM] = {0}, xb_voff[LVX_NUM_FAM] = {0}; int xb_nr[LVX_NUM_FAM] = {0}, xb_w[LVX_NUM_FAM] = {0};
+  hipEvent_t ev_xb[LVX_NUM_FAM] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  bool xb_valid = false;   // the last evaluation requested LVX_EVAL_JACOBIAN_BLOCKS and succeeded
   const double* last_state_d = nullptr; bool last_want_res = false, err_unchecked = false;   // see check_last_eval
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];

@@ -37,7 +37,7 @@ struct HubShared { PoseEval A; int ok; double M[6][24]; };   // M: hub_matrix(A)
 // family policies
 // ---------------------------------------------------------------------------------------------------------
 struct GyroFam {
-  enum { NC = GYRO_NC, NR = GYRO_NR, USES_HUB = 0 };
+  enum { NC = GYRO_NC, NR = GYRO_NR, USES_HUB = 0, FAM = LVX_FAM_GYRO, KEYS = 1 };
   int n; const double* t; const double* m3; const int* perm; double weight, huber;
   __device__ void make_hub(const DevCommon&, const SplineRef&, const Cal&, HubShared*) const {}
   __device__ int eval(const DevCommon& cm, const SplineRef& sp, const Cal& cal, const HubShared&, int si, double r[NR], double (*J)[NC], Keys& k) const {
@@ -47,7 +47,7 @@ struct GyroFam {
   __device__ int col(int c, const Keys& k, int N) const { return gyro_col(c, k.k0, N); }
 };
 struct AccelFam {
-  enum { NC = ACC_NC, NR = ACC_NR, USES_HUB = 0 };
+  enum { NC = ACC_NC, NR = ACC_NR, USES_HUB = 0, FAM = LVX_FAM_ACCEL, KEYS = 1 };
   int n; const double* t; const double* m3; const int* perm; double weight, huber;
   __device__ void make_hub(const DevCommon&, const SplineRef&, const Cal&, HubShared*) const {}
   __device__ int eval(const DevCommon& cm, const SplineRef& sp, const Cal& cal, const HubShared&, int si, double r[NR], double (*J)[NC], Keys& k) const {
@@ -57,7 +57,7 @@ struct AccelFam {
   __device__ int col(int c, const Keys& k, int N) const { return acc_col(c, k.k0, N); }
 };
 struct PriorFam {
-  enum { NC = PRI_NC, NR = PRI_NR, USES_HUB = 0 };
+  enum { NC = PRI_NC, NR = PRI_NR, USES_HUB = 0, FAM = LVX_FAM_PRIOR, KEYS = 1 };
   int n; double t; quat q; const int* perm; double weight, huber;
   __device__ void make_hub(const DevCommon&, const SplineRef&, const Cal&, HubShared*) const {}
   __device__ int eval(const DevCommon& cm, const SplineRef& sp, const Cal&, const HubShared&, int, double r[NR], double (*J)[NC], Keys& k) const {
@@ -72,7 +72,7 @@ LVX_HD void hub_spans(double t_map, bool tau_locked, double mto, double sp1[1][2
 }
 
 template <bool TAU> struct SurfFamT {
-  enum { NC = SURF_NC + (TAU ? 1 : 0), NR = SURF_NR, USES_HUB = 1 };
+  enum { NC = SURF_NC + (TAU ? 1 : 0), NR = SURF_NR, USES_HUB = 1, FAM = LVX_FAM_SURFEL, KEYS = 2 };
   int n; const double* t; const double* pt; const int* plane; const int* perm; const double* planes; double t_map, weight, huber;
   __device__ void make_hub(const DevCommon& cm, const SplineRef& sp, const Cal& cal, HubShared* h) const {
     double s1[1][2]; hub_spans(t_map, (cm.locks & LVX_LOCK_LIDAR_TAU) != 0, cm.sensor_mto, s1);
@@ -105,7 +105,7 @@ template <bool TAU> struct SurfFamT {
 };
 using SurfFam = SurfFamT<false>;
 template <bool TAU> struct CamSurfFamT {
-  enum { NC = CS_NC + (TAU ? 1 : 0), NR = CS_NR, USES_HUB = 1 };
+  enum { NC = CS_NC + (TAU ? 1 : 0), NR = CS_NR, USES_HUB = 1, FAM = LVX_FAM_CAMSURF, KEYS = 2 };
   int n; const int* lm; const int* plane; const int* perm; const double* planes; const double* lm_uv; const double* lm_t0; double t_map, weight, huber;
   __device__ void make_hub(const DevCommon& cm, const SplineRef& sp, const Cal& cal, HubShared* h) const {
     double s1[1][2]; hub_spans(t_map, (cm.locks & LVX_LOCK_CAM_TAU) != 0, cm.sensor_mto, s1);
@@ -139,7 +139,7 @@ template <bool TAU> struct CamSurfFamT {
 };
 using CamSurfFam = CamSurfFamT<false>;
 template <bool TAU> struct ReprojFamT {
-  enum { NC = REP_NC + (TAU ? 1 : 0), NR = REP_NR, USES_HUB = 0 };
+  enum { NC = REP_NC + (TAU ? 1 : 0), NR = REP_NR, USES_HUB = 0, FAM = LVX_FAM_REPROJ, KEYS = 3 };
   int n; const int* lm; const double* uv; const double* t0o; const int* perm; const double* lm_uv; const double* lm_t0; double weight, huber;
   __device__ void make_hub(const DevCommon&, const SplineRef&, const Cal&, HubShared*) const {}
   __device__ int eval(const DevCommon& cm, const SplineRef& sp, const Cal& cal, const HubShared&, int si, double r[NR], double (*J)[NC], Keys& k) const {
@@ -205,8 +205,39 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
+// Per-block Jacobian records (LVX_EVAL_JACOBIAN_BLOCKS, include/lvx.h): written by the EXP instantiations of the evaluating kernels only, right after the
+// evaluation and before the Huber scale — one record per lane at the block's input position pi, the per-segment kernel's own columns, 0.0 at constant columns.
+// val(a, c): row a, record column c of the block (the fused kernels map their own column order onto the record's here).
+template <int NR, int W, class V>
+__device__ __forceinline__ void put_record(const DevCommon& cm, int fam, int pi, int k0, int k1, int lm, V&& val) {
+  int32_t* kd = cm.xb->keys[fam] + 3 * (size_t)pi;
+  kd[0] = k0; kd[1] = k1; kd[2] = lm;
+  double* vd = cm.xb->vals[fam] + (size_t)pi * (NR * W);
+#pragma unroll
+  for (int a = 0; a < NR; ++a)
+#pragma unroll
+    for (int c = 0; c < W; ++c) vd[a * W + c] = tangent_locked(block_col(fam, c, k0, k1, lm, cm.N), cm.N, cm.L, cm.locks) ? 0.0 : val(a, c);
+}
+// a block that was not evaluated (or that the exact kernel behind a fused one evaluates: it overwrites the record)
+__device__ __forceinline__ void put_skipped(const DevCommon& cm, int fam, int pi) {
+  int32_t* kd = cm.xb->keys[fam] + 3 * (size_t)pi;
+  kd[0] = -1; kd[1] = -1; kd[2] = -1;
+}
+// hub knot column c (0..23) of a pseudo-hub row: g0 (the row's 6 pseudo columns) x M_hub (the pass's prepass, HubShared::M)
+__device__ __forceinline__ double hub_col(const HubShared& h, const double* g0, int c) {
+  double s = 0.0;
+#pragma unroll
+  for (int p = 0; p < 6; ++p) s += g0[p] * h.M[p][c];
+  return s;
+}
+
 // PW = wavefronts per workgroup: wave 0 evaluates the 64 measurements (phase 1), all PW waves share the pair work of phase 2
-template <class F, int PW>
+// The export instantiation evaluates through a flattened copy of F::eval: the default instantiation then stays its only caller, and the inliner decides
+// for it exactly as without the export (a second call site of the reprojection residual cost k_family<ReprojFamT, 4> its inlining: 316 -> 2 276 B of scratch)
+template <class F, class... A>
+__device__ __attribute__((always_inline, flatten)) int eval_flat(const F& fam, A&&... a) { return fam.eval(static_cast<A&&>(a)...); }
+// EXP: also the per-block records (LVX_EVAL_JACOBIAN_BLOCKS)
+template <class F, int PW, bool EXP = false>
 __global__ __launch_bounds__(64 * PW) void k_family(F fam, DevCommon cm, const uint16_t* __restrict__ pairs, long long row0, const int* __restrict__ rows = nullptr, const int* __restrict__ nrows = nullptr) {
   constexpr int NC = F::NC, NR = F::NR, TS = NR * 64 + 1, NP = NC * (NC + 1) / 2;
   __shared__ double Jt[NC * TS];
@@ -238,9 +269,15 @@ __global__ __launch_bounds__(64 * PW) void k_family(F fam, DevCommon cm, const u
   Keys key{-1, -1, -1};
   bool valid = false;
   if (in) {
-    const int status = fam.eval(cm, sp, cal, hub, si, r, J, key);
+    int status;
+    if constexpr (EXP) status = eval_flat(fam, cm, sp, cal, hub, si, r, J, key);
+    else status = fam.eval(cm, sp, cal, hub, si, r, J, key);
     valid = status == RES_OK;
     if (!valid) { atomicOr(cm.err, status); key = Keys{-1, -1, -1}; }
+    if constexpr (EXP) {
+      if (valid) put_record<NR, NC>(cm, F::FAM, fam.perm[si], key.k0, F::KEYS > 1 ? key.k1 : -1, F::KEYS > 2 ? key.lm : -1, [&](int a, int c) { return J[a][c]; });
+      else put_skipped(cm, F::FAM, fam.perm[si]);
+    }
   }
   double mycost = 0.0;
   if (valid) {
@@ -254,7 +291,7 @@ __global__ __launch_bounds__(64 * PW) void k_family(F fam, DevCommon cm, const u
 #pragma unroll
       for (int a = 0; a < NR; ++a) cm.residuals[orow + a] = r[a];
     }
-    if (cm.jcols) {
+    if (!EXP && cm.jcols) {   // (EXP: jvals holds the record table)
 #pragma unroll
       for (int a = 0; a < NR; ++a) {
         int32_t* jc = cm.jcols + (orow + a) * LVX_JAC_WIDTH;
@@ -394,6 +431,11 @@ struct GyroAcc {
   }
   __device__ static int klv(int c) { return 6 * (c / 3) + 3 + c % 3; }
   __device__ static int gcol(int g, int N, int nt) { return 6 * N + 5 + g; }
+  // per-block record: the columns are gyro_residual's own
+  __device__ void put(const DevCommon& cm, const HubShared*, int si, bool valid, int key, const double (*J)[NCP]) const {
+    if (!valid) { put_skipped(cm, FAM, perm[si]); return; }
+    put_record<NR, GYRO_NC>(cm, FAM, perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
+  }
 };
 // TAU (free LiDAR time offset, the reference's opt_time_offset_ stages: trajectory_manager_lvi.cpp:159-165, sensors.h:70-85): one more global column, d r / d tau_L =
 // g_p (v_k - v_0) + g_xi0 w_0 + g_xik w_k — the pose gradients the row already has, contracted with the spline's velocity and body angular velocity at both poses —
@@ -433,6 +475,11 @@ template <bool TAU> struct SurfAccT {
   }
   __device__ static int klv(int c) { return c; }
   __device__ static int gcol(int g, int N, int nt) { return g < 6 ? nt + g : 6 * N + 8 + (g - 6); }   // g = 12 (TAU): 6 N + 14, the LiDAR time offset
+  // per-block record in surf_col order: [hub knots (g0 M_hub) | point knots | LiDAR extrinsics (| offset)] from [point knots 24 | pseudo 6 | extrinsics 6 (| offset)]
+  __device__ void put(const DevCommon& cm, const HubShared* hub, int si, bool valid, int key, const double (*J)[NCP]) const {
+    if (!valid) { put_skipped(cm, FAM, perm[si]); return; }
+    put_record<NR, SURF_NC + (TAU ? 1 : 0)>(cm, FAM, perm[si], hub->A.k.i0, key, -1, [&](int a, int c) { return c < 24 ? hub_col(*hub, &J[a][24], c) : (c < 48 ? J[a][c - 24] : J[a][c - 18]); });
+  }
 };
 using SurfAcc = SurfAccT<false>;
 template <bool TAU> struct CamSurfAccT {
@@ -467,6 +514,11 @@ template <bool TAU> struct CamSurfAccT {
   }
   __device__ static int klv(int c) { return c; }
   __device__ static int gcol(int g, int N, int nt) { return g < 6 ? nt + 6 + g : (g < 12 ? 6 * N + 15 + (g - 6) : (g < 18 ? 6 * N + 8 + (g - 12) : 6 * N + 21)); }   // g = 18 (TAU): the camera time offset
+  // per-block record in cs_col order: [hub knots (g0 M_hub) | reference-pose knots | camera, LiDAR extrinsics (| offset)] from [knots 24 | pseudo 6 | camera 6 | LiDAR 6 (| offset)]
+  __device__ void put(const DevCommon& cm, const HubShared* hub, int si, bool valid, int key, const double (*J)[NCP]) const {
+    if (!valid) { put_skipped(cm, FAM, perm[si]); return; }
+    put_record<NR, CS_NC + (TAU ? 1 : 0)>(cm, FAM, perm[si], hub->A.k.i0, key, -1, [&](int a, int c) { return c < 24 ? hub_col(*hub, &J[a][24], c) : (c < 48 ? J[a][c - 24] : J[a][c - 18]); });
+  }
 };
 using CamSurfAcc = CamSurfAccT<false>;
 
@@ -511,7 +563,8 @@ template <int SIDE, bool TAU = false> struct RepSideAcc {   // SIDE 0: the refer
 // Reprojection phase 1 on its own: residual + Jacobian of every block (observation order), Huber-scaled, to HBM (0.9 KB per block);
 // cost and residual output happen here.  The two-pose rolling-shutter residual needs > 512 registers when it shares a kernel with the
 // assembly, so the MFMA passes read the rows back instead (2 x 45 MB at config 4, nothing against their atomics).
-template <bool TAU>
+// EXP: also the unscaled rows as per-block records (LVX_EVAL_JACOBIAN_BLOCKS) in input order
+template <bool TAU, bool EXP = false>
 __global__ __launch_bounds__(64) void k_reproj_jac(ReprojFamT<TAU> fam, DevCommon cm, double* Jb, double* rb, int* kb, long long row0, double* Trec) {
   constexpr int RJ = REP_NC + (TAU ? 1 : 0), RW = 56 + (TAU ? 1 : 0);
   constexpr int RS = RW | 1;           // odd LDS stride: a lane writes its record's words one instruction at a time
@@ -526,6 +579,10 @@ __global__ __launch_bounds__(64) void k_reproj_jac(ReprojFamT<TAU> fam, DevCommo
     double r[2], J[2][RJ];
     Keys key{-1, -1, -1};
     const int status = fam.eval_pre(cm, sp, cal, si, r, J, key);
+    if constexpr (EXP) {
+      if (status != RES_OK) put_skipped(cm, LVX_FAM_REPROJ, fam.perm[si]);
+      else put_record<2, RJ>(cm, LVX_FAM_REPROJ, fam.perm[si], key.k0, key.k1, key.lm, [&](int a, int c) { return J[a][c]; });
+    }
     if (status != RES_OK) { if (status == RES_OUTSIDE) fallback_row(cm, LVX_FAM_REPROJ, si); else atomicOr(cm.err, status); kb[si] = -1; kb[n + si] = -1; }
     else {
       double scale;
@@ -978,7 +1035,8 @@ template <class F> size_t mfma_lds_bytes(int cr) {
 }
 
 // CR = knot intervals per workgroup, chosen per problem by the host (pick_chunk) so that the workgroup count fills whole rounds of the CUs
-template <class F, int OCC>
+// EXP: also the per-block records (LVX_EVAL_JACOBIAN_BLOCKS), from the registers the row was just evaluated into (F::put)
+template <class F, int OCC, bool EXP = false>
 __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, const int* __restrict__ chunk_off, long long row0, int CR, int var_nch, const int* __restrict__ det_list) {
   using G = MfmaGeom<F>;
   constexpr int NK = F::NK, NG = F::NG, NC = F::NCP, NR = F::NR, KPK = F::KPK, WS = F::WS, GL = F::GL, LB = F::LB;
@@ -1093,6 +1151,7 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
       else if (!valid && status > 0) atomicOr(cm.err, status);   // status < 0: row skipped (reported by the kernel that produced it)
     }
     if constexpr (RowOf<F>::prefetch) { const int sn = si + nwv * LB; if (lane < LB && sn < m1) nxt = fam.load(sn); }   // next batch's rows: in flight during this batch's assembly
+    if constexpr (EXP) { if (in) fam.put(cm, hub, si, valid, key, J); }
     if (valid) {
       double s = 0.0;
 #pragma unroll
@@ -1486,6 +1545,8 @@ __global__ void k_imu_rtab(int* out) {
   for (int i = 0; i < ImuG::NTP * 4; ++i) out[i * 64 + lane] = rtg[i];
   for (int i = 0; i < ImuA::NTP * 4; ++i) out[(ImuG::NTP * 4 + i) * 64 + lane] = rta[i];
 }
+// EXP: also the per-block records of both blocks of every sample (LVX_EVAL_JACOBIAN_BLOCKS)
+template <bool EXP = false>
 __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, const int* __restrict__ chunk_off, ImuOwn ow, long long row0_g, long long row0_a, int det, const int* __restrict__ rtab_g) {
   constexpr int PAN = (ImuG::PR * ImuG::LDP > ImuA::PR * ImuA::LDP) ? ImuG::PR * ImuG::LDP : ImuA::PR * ImuA::LDP;
   constexpr int ACC_LV = IMU_LV, CR = IMU_CR, HB = ACC_BW / 2;
@@ -1588,7 +1649,9 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
             for (int b = 0; b < 3; ++b) J[a][12 + b] = (a == b) ? -w : 0.0;
           mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
           if (cm.residuals) { const long long orow = row0_g + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
+          if constexpr (EXP) put_record<3, GYRO_NC>(cm, LVX_FAM_GYRO, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
         }
+        if constexpr (EXP) { if (in && !valid) { put_skipped(cm, LVX_FAM_GYRO, fam.perm[si]); put_skipped(cm, LVX_FAM_ACCEL, fam.perm[si]); } }
         if (want_ne) imu_assemble<ImuG>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC);
         IKT(2)
       }
@@ -1628,6 +1691,7 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
           }
           mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
           if (cm.residuals) { const long long orow = row0_a + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
+          if constexpr (EXP) put_record<3, ACC_NC>(cm, LVX_FAM_ACCEL, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
         }
         if (want_ne) imu_assemble<ImuA>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC);
         IKT(3)
@@ -2588,8 +2652,52 @@ __global__ __launch_bounds__(256) void k_clear(ClearList cl, BandClear bc, int n
   }
 }
 
+// k_family with or without the per-block records (EXP)
+template <class F, int PW>
+static void launch_family(bool exp, dim3 grid, dim3 block, hipStream_t s, const F& f, const DevCommon& cm, const uint16_t* pairs, long long row0, const int* rows = nullptr, const int* nrows = nullptr) {
+  if (exp) hipLaunchKernelGGL((k_family<F, PW, true>), grid, block, 0, s, f, cm, pairs, row0, rows, nrows);
+  else hipLaunchKernelGGL((k_family<F, PW>), grid, block, 0, s, f, cm, pairs, row0, rows, nrows);
+}
+// LVX_EVAL_JACOBIAN_BLOCKS: per-family record geometry and device buffers (sized for this layout and lock mask); the family offsets of both buffers
+static int setup_blocks(lvx_ctx* ctx, DevCommon& cm) {
+  static const int nrs[LVX_NUM_FAM] = {GYRO_NR, ACC_NR, PRI_NR, SURF_NR, REP_NR, CS_NR};
+  const bool tauL = !(ctx->locks & LVX_LOCK_LIDAR_TAU), tauC = !(ctx->locks & LVX_LOCK_CAM_TAU);
+  int64_t nk = 0, nv = 0;
+  for (int f = 0; f < LVX_NUM_FAM; ++f) {
+    ctx->xb_nr[f] = nrs[f];
+    ctx->xb_w[f] = block_width(f, f == LVX_FAM_SURFEL ? tauL : (f >= LVX_FAM_REPROJ ? tauC : false));
+    ctx->xb_n[f] = (ctx->fam_row0[f + 1] - ctx->fam_row0[f]) / nrs[f];
+    ctx->xb_off[f] = nk; ctx->xb_voff[f] = nv;
+    nk += ctx->xb_n[f]; nv += ctx->xb_n[f] * nrs[f] * ctx->xb_w[f];
+  }
+  int rc;
+  if ((rc = dev_alloc(ctx, ctx->d_xkeys, (size_t)std::max<int64_t>(nk, 1) * 12))) return rc;
+  if ((rc = dev_alloc(ctx, ctx->d_xvals, (size_t)std::max<int64_t>(nv, 1) * 8))) return rc;
+  if (ctx->h_xkeys_cap < (size_t)nk * 3) {
+    if (ctx->h_xkeys) { (void)hipHostFree(ctx->h_xkeys); ctx->h_xkeys = nullptr; ctx->h_xkeys_cap = 0; }
+    LVX_HIP(ctx, hipHostMalloc((void**)&ctx->h_xkeys, (size_t)nk * 12, hipHostMallocDefault)); ctx->h_xkeys_cap = (size_t)nk * 3;
+  }
+  if (ctx->h_xvals_cap < (size_t)nv) {
+    if (ctx->h_xvals) { (void)hipHostFree(ctx->h_xvals); ctx->h_xvals = nullptr; ctx->h_xvals_cap = 0; }
+    LVX_HIP(ctx, hipHostMalloc((void**)&ctx->h_xvals, (size_t)nv * 8, hipHostMallocDefault)); ctx->h_xvals_cap = (size_t)nv;
+  }
+  XbTab t{};
+  for (int f = 0; f < LVX_NUM_FAM; ++f) {
+    if (!ctx->ev_xb[f]) LVX_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_xb[f], hipEventDisableTiming));
+    t.keys[f] = (int32_t*)ctx->d_xkeys.p + 3 * ctx->xb_off[f];
+    t.vals[f] = (double*)ctx->d_xvals.p + ctx->xb_voff[f];
+  }
+  if (!ctx->d_xtab.p || std::memcmp(&t, &ctx->h_xtab, sizeof(t)) != 0) {   // (the table changes with the layout only)
+    if ((rc = upload_tmp(ctx, ctx->d_xtab, &t, sizeof(t)))) return rc;
+    ctx->h_xtab = t;
+  }
+  cm.xb = (const XbTab*)ctx->d_xtab.p;
+  return LVX_OK;
+}
+
 static bool fast_fb(const lvx_ctx* ctx, uint32_t what) { return ctx->fb_on && !ctx->force_legacy && !(what & LVX_EVAL_JACOBIAN) && !ctx->sw.force_legacy; }
 int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cost, bool want_res_buffer) {
+  ctx->xb_valid = false;   // (first: a call that fails anywhere below leaves no records to read)
   int rc = ensure_layout(ctx);
   if (rc) return rc;
   hipStream_t st = ctx->stream;
@@ -2597,6 +2705,12 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
   if (want_res_buffer) {
     if ((rc = dev_alloc(ctx, ctx->d_res, (size_t)std::max<int64_t>(ctx->n_residuals, 1) * 8))) return rc;
     cm.residuals = (double*)ctx->d_res.p;
+  }
+  const bool xb = (what & LVX_EVAL_JACOBIAN_BLOCKS) != 0;
+  if (xb && (what & LVX_EVAL_JACOBIAN)) return fail(ctx, LVX_E_ARG, "LVX_EVAL_JACOBIAN and LVX_EVAL_JACOBIAN_BLOCKS are exclusive");
+  if (xb) {   // the previous pass's record copies read the buffers this pass writes (a pass without the bit does not touch them)
+    for (int f = 0; f < LVX_NUM_FAM; ++f) if (ctx->ev_xb[f]) LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_xb[f], 0));
+    if ((rc = setup_blocks(ctx, cm))) return rc;
   }
   if (what & LVX_EVAL_JACOBIAN) {
     const size_t nrow = (size_t)std::max<int64_t>(ctx->n_residuals, 1);
@@ -2675,24 +2789,40 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
     // arranged accordingly: k_imu_own's columns are stored before the IMU lists run, the fold's store of the far hub rows is switched off when a LiDAR family has a list
     // (hub_partial below), the landmark rows are stored by k_reproj_lmrows on the chain before the reprojection list runs there.
     hipStream_t s_fb = (sw.serial || det) ? st : ctx->fam_stream[1];
+    // LVX_EVAL_JACOBIAN_BLOCKS: family f's records go to the pinned host buffer on a copy stream, right behind the last kernel that writes them (on stream s),
+    // while the pass goes on; lvx_get_jacobian_blocks waits for ev_xb[f]
+    hipStream_t s_cp = ctx->fam_stream[2];
+    auto xb_copy = [&](int f, hipStream_t s) -> int {
+      if (!xb) return LVX_OK;
+      LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s)); LVX_HIP(ctx, hipStreamWaitEvent(s_cp, ctx->ev_xb[f], 0));
+      if (ctx->xb_n[f] > 0) {
+        LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xkeys + 3 * ctx->xb_off[f], ctx->h_xtab.keys[f], (size_t)ctx->xb_n[f] * 12, hipMemcpyDeviceToHost, s_cp));
+        LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xvals + ctx->xb_voff[f], ctx->h_xtab.vals[f], (size_t)ctx->xb_n[f] * ctx->xb_nr[f] * ctx->xb_w[f] * 8, hipMemcpyDeviceToHost, s_cp));
+      }
+      LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s_cp));
+      return LVX_OK;
+    };
     bool fb_used = false;
     int fb_ev = 0;
     auto fb_fork = [&]() -> int { if (s_fb != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_fb[fb_ev], st)); LVX_HIP(ctx, hipStreamWaitEvent(s_fb, ctx->ev_fb[fb_ev], 0)); fb_ev ^= 1; fb_used = true; } return LVX_OK; };
     if (imu_fused_on) {   // gyroscope + accelerometer blocks in one owner-computes kernel, FIRST on the band: it stores what it owns (k_imu_own)
       const ImuFused f{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, ctx->imu.huber /*w_acc*/};
       const size_t lds_ = imu_fused_lds_bytes(ctx->imu_span);
-      LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_imu_own, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));
+      LVX_HIP(ctx, hipFuncSetAttribute(xb ? (const void*)k_imu_own<true> : (const void*)k_imu_own<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));
       const ImuOwn ow{(const int*)ctx->d_imu_wg.p, imu_own ? (const int*)ctx->d_imu_own.p + ctx->imu_own_k_off : nullptr, ctx->imu_nch, ctx->imu_span};
       ProfScope ps(ctx, LVX_FAM_GYRO, st);
-      hipLaunchKernelGGL(k_imu_own, dim3(ctx->imu_wg), dim3(256), lds_, st, f, cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
+      if (xb) hipLaunchKernelGGL(k_imu_own<true>, dim3(ctx->imu_wg), dim3(256), lds_, st, f, cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
+      else hipLaunchKernelGGL(k_imu_own<false>, dim3(ctx->imu_wg), dim3(256), lds_, st, f, cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
       if (fb_fam(LVX_FAM_GYRO)) {   // listed samples: both blocks by the exact kernels (they ADD to what k_imu_own stored)
         if ((rc = fb_fork())) return rc;
         ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb);
         GyroFam gf{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-        hipLaunchKernelGGL((k_family<GyroFam, 1>), fb_grid, dim3(64), 0, s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
+        launch_family<GyroFam, 1>(xb, fb_grid, dim3(64), s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
         AccelFam af{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.huber /*w_acc*/, 0.0};
-        hipLaunchKernelGGL((k_family<AccelFam, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, s_fb, af, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
+        launch_family<AccelFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, af, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
       }
+      const hipStream_t s_imu = fb_fam(LVX_FAM_GYRO) ? s_fb : st;
+      if ((rc = xb_copy(LVX_FAM_GYRO, s_imu)) || (rc = xb_copy(LVX_FAM_ACCEL, s_imu))) return rc;
     }
     // Schedule.  ONE chain on the caller's stream — clear -> fused IMU kernel (stores its band columns) -> prior -> LiDAR kernels -> reprojection Jacobian -> observation
     // pass -> cross terms -> landmark rows -> fold — and ONE side stream that takes the reprojection reference pass (it only reads the materialised rows and adds
@@ -2703,21 +2833,23 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
     hipStream_t s_side = side_on ? ctx->fam_stream[0] : st;
     bool side_used = false;
   #define LVX_T2(...) __VA_ARGS__
-  #define LVX_LAUNCH_MFMA1(FT, OCCV, fam_obj, chunk_slot, stream, row0v)                                                                        \
+  #define LVX_LAUNCH_MFMA1(FT, OCCV, fam_obj, chunk_slot, stream, row0v) LVX_LAUNCH_MFMA1X(FT, OCCV, false, fam_obj, chunk_slot, stream, row0v)
+  #define LVX_LAUNCH_MFMA1X(FT, OCCV, EXPV, fam_obj, chunk_slot, stream, row0v)                                                                 \
     do {                                                                                                                                     \
       const size_t lds_ = mfma_lds_bytes<FT>(ctx->chunk_r[chunk_slot]);                                                                      \
-      LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_family_mfma<FT, OCCV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));       \
+      LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_family_mfma<FT, OCCV, EXPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
       if (det && ctx->det_col[chunk_slot].size() > 1) {   /* colour after colour: no two workgroups of a launch touch the same knots */            \
         const std::vector<int>& dc_ = ctx->det_col[chunk_slot];                                                                              \
         for (size_t q_ = 0; q_ + 1 < dc_.size(); ++q_)                                                                                       \
-          hipLaunchKernelGGL((k_family_mfma<FT, OCCV>), dim3(dc_[q_ + 1] - dc_[q_]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
+          hipLaunchKernelGGL((k_family_mfma<FT, OCCV, EXPV>), dim3(dc_[q_ + 1] - dc_[q_]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
                              ctx->chunk_r[chunk_slot], ctx->chunk_var[chunk_slot] ? ctx->n_chunk[chunk_slot] : 0, (const int*)ctx->d_det_list[chunk_slot].p + dc_[q_]); \
       } else                                                                                                                                 \
-      hipLaunchKernelGGL((k_family_mfma<FT, OCCV>), dim3(ctx->n_chunk[chunk_slot]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
+      hipLaunchKernelGGL((k_family_mfma<FT, OCCV, EXPV>), dim3(ctx->n_chunk[chunk_slot]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
                          ctx->chunk_r[chunk_slot], ctx->chunk_var[chunk_slot] ? ctx->n_chunk[chunk_slot] : 0, (const int*)nullptr);          \
     } while (0)
   #define LVX_LAUNCH_MFMA(FT, fam_obj, chunk_slot, stream, row0v)                                                                               \
-    do { if ((int)FT::OCC == 1) LVX_LAUNCH_MFMA1(FT, 1, fam_obj, chunk_slot, stream, row0v); else LVX_LAUNCH_MFMA1(FT, 2, fam_obj, chunk_slot, stream, row0v); } while (0)
+    do { if (xb) { if ((int)FT::OCC == 1) LVX_LAUNCH_MFMA1X(FT, 1, true, fam_obj, chunk_slot, stream, row0v); else LVX_LAUNCH_MFMA1X(FT, 2, true, fam_obj, chunk_slot, stream, row0v); }          \
+         else if ((int)FT::OCC == 1) LVX_LAUNCH_MFMA1(FT, 1, fam_obj, chunk_slot, stream, row0v); else LVX_LAUNCH_MFMA1(FT, 2, fam_obj, chunk_slot, stream, row0v); } while (0)
     // ---- IMU blocks when the fused kernel does not apply: Solve #0 (no R3 spline: gyroscope blocks only) on the MFMA path, everything else per segment ----
     if (ctx->imu.n > 0 && !imu_fused_on) {
       if (fast) {
@@ -2726,23 +2858,25 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         if (fb_fam(LVX_FAM_GYRO)) { if ((rc = fb_fork())) return rc;
           ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb);
           GyroFam gf{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-          hipLaunchKernelGGL((k_family<GyroFam, 1>), fb_grid, dim3(64), 0, s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO)); }
+          launch_family<GyroFam, 1>(xb, fb_grid, dim3(64), s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO)); }
       } else {
         GyroFam g{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
         ProfScope ps(ctx, LVX_FAM_GYRO, st);
-        hipLaunchKernelGGL((k_family<GyroFam, 1>), grid(g.n), dim3(64), 0, st, g, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0]);
+        launch_family<GyroFam, 1>(xb, grid(g.n), dim3(64), st, g, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0]);
       }
       if (!(ctx->locks & LVX_LOCK_R3)) {
         AccelFam a{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.huber /*w_acc*/, 0.0};
         ProfScope ps(ctx, LVX_FAM_ACCEL, st);
-        hipLaunchKernelGGL((k_family<AccelFam, LVX_PW>), grid(a.n), dim3(64 * LVX_PW), 0, st, a, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1]);
+        launch_family<AccelFam, LVX_PW>(xb, grid(a.n), dim3(64 * LVX_PW), st, a, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1]);
       }
+      if ((rc = xb_copy(LVX_FAM_GYRO, (fast && fb_fam(LVX_FAM_GYRO)) ? s_fb : st)) || (rc = xb_copy(LVX_FAM_ACCEL, st))) return rc;
     }
     if (ctx->has_prior) {
       DevBuf& pb = ctx->d_zero;   // identity permutation for the single prior block (zeroed by ensure_layout)
       PriorFam p{1, ctx->prior_t, mkq(ctx->prior_q[0], ctx->prior_q[1], ctx->prior_q[2], ctx->prior_q[3]), (const int*)pb.p, ctx->prior_w, 0.0};
       ProfScope ps(ctx, LVX_FAM_PRIOR, st);
-      hipLaunchKernelGGL((k_family<PriorFam, 1>), dim3(1), dim3(64), 0, st, p, cm, (const uint16_t*)ctx->d_pairs[2].p, (long long)ctx->fam_row0[2]);
+      launch_family<PriorFam, 1>(xb, dim3(1), dim3(64), st, p, cm, (const uint16_t*)ctx->d_pairs[2].p, (long long)ctx->fam_row0[2]);
+      if ((rc = xb_copy(LVX_FAM_PRIOR, st))) return rc;
     }
     // ---- LiDAR surfel blocks ----
     if (ctx->surf.n > 0) {
@@ -2751,19 +2885,20 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         SurfAccT<true> f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const double*)ctx->surf.d_b3.p, (const int*)ctx->surf.d_perm.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
         LVX_LAUNCH_MFMA(SurfAccT<true>, f, LVX_FAM_SURFEL, st, ctx->fam_row0[3]);
         if (fb_fam(LVX_FAM_SURFEL)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); SurfFamT<true> ff{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-          hipLaunchKernelGGL((k_family<SurfFamT<true>, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
+          launch_family<SurfFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
       } else if (fast_surf) {
         SurfAcc f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const double*)ctx->surf.d_b3.p, (const int*)ctx->surf.d_perm.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
         LVX_LAUNCH_MFMA(SurfAcc, f, LVX_FAM_SURFEL, st, ctx->fam_row0[3]);
         if (fb_fam(LVX_FAM_SURFEL)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); SurfFam ff{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-          hipLaunchKernelGGL((k_family<SurfFam, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
+          launch_family<SurfFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
       } else if (tauL) {
         SurfFamT<true> f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        hipLaunchKernelGGL((k_family<SurfFamT<true>, 1>), grid(f.n), dim3(64), 0, st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
+        launch_family<SurfFamT<true>, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
       } else {
         SurfFam f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        hipLaunchKernelGGL((k_family<SurfFam, 1>), grid(f.n), dim3(64), 0, st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
+        launch_family<SurfFam, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
       }
+      if ((rc = xb_copy(LVX_FAM_SURFEL, (fast_surf && fb_fam(LVX_FAM_SURFEL)) ? s_fb : st))) return rc;
     }
     // ---- camera-landmark-to-surfel blocks ----
     if (ctx->cs.n > 0) {
@@ -2772,19 +2907,20 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         CamSurfAccT<true> f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
         LVX_LAUNCH_MFMA(CamSurfAccT<true>, f, LVX_FAM_CAMSURF, st, ctx->fam_row0[5]);
         if (fb_fam(LVX_FAM_CAMSURF)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); CamSurfFamT<true> ff{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-          hipLaunchKernelGGL((k_family<CamSurfFamT<true>, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
+          launch_family<CamSurfFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
       } else if (fast_cs) {
         CamSurfAcc f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
         LVX_LAUNCH_MFMA(CamSurfAcc, f, LVX_FAM_CAMSURF, st, ctx->fam_row0[5]);
         if (fb_fam(LVX_FAM_CAMSURF)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); CamSurfFam ff{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-          hipLaunchKernelGGL((k_family<CamSurfFam, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
+          launch_family<CamSurfFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
       } else if (tauC) {
         CamSurfFamT<true> f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        hipLaunchKernelGGL((k_family<CamSurfFamT<true>, 1>), grid(f.n), dim3(64), 0, st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
+        launch_family<CamSurfFamT<true>, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
       } else {
         CamSurfFam f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        hipLaunchKernelGGL((k_family<CamSurfFam, 1>), grid(f.n), dim3(64), 0, st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
+        launch_family<CamSurfFam, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
       }
+      if ((rc = xb_copy(LVX_FAM_CAMSURF, (fast_cs && fb_fam(LVX_FAM_CAMSURF)) ? s_fb : st))) return rc;
     }
     // ---- reprojection blocks ----
     if (ctx->rep.n > 0) {
@@ -2798,14 +2934,17 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         { ProfScope ps(ctx, LVX_KERNEL_REP_JAC, st);
           const ReprojFamT<T> rf{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
           double* trec = (ctx->L > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS) && ctx->rep_groups > 0 && (what & LVX_EVAL_NORMAL_EQ)) ? (double*)ctx->d_repT.p : (double*)nullptr;
-          hipLaunchKernelGGL(k_reproj_jac<T>, grid(r.n), dim3(64), trec ? (size_t)64 * ((56 + (T ? 1 : 0)) | 1) * 8 : 0, st, rf, cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec); }
+          const size_t lds_j = trec ? (size_t)64 * ((56 + (T ? 1 : 0)) | 1) * 8 : 0;
+          if (xb) hipLaunchKernelGGL((k_reproj_jac<T, true>), grid(r.n), dim3(64), lds_j, st, rf, cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec);
+          else hipLaunchKernelGGL(k_reproj_jac<T>, grid(r.n), dim3(64), lds_j, st, rf, cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec); }
+        if (!fb_fam(LVX_FAM_REPROJ)) { const int rcc = xb_copy(LVX_FAM_REPROJ, st); if (rcc) return rcc; }   // (listed blocks: behind the exact kernel, rep_fixup)
         if (!(what & LVX_EVAL_NORMAL_EQ)) return LVX_OK;
         const RepJac jac{Jb, rb, kb, r.n};
         if (s_side != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_jac, st)); LVX_HIP(ctx, hipStreamWaitEvent(s_side, ctx->ev_jac, 0)); side_used = true; }
         { RepSideAcc<0, T> rr{r.n, jac, 0.0};
-          ProfScope ps(ctx, LVX_KERNEL_REP_REF, s_side); LVX_LAUNCH_MFMA1(LVX_T2(RepSideAcc<0, T>), 1, rr, LVX_FAM_PRIOR, s_side, ctx->fam_row0[4]); }
+          ProfScope ps(ctx, LVX_KERNEL_REP_REF, s_side); LVX_LAUNCH_MFMA1X(LVX_T2(RepSideAcc<0, T>), 1, false, rr, LVX_FAM_PRIOR, s_side, ctx->fam_row0[4]); }
         { RepSideAcc<1, T> ro{r.n, jac, 0.0};
-          ProfScope ps(ctx, LVX_KERNEL_REP_OBS, st); LVX_LAUNCH_MFMA1(LVX_T2(RepSideAcc<1, T>), 1, ro, LVX_FAM_REPROJ, st, ctx->fam_row0[4]); }
+          ProfScope ps(ctx, LVX_KERNEL_REP_OBS, st); LVX_LAUNCH_MFMA1X(LVX_T2(RepSideAcc<1, T>), 1, false, ro, LVX_FAM_REPROJ, st, ctx->fam_row0[4]); }
         if (ctx->rep_groups > 0) {
           const int* gt = (const int*)ctx->d_repB[2].p;
           RepCross rx{jac, r.lm, gt, gt + ctx->rep_groups + 1, ctx->rep_groups, (double*)ctx->d_repT.p, nullptr};
@@ -2845,10 +2984,10 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         if (!fb_fam(LVX_FAM_REPROJ)) return;
         ProfScope psf(ctx, LVX_KERNEL_FIXUP, st);
         if (tauC) { ReprojFamT<true> rt{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-          hipLaunchKernelGGL((k_family<ReprojFamT<true>, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ)); }
-        else hipLaunchKernelGGL((k_family<ReprojFam, LVX_PW>), fb_grid, dim3(64 * LVX_PW), 0, st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ));
+          launch_family<ReprojFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ)); }
+        else launch_family<ReprojFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ));
       };
-      if (fast && ctx->rep_fused_wg > 0) {
+      if (fast && ctx->rep_fused_wg > 0 && !xb) {   // (k_reproj_fused writes no records: with them the chain runs)
         const int rcf = tauC ? rep_one(std::true_type{}) : rep_one(std::false_type{});
         if (rcf) return rcf;
         rep_fixup();
@@ -2856,14 +2995,16 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
         const int rcf = tauC ? rep_fused(std::true_type{}) : rep_fused(std::false_type{});
         if (rcf) return rcf;
         rep_fixup();
+        if (fb_fam(LVX_FAM_REPROJ) && (rc = xb_copy(LVX_FAM_REPROJ, st))) return rc;
       } else if (tauC) {
         ProfScope ps(ctx, LVX_FAM_REPROJ, st);
         ReprojFamT<true> rt{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-        hipLaunchKernelGGL((k_family<ReprojFamT<true>, LVX_PW>), grid(r.n), dim3(64 * LVX_PW), 0, st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
+        launch_family<ReprojFamT<true>, LVX_PW>(xb, grid(r.n), dim3(64 * LVX_PW), st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
       } else {
         ProfScope ps(ctx, LVX_FAM_REPROJ, st);
-        hipLaunchKernelGGL((k_family<ReprojFam, LVX_PW>), grid(r.n), dim3(64 * LVX_PW), 0, st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
+        launch_family<ReprojFam, LVX_PW>(xb, grid(r.n), dim3(64 * LVX_PW), st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
       }
+      if (!fast && (rc = xb_copy(LVX_FAM_REPROJ, st))) return rc;
     }
     if (side_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[0], s_side)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0)); }
     if (fb_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[2], s_fb)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[2], 0)); }
@@ -2895,7 +3036,7 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
   };
   // graph replay pays for small problems (a pass is ~35 API calls: launch-bound at ~0.37 ms issued call by call, 0.26 ms replayed); at config-4 size the kernels are long
   // enough for the host to stay ahead and the replayed graph is the SLOWER one (0.61 against 0.58 ms: its cross-stream edges become barrier packets between every node)
-  const bool use_graph = !ctx->sw.no_graph && !ctx->profiling && !(what & LVX_EVAL_JACOBIAN) && ctx->n_blocks <= 400000;
+  const bool use_graph = !ctx->sw.no_graph && !ctx->profiling && !(what & (LVX_EVAL_JACOBIAN | LVX_EVAL_JACOBIAN_BLOCKS)) && ctx->n_blocks <= 400000;   // the records' copies are issued call by call
   if (!use_graph) { if ((rc = enqueue())) return rc; }
   else {
     const int flags = (want_res_buffer ? 1 : 0) | (ctx->force_legacy ? 2 : 0) | (ctx->fb_on ? 4 : 0) | (ctx->fb_mask << 3);   // a switch change bumps cfg_version
@@ -2943,6 +3084,7 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
     if (err[0] & RES_NONUNIT) return fail(ctx, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
     if (err[0] & 4) return fail(ctx, LVX_E_STATE, "normal-equation entry outside the computed bandwidth");
   }
+  ctx->xb_valid = xb;
   return LVX_OK;
 }
 

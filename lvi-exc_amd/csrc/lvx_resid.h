@@ -690,6 +690,22 @@ LVX_HD int rep_col(int c, int i0r, int i0o, int N, int lm) {
 LVX_HD int cs_col(int c, int i0h, int i0k, int N) {
   return c < 24 ? 6 * (i0h + c / 6) + c % 6 : (c < 48 ? 6 * (i0k + (c - 24) / 6) + (c - 24) % 6 : (c < 54 ? 6 * N + 15 + (c - 48) : (c < 60 ? 6 * N + 8 + (c - 54) : 6 * N + 21))); }   // c == 60: cam tau
 LVX_HD int pri_col(int c, int i0, int N) { return 6 * (i0 + c / 3) + 3 + c % 3; }
+// the maps above by family (LVX_FAM_* order: gyro, accel, prior, surfel, reprojection, camera-surfel) for the keys of a per-block record
+// (lvx_jacobian_blocks: k0, k1, landmark); width = the family's column count, +1 with a free time offset; -1: no such family / width
+LVX_HD int block_width(int fam, bool tau_free) {
+  switch (fam) {
+    case 0: return GYRO_NC; case 1: return ACC_NC; case 2: return PRI_NC;
+    case 3: return SURF_NC + (tau_free ? 1 : 0); case 4: return REP_NC + (tau_free ? 1 : 0); case 5: return CS_NC + (tau_free ? 1 : 0);
+  }
+  return -1;
+}
+LVX_HD int block_col(int fam, int c, int k0, int k1, int lm, int N) {
+  switch (fam) {
+    case 0: return gyro_col(c, k0, N); case 1: return acc_col(c, k0, N); case 2: return pri_col(c, k0, N);
+    case 3: return surf_col(c, k0, k1, N); case 4: return rep_col(c, k0, k1, N, lm); case 5: return cs_col(c, k0, k1, N);
+  }
+  return -1;
+}
 
 // lock mask (include/lvx.h LVX_LOCK_*) -> is global tangent index g constant?
 LVX_HD bool tangent_locked(int g, int N, int n_lm, uint32_t locks) {

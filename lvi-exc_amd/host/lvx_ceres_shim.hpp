@@ -14,10 +14,14 @@
 // Tangent -> ambient: lvx produces Jacobians in the tangent of ceres::EigenQuaternionParameterization (3 columns per quaternion).  Ceres
 // multiplies whatever a CostFunction returns by the manifold Jacobian P(q) (4 x 3, columns e_j (x) q, P^T P = I for unit q), so the block
 // handed out is J_tangent P(q)^T: Ceres' own J P then reproduces the tangent rows exactly.
+// Two routes for the Jacobian rows (JacobianRows): kDebugRows (default) — the 64-wide debug rows of LVX_EVAL_JACOBIAN, each row scanned once per
+// parameter block; kBlocks — the compact per-block records of LVX_EVAL_JACOBIAN_BLOCKS (include/lvx.h) produced by the fused kernels into pinned memory,
+// which LvxRowBlock maps column by column onto its parameter blocks through a table built once from its BlockSpec (O(rows x width) per Evaluate).
 // Only <ceres/ceres.h> (CostFunction, EvaluationCallback) is needed; header-only; no HIP types.
 #pragma once
 #include <ceres/ceres.h>
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <functional>
@@ -107,41 +111,81 @@ class BlockLayout {
   double t0_, dt_; int N_, L_; double readout_, mto_; uint32_t locks_;
 };
 
+enum class JacobianRows { kDebugRows, kBlocks };
+
 // ceres::Solver::Options::evaluation_callback: evaluates every block on the GPU once per iterate
 class LvxEvaluationCallback : public ceres::EvaluationCallback {
  public:
   // pack(state): copy the parameter blocks Ceres has just updated into the flat state (PackState below, bound to the host's entities)
-  LvxEvaluationCallback(lvx_ctx* ctx, std::function<void(double*)> pack) : ctx_(ctx), pack_(std::move(pack)) {
+  LvxEvaluationCallback(lvx_ctx* ctx, std::function<void(double*)> pack, JacobianRows mode = JacobianRows::kDebugRows) : ctx_(ctx), pack_(std::move(pack)), mode_(mode) {
     lvx_layout lo;
     if (lvx_get_layout(ctx_, &lo) != LVX_OK) throw std::runtime_error(lvx_last_error(ctx_));
+    n_knots_ = lo.n_knots;
     state_.assign((size_t)lvx_state_size(ctx_), 0.0);
     residuals_.assign((size_t)lo.n_residuals, 0.0);
-    jac_cols_.assign((size_t)lo.n_residuals * LVX_JAC_WIDTH, -1);
-    jac_vals_.assign((size_t)lo.n_residuals * LVX_JAC_WIDTH, 0.0);
+    if (mode_ == JacobianRows::kDebugRows) {
+      jac_cols_.assign((size_t)lo.n_residuals * LVX_JAC_WIDTH, -1);
+      jac_vals_.assign((size_t)lo.n_residuals * LVX_JAC_WIDTH, 0.0);
+    }
     if (lvx_get_family_rows(ctx_, row0_) != LVX_OK) throw std::runtime_error(lvx_last_error(ctx_));
+    bind(state_.data(), residuals_.data(), jac_cols_.data(), jac_vals_.data());
+  }
+  // no context: the caller supplies what an evaluation would (Provide) — the scatter of LvxRowBlock driven from views of its own
+  LvxEvaluationCallback(JacobianRows mode, int n_knots, const int64_t row0[LVX_NUM_FAM + 1]) : ctx_(nullptr), mode_(mode), n_knots_(n_knots) {
+    for (int f = 0; f <= LVX_NUM_FAM; ++f) row0_[f] = row0[f];
+  }
+  // state / residual rows and, per mode, the debug rows (cols, vals: [n_residuals][LVX_JAC_WIDTH]) or the six per-family record views; not copied
+  void Provide(const double* state, const double* residuals, const int32_t* cols, const double* vals, const lvx_jacobian_blocks* blocks) {
+    bind(state, residuals, cols, vals);
+    if (blocks) for (int f = 0; f < LVX_NUM_FAM; ++f) blocks_[f] = blocks[f];
+    ok_ = true; have_jac_ = mode_ == JacobianRows::kBlocks ? blocks != nullptr : (cols != nullptr && vals != nullptr);
   }
   void PrepareForEvaluation(bool evaluate_jacobians, bool new_evaluation_point) override {
+    if (!ctx_) return;
     if (!new_evaluation_point && !(evaluate_jacobians && !have_jac_)) return;
     pack_(state_.data());
     double cost = 0;
-    const int rc = lvx_evaluate(ctx_, state_.data(), LVX_EVAL_COST | LVX_EVAL_RESIDUALS | (evaluate_jacobians ? LVX_EVAL_JACOBIAN : 0u), &cost, residuals_.data());
+    const uint32_t jbit = !evaluate_jacobians ? 0u : (mode_ == JacobianRows::kBlocks ? LVX_EVAL_JACOBIAN_BLOCKS : LVX_EVAL_JACOBIAN);
+    int rc = lvx_evaluate(ctx_, state_.data(), LVX_EVAL_COST | LVX_EVAL_RESIDUALS | jbit, &cost, residuals_.data());
     ok_ = rc == LVX_OK;   // a failed evaluation makes every block's Evaluate return false: Ceres rejects the step, as it does for a throwing functor
-    if (ok_ && evaluate_jacobians) ok_ = lvx_get_jacobian(ctx_, jac_cols_.data(), jac_vals_.data()) == LVX_OK;
+    if (ok_ && evaluate_jacobians) {
+      if (mode_ == JacobianRows::kDebugRows) ok_ = lvx_get_jacobian(ctx_, jac_cols_.data(), jac_vals_.data()) == LVX_OK;
+      else {
+        rc = get_blocks();
+        if (rc == LVX_E_STATE) {   // the pass has just selected the exact fallback (lvx_synchronize): evaluate once more, as the LM loop does
+          rc = lvx_evaluate(ctx_, state_.data(), LVX_EVAL_COST | LVX_EVAL_RESIDUALS | jbit, &cost, residuals_.data());
+          if (rc == LVX_OK) rc = get_blocks();
+        }
+        ok_ = rc == LVX_OK;
+      }
+    }
     have_jac_ = evaluate_jacobians && ok_;
   }
   bool ok() const { return ok_; }
   bool have_jacobians() const { return have_jac_; }
-  const double* state() const { return state_.data(); }
-  const double* residual_row(int family, int index, int nr) const { return residuals_.data() + row0_[family] + (int64_t)index * nr; }
-  const int32_t* cols_row(int64_t row) const { return jac_cols_.data() + row * LVX_JAC_WIDTH; }
-  const double* vals_row(int64_t row) const { return jac_vals_.data() + row * LVX_JAC_WIDTH; }
+  JacobianRows mode() const { return mode_; }
+  int n_knots() const { return n_knots_; }
+  const double* state() const { return state_p_; }
+  const double* residual_row(int family, int index, int nr) const { return res_p_ + row0_[family] + (int64_t)index * nr; }
+  const int32_t* cols_row(int64_t row) const { return cols_p_ + row * LVX_JAC_WIDTH; }
+  const double* vals_row(int64_t row) const { return vals_p_ + row * LVX_JAC_WIDTH; }
   int64_t first_row(int family, int index, int nr) const { return row0_[family] + (int64_t)index * nr; }
+  const lvx_jacobian_blocks& blocks(int family) const { return blocks_[family]; }
 
  private:
+  void bind(const double* state, const double* res, const int32_t* cols, const double* vals) { state_p_ = state; res_p_ = res; cols_p_ = cols; vals_p_ = vals; }
+  int get_blocks() {
+    for (int f = 0; f < LVX_NUM_FAM; ++f) { const int rc = lvx_get_jacobian_blocks(ctx_, f, &blocks_[f]); if (rc != LVX_OK) return rc; }
+    return LVX_OK;
+  }
   lvx_ctx* ctx_;
   std::function<void(double*)> pack_;
+  JacobianRows mode_;
+  int n_knots_ = 0;
   std::vector<double> state_, residuals_, jac_vals_;
   std::vector<int32_t> jac_cols_;
+  const double* state_p_ = nullptr; const double* res_p_ = nullptr; const int32_t* cols_p_ = nullptr; const double* vals_p_ = nullptr;
+  lvx_jacobian_blocks blocks_[LVX_NUM_FAM] = {};
   int64_t row0_[LVX_NUM_FAM + 1] = {0};
   bool ok_ = false, have_jac_ = false;
 };
@@ -152,6 +196,7 @@ class LvxRowBlock : public ceres::CostFunction {
   LvxRowBlock(const LvxEvaluationCallback* cb, BlockSpec spec) : cb_(cb), spec_(std::move(spec)) {
     set_num_residuals(spec_.num_residuals);
     for (const auto& p : spec_.params) mutable_parameter_block_sizes()->push_back(p.size);
+    if (cb_->mode() == JacobianRows::kBlocks) build_table();
   }
   bool Evaluate(double const* const* /*parameters*/, double* residuals, double** jacobians) const override {
     if (!cb_->ok()) return false;
@@ -160,6 +205,7 @@ class LvxRowBlock : public ceres::CostFunction {
     for (int a = 0; a < nr; ++a) residuals[a] = r[a];
     if (!jacobians) return true;
     if (!cb_->have_jacobians()) return false;
+    if (cb_->mode() == JacobianRows::kBlocks) return scatter_record(jacobians);
     const int64_t row0 = cb_->first_row(spec_.family, spec_.index, nr);
     for (size_t k = 0; k < spec_.params.size(); ++k) {
       double* J = jacobians[k];
@@ -184,8 +230,77 @@ class LvxRowBlock : public ceres::CostFunction {
   const BlockSpec& spec() const { return spec_; }
 
  private:
+  // tangent scalar -> (parameter block, offset in its tangent): knots through their first-knot-relative index, the 22 calibration scalars through a fixed table,
+  // the landmark's rho; built once (the keys of a record are re-read on every Evaluate: a free time offset can move a block's interval)
+  struct Slot { int k = -1, d = 0; };
+  void build_table() {
+    const int N = cb_->n_knots();
+    int kmin = 1 << 30, kmax = -1;
+    for (const auto& p : spec_.params) if (p.tangent_off >= 0 && p.tangent_off < 6 * N) { kmin = std::min(kmin, p.tangent_off / 6); kmax = std::max(kmax, p.tangent_off / 6); }
+    kmin_ = kmax >= 0 ? kmin : 0;
+    knot_.assign(kmax >= 0 ? (size_t)(kmax - kmin + 1) * 2 : 0, -1);
+    for (size_t k = 0; k < spec_.params.size(); ++k) {
+      const ParamBlock& p = spec_.params[k];
+      if (p.tangent_off < 0) continue;
+      const int nt = p.quat ? 3 : p.size;
+      if (p.tangent_off < 6 * N) knot_[(size_t)(p.tangent_off / 6 - kmin_) * 2 + (p.tangent_off % 6 >= 3 ? 1 : 0)] = (int)k;
+      else if (p.tangent_off < 6 * N + 22) for (int d = 0; d < nt; ++d) calib_[p.tangent_off - 6 * N + d] = Slot{(int)k, d};
+      else { rho_g_ = p.tangent_off; rho_k_ = (int)k; }
+    }
+  }
+  Slot slot(int g, int N) const {
+    if (g < 0) return Slot{};
+    if (g < 6 * N) {
+      const int i = g / 6 - kmin_;
+      if (i < 0 || (size_t)i * 2 >= knot_.size()) return Slot{};
+      return Slot{knot_[(size_t)i * 2 + (g % 6 >= 3 ? 1 : 0)], g % 3};
+    }
+    if (g < 6 * N + 22) return calib_[g - 6 * N];
+    return g == rho_g_ ? Slot{rho_k_, 0} : Slot{};
+  }
+  // the block's record: each of its `width` columns added to the one parameter block it belongs to (columns in record order, as the debug route sums them)
+  bool scatter_record(double** jacobians) const {
+    const lvx_jacobian_blocks& B = cb_->blocks(spec_.family);
+    const int nr = spec_.num_residuals, W = B.width, N = cb_->n_knots();
+    if (spec_.index >= B.n_blocks || B.rows_per_block != nr || W > LVX_JAC_WIDTH) return false;
+    const int np = (int)spec_.params.size();
+    if (np > kMaxParams) return false;
+    double jt[kMaxParams][4][3];                         // tangent rows of the quaternion blocks
+    for (int k = 0; k < np; ++k) {
+      const ParamBlock& p = spec_.params[k];
+      if (jacobians[k]) for (int e = 0; e < nr * p.size; ++e) jacobians[k][e] = 0.0;
+      if (p.quat) for (int a = 0; a < nr; ++a) jt[k][a][0] = jt[k][a][1] = jt[k][a][2] = 0.0;
+      if (jacobians[k] && p.tangent_off < 0 && p.state_off >= 0) return false;   // a block lvx treats as constant was left variable in the Problem
+    }
+    const int32_t* key = B.keys + 3 * (int64_t)spec_.index;
+    if (key[0] >= 0) {                                   // (-1, -1, -1): not evaluated — zero rows, as the debug route's cleared rows
+      int32_t cols[LVX_JAC_WIDTH];
+      if (lvx_jacobian_block_cols(spec_.family, N, W, key, cols) != LVX_OK) return false;
+      const double* v = B.vals + (int64_t)spec_.index * nr * W;
+      for (int c = 0; c < W; ++c) {
+        const Slot s = slot(cols[c], N);
+        if (s.k < 0 || !jacobians[s.k]) continue;
+        const ParamBlock& p = spec_.params[s.k];
+        if (p.quat) for (int a = 0; a < nr; ++a) jt[s.k][a][s.d] += v[a * W + c];
+        else for (int a = 0; a < nr; ++a) jacobians[s.k][a * p.size + s.d] += v[a * W + c];
+      }
+    }
+    for (int k = 0; k < np; ++k) {
+      const ParamBlock& p = spec_.params[k];
+      double* J = jacobians[k];
+      if (!J || !p.quat || p.tangent_off < 0) continue;
+      const double* q = cb_->state() + p.state_off;     // J_ambient = J_tangent P(q)^T (see the default route below)
+      const double P[4][3] = {{q[3], q[2], -q[1]}, {-q[2], q[3], q[0]}, {q[1], -q[0], q[3]}, {-q[0], -q[1], -q[2]}};
+      for (int a = 0; a < nr; ++a) for (int c = 0; c < 4; ++c) J[a * 4 + c] = jt[k][a][0] * P[c][0] + jt[k][a][1] * P[c][1] + jt[k][a][2] * P[c][2];
+    }
+    return true;
+  }
+  static constexpr int kMaxParams = 64;
   const LvxEvaluationCallback* cb_;
   BlockSpec spec_;
+  int kmin_ = 0, rho_g_ = -1, rho_k_ = -1;
+  std::vector<int> knot_;                                // [knot - kmin][position | rotation] -> parameter block
+  std::array<Slot, 22> calib_{};
 };
 
 // ---------------------------------------------------------------------------------------------------------

@@ -25,7 +25,7 @@ LOCK_ACC_BIAS = 1 << 8
 LOCK_GYRO_BIAS = 1 << 9
 LOCK_LANDMARKS = 1 << 10
 
-EVAL_COST, EVAL_RESIDUALS, EVAL_NORMAL_EQ, EVAL_JACOBIAN = 1, 2, 4, 8
+EVAL_COST, EVAL_RESIDUALS, EVAL_NORMAL_EQ, EVAL_JACOBIAN, EVAL_JACOBIAN_BLOCKS = 1, 2, 4, 8, 16
 (FAM_GYRO, FAM_ACCEL, FAM_PRIOR, FAM_SURFEL, FAM_REPROJ, FAM_CAMSURF, KERNEL_FOLD, KERNEL_SOLVE, KERNEL_UPSTREAM, KERNEL_CLEAR, KERNEL_REP_JAC, KERNEL_REP_OBS,
  KERNEL_REP_REF, KERNEL_REP_CROSS, KERNEL_REP_LMROWS, KERNEL_REP_FUSED, KERNEL_FIXUP) = range(17)
 KERNEL_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf", "fold", "solve", "upstream", "clear", "reproj_jac", "reproj_obs", "reproj_ref", "reproj_cross", "reproj_lmrows", "reproj_fused", "fixup"]
@@ -36,6 +36,21 @@ class Pinhole(C.Structure):
     _fields_ = [("rows", C.c_int32), ("cols", C.c_int32), ("readout", C.c_double), ("fx", C.c_double), ("fy", C.c_double),
                 ("cx", C.c_double), ("cy", C.c_double), ("k1", C.c_double), ("k2", C.c_double), ("p1", C.c_double),
                 ("p2", C.c_double), ("k3", C.c_double)]
+
+
+class JacobianBlocks(C.Structure):
+    _fields_ = [("n_blocks", C.c_int64), ("rows_per_block", C.c_int32), ("width", C.c_int32), ("keys", C.c_void_p), ("vals", C.c_void_p),
+                ("keys_d", C.c_void_p), ("vals_d", C.c_void_p)]
+
+
+def jacobian_block_cols(family, n_knots, width, key):
+    """Tangent index of each of the `width` columns of a per-block record with keys (k0, k1, landmark), as lvx_jacobian_block_cols."""
+    k = _i(np.asarray(key).reshape(3))
+    out = np.zeros(width, dtype=np.int32)
+    rc = lib().lvx_jacobian_block_cols(C.c_int(family), C.c_int(n_knots), C.c_int(width), _p(k), _p(out))
+    if rc != 0:
+        raise LvxError(rc, "lvx_jacobian_block_cols")
+    return out
 
 
 class Layout(C.Structure):
@@ -195,11 +210,11 @@ class Context:
         return [int(v) for v in r]
 
     # --- evaluation ---
-    def evaluate(self, state, jac=False, normal_eq=False, dense=True, residuals=True):
+    def evaluate(self, state, jac=False, normal_eq=False, dense=True, residuals=True, jac_blocks=False):
         state = _d(state)
         assert state.size == self.state_size
         lo = self.layout()
-        what = EVAL_COST | (EVAL_RESIDUALS if residuals else 0) | (EVAL_NORMAL_EQ if normal_eq else 0) | (EVAL_JACOBIAN if jac else 0)
+        what = EVAL_COST | (EVAL_RESIDUALS if residuals else 0) | (EVAL_NORMAL_EQ if normal_eq else 0) | (EVAL_JACOBIAN if jac else 0) | (EVAL_JACOBIAN_BLOCKS if jac_blocks else 0)
         cost = C.c_double(0)
         res = np.zeros(lo["n_residuals"]) if residuals else None
         self._ck(self._l.lvx_evaluate(self._h, _p(state), C.c_uint32(what), C.byref(cost), _p(res)))
@@ -209,6 +224,8 @@ class Context:
             jv = np.zeros((lo["n_residuals"], JAC_WIDTH))
             self._ck(self._l.lvx_get_jacobian(self._h, _p(jc), _p(jv)))
             out["jac_cols"], out["jac_vals"] = jc, jv
+        if jac_blocks:
+            out["jac_blocks"] = [self.jacobian_blocks(f) for f in range(6)]
         if normal_eq and dense:
             nt = self.tangent_size
             H = np.zeros((nt, nt))
@@ -216,6 +233,17 @@ class Context:
             self._ck(self._l.lvx_get_normal_eq_dense(self._h, _p(H), _p(g)))
             out["H"], out["g"] = H, g
         return out
+
+    def jacobian_blocks(self, family):
+        """(keys [n][3], vals [n][rows_per_block][width]) of the last EVAL_JACOBIAN_BLOCKS evaluation for one family: numpy copies of lvx_get_jacobian_blocks."""
+        jb = JacobianBlocks()
+        self._ck(self._l.lvx_get_jacobian_blocks(self._h, C.c_int(family), C.byref(jb)))
+        n, nr, w = int(jb.n_blocks), int(jb.rows_per_block), int(jb.width)
+        if n == 0:
+            return np.zeros((0, 3), dtype=np.int32), np.zeros((0, nr, w))
+        keys = np.ctypeslib.as_array(C.cast(jb.keys, C.POINTER(C.c_int32)), shape=(n, 3)).copy()
+        vals = np.ctypeslib.as_array(C.cast(jb.vals, C.POINTER(C.c_double)), shape=(n, nr, w)).copy()
+        return keys, vals
 
     def gradient(self):
         """(g = J^T r, diag(J^T J)) of the last normal-equation evaluation in the tangent layout (any problem size)."""
