@@ -151,6 +151,25 @@ int lvx_get_family_rows(lvx_ctx* ctx, int64_t row0[LVX_NUM_FAM + 1]);
 int lvx_evaluate(lvx_ctx* ctx, const double* state, uint32_t what, double* cost, double* residuals);
 /* same, state already resident on the device; nothing is copied back except *cost (if not NULL) */
 int lvx_evaluate_d(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cost);
+/* Error statistics: what the reference prints around every optimisation stage (TrajectoryManagerLVI::printErrorStatistics, trajectory_manager_lvi.cpp:621-697) and what
+ * decides which surfels / landmarks to drop: per family the block counts, the cost share, the Huber outliers and the sums of the RAW error (the residual row divided by
+ * the family weight: unweighted, unrobustified), per surfel plane and per landmark the same over its blocks.  A value-only pass of its own (no Jacobians, no normal
+ * equations: it neither reads nor writes anything of lvx_evaluate) reduced on the device in a fixed order — two calls on one state give identical bits.  A block the
+ * evaluation cannot take (a time outside the spline, a non-unit quaternion) is not counted in n_evaluated and the call returns LVX_E_RANGE / LVX_E_NONUNIT_QUAT as
+ * lvx_evaluate does; `out` then still holds the sums over the blocks that were evaluated. */
+typedef struct lvx_family_stats {
+  int64_t n_blocks, n_evaluated, n_outliers;      /* outlier: squared norm of the weighted residual > huber^2 (Ceres HuberLoss); 0 for gyro / accel / prior */
+  double  cost;                                   /* sum over blocks of 0.5 * rho(||r||^2): the family's share of lvx_evaluate's cost */
+  double  sum[3], sum_abs[3], sum_sq[3], max_abs[3];   /* raw error per component; components the family does not have stay 0 */
+} lvx_family_stats;
+typedef struct lvx_error_stats { lvx_family_stats fam[LVX_NUM_FAM]; double cost; } lvx_error_stats;
+int lvx_error_statistics(lvx_ctx* ctx, const double* state, lvx_error_stats* out);
+/* state already on the device (NULL: the state of lvx_set_state); one host stop */
+int lvx_error_statistics_d(lvx_ctx* ctx, const double* state_d, lvx_error_stats* out);
+/* of the last statistics call; arrays of n_planes / n_landmarks as set by lvx_set_planes / lvx_set_landmarks; any pointer may be NULL.  A plane / landmark without
+ * (evaluated) blocks reports n = 0 and zeros.  LVX_E_STATE: no statistics call yet, or the problem changed since; LVX_E_ARG: another count than the tables'. */
+int lvx_get_plane_stats(lvx_ctx* ctx, int n_planes, int64_t* n, double* sum_abs, double* max_abs);        /* surfel family: |point-to-plane distance|, metres */
+int lvx_get_landmark_stats(lvx_ctx* ctx, int n_landmarks, int64_t* n, double* sum_sq, double* max_norm);  /* reprojection family: raw pixels, squared norm of the 2-vector */
 /* debug / parity: expand the structured normal equations into dense host arrays (n_tangent^2 and n_tangent); small problems only */
 int lvx_get_normal_eq_dense(lvx_ctx* ctx, double* H, double* g);
 /* g = J^T r and diag(J^T J) (robustified, tangent layout, 0 for constant scalars) of the last LVX_EVAL_NORMAL_EQ evaluation — what

@@ -106,6 +106,7 @@ void lvx_destroy(lvx_ctx* c) {
   (void)lvx_rccl_finalize(c);
   if (c->d_comm.p) (void)hipFree(c->d_comm.p);
   bcr_destroy(c);
+  stats_destroy(c);
   for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv}) if (b->p) (void)hipFree(b->p);
   for (auto& e : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);

@@ -157,6 +157,12 @@ struct lvx_ctx {
   hipEvent_t ev_xb[LVX_NUM_FAM] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   bool xb_valid = false;   // the last evaluation requested LVX_EVAL_JACOBIAN_BLOCKS and succeeded
   const double* last_state_d = nullptr; bool last_want_res = false, err_unchecked = false;   // see check_last_eval
+  // error statistics (lvx_stats.hip): the state copy of the host entry point, per-workgroup partial records, per-row raw errors (surfel rows in input order, reprojection
+  // blocks in device order), the results [family records | error word | plane n, sum |e|, max |e| | landmark n, sum |e|^2, max |e|] with their pinned host mirror, and the
+  // plane -> surfel rows lists [ptr (P + 1) | rows], built on the first statistics call after a layout change.  st_cfg / st_plist_cfg: cfg_version they belong to.
+  lvx::DevBuf d_st_state, d_st_part, d_st_val, d_st_out, d_st_plist;
+  double* h_st = nullptr; size_t h_st_cap = 0;
+  uint64_t st_cfg = 0, st_plist_cfg = 0; bool st_valid = false, st_plist_valid = false; int st_P = 0, st_L = 0;
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];
   size_t assoc_rings = 0; int assoc_wpr = 0, assoc_list_total = 0;
@@ -224,6 +230,7 @@ int bcr_forward(lvx_ctx* c, double* Zin, double* Zy, int ldz, int nrhs);
 int bcr_backward(lvx_ctx* c, double* Zy, double* Zx, int ldz, int nrhs);
 int bcr_gram(lvx_ctx* c, const double* Z, int ldz, int n, double* M, int row_major_nz = 0);
 void bcr_destroy(lvx_ctx* c);
+void stats_destroy(lvx_ctx* c);   // lvx_stats.hip
 // leaves + separators elimination (lvx_nd.h): nd_plan decides from the column profile whether it applies (nd_active afterwards) and sizes its buffers
 int nd_plan(lvx_ctx* c, int nrhs);
 bool nd_active(const lvx_ctx* c);

@@ -52,11 +52,13 @@ struct CalibrateOptions {
   double w_gyro = 28, w_acc = 18, w_surfel = 10, w_cam = 5, w_cam_surfel = 30;   // SetCalibWeights (lvi_initialize_surfel_orb.cpp:904-928)
   bool opt_time_offset = false;
   bool keep_history = false, keep_clouds = false;   // AssociationRecord per DataAssociation round (tests, diagnostics)
+  bool error_statistics = false;   // printErrorStatistics("Before optimization") / ("After optimization") around every stage's solve (trajectory_manager_lvi.cpp:339-342): StageReport::stats_before / stats_after
   int verbose = 1;
 };
 struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_surfel_points = 0, n_cam_surfel = 0;
                      std::vector<double> cost_history, radius_history; std::vector<int32_t> accepted;   // per-iteration trace of the stage's solve (lvx_lm_get_history)
-                     std::vector<double> state_in; };   // the state the stage's solve started from (CalibrateOptions::keep_history)
+                     std::vector<double> state_in;   // the state the stage's solve started from (CalibrateOptions::keep_history)
+                     bool has_stats = false; lvx_error_stats stats_before{}, stats_after{}; };   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
 struct AssociationRecord { std::vector<double> state; std::vector<lvx_surfel_plane> planes; std::vector<double> pt, pt_map, t; std::vector<int32_t> plane; std::vector<float> scans_in_map; };
@@ -239,7 +241,9 @@ class Calibrator {
     lvx_lm_options o; lvx_lm_default_options(&o); o.max_iterations = max_it; o.verbose = opt_.verbose > 1;
     lvx_lm_summary s{};
     if (opt_.keep_history) stage_state_in_ = *state;
+    if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_before_));
     check(lvx_lm_solve(ctx_, state->data(), &o, &s));
+    if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_after_));
     const int cap = 4 * max_it + 8;
     hist_cost_.assign((size_t)cap, 0.0); hist_radius_.assign((size_t)cap, 0.0); hist_acc_.assign((size_t)cap, 0);
     const int k = lvx_lm_get_history(ctx_, cap, hist_cost_.data(), hist_radius_.data(), hist_acc_.data());
@@ -247,7 +251,10 @@ class Calibrator {
     if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] solve: %d iterations, cost %.6e -> %.6e, termination %d\n", s.iterations, s.initial_cost, s.final_cost, s.termination);
     return s;
   }
-  void attach_history(StageReport* r) const { r->cost_history = hist_cost_; r->radius_history = hist_radius_; r->accepted = hist_acc_; r->state_in = stage_state_in_; }
+  void attach_history(StageReport* r) const {
+    r->cost_history = hist_cost_; r->radius_history = hist_radius_; r->accepted = hist_acc_; r->state_in = stage_state_in_;
+    r->has_stats = opt_.error_statistics; r->stats_before = stats_before_; r->stats_after = stats_after_;
+  }
   void check(int rc) {
     if (rc == LVX_OK) return;
     const std::string msg = ctx_ ? lvx_last_error(ctx_) : "lvx error";
@@ -263,6 +270,7 @@ class Calibrator {
   std::vector<int32_t> key_scans_;
   std::vector<double> sp_pt_, sp_map_, sp_t_; std::vector<int32_t> sp_plane_;
   int n_surfel_used_ = 0;
+  lvx_error_stats stats_before_{}, stats_after_{};
 };
 
 }  // namespace lvx_host

@@ -12,6 +12,7 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <sstream>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -30,6 +31,40 @@ struct OrientationMeasurement { double t; std::array<double, 4> q_wxyz; double w
 struct Summary { lvx_lm_summary lm; std::string BriefReport() const {
   static const char* term[] = {"NO_CONVERGENCE", "CONVERGENCE (function tolerance)", "CONVERGENCE (parameter tolerance)", "CONVERGENCE (gradient tolerance)", "NO_CONVERGENCE (max iterations)", "FAILURE"};
   return "lvx LM: iterations " + std::to_string(lm.iterations) + ", initial cost " + std::to_string(lm.initial_cost) + ", final cost " + std::to_string(lm.final_cost) + ", " + term[lm.termination]; } };
+
+// TrajectoryManagerLVI::printErrorStatistics (trajectory_manager_lvi.cpp:621-697) over the device-side statistics of lvx_error_statistics:
+//     ============== intro ================
+//     [Gyro]  Error size, average: N; x y z        mean |ErrorRaw| per axis (gyroscope_measurement.h:46-48)
+//     [Accel] Error size, average: N;  x y z       (accelerometer_measurement.h:49-51; the reference's two blanks)
+//     [LiDAR] Error size, average: N; d            mean |point2plane| (lidar_surfel_point.h:86-89)
+//     [CAMERA] Error size, average: N; u v         SIGNED mean of the weighted Error, as the reference sums it (cam_weight: the weight given to lvx_set_reproj — the sums
+//                                                  of lvx_error_stats are raw; 1 with the reference's argument swap, trajectory_manager_lvi.cpp:525)
+// A family without blocks prints no line, as in the reference.  The numbers are written the way Eigen's operator<< writes a row vector: stream precision (6
+// significant digits), one blank between coefficients, every coefficient right-aligned to the widest.  The sums start from zero (the reference's accumulators are
+// uninitialised); the mean is over the blocks that were evaluated.
+inline std::string FormatErrorStatistics(const std::string& intro, const lvx_error_stats& st, double cam_weight = 1.0) {
+  std::ostringstream os;
+  os << "============== " << intro << " ================\n";
+  auto row = [](const double* v, int n) {
+    std::string txt[3]; size_t w = 0;
+    for (int k = 0; k < n; ++k) { std::ostringstream o; o << v[k]; txt[k] = o.str(); w = txt[k].size() > w ? txt[k].size() : w; }
+    std::string out;
+    for (int k = 0; k < n; ++k) { if (k) out += " "; out += std::string(w - txt[k].size(), ' ') + txt[k]; }
+    return out;
+  };
+  auto line = [&](const char* head, const char* sep, const lvx_family_stats& f, int n, const double* sums, double scale) {
+    if (f.n_blocks <= 0) return;
+    const double d = f.n_evaluated > 0 ? (double)f.n_evaluated : 1.0;
+    double m[3] = {0, 0, 0};
+    for (int k = 0; k < n; ++k) m[k] = scale * sums[k] / d;
+    os << head << f.n_blocks << sep << row(m, n) << "\n";
+  };
+  line("[Gyro]  Error size, average: ", "; ", st.fam[LVX_FAM_GYRO], 3, st.fam[LVX_FAM_GYRO].sum_abs, 1.0);
+  line("[Accel] Error size, average: ", ";  ", st.fam[LVX_FAM_ACCEL], 3, st.fam[LVX_FAM_ACCEL].sum_abs, 1.0);
+  line("[LiDAR] Error size, average: ", "; ", st.fam[LVX_FAM_SURFEL], 1, st.fam[LVX_FAM_SURFEL].sum_abs, 1.0);
+  line("[CAMERA] Error size, average: ", "; ", st.fam[LVX_FAM_REPROJ], 2, st.fam[LVX_FAM_REPROJ].sum, cam_weight);
+  return os.str();
+}
 
 // SplitTrajectory + sensors live in one flat state vector (layout in lvx.h); the estimator writes results back into it in place,
 // as ceres does with the entities' parameter stores (dynamic_pstore.h:25-30).
@@ -73,6 +108,14 @@ class TrajectoryEstimator {
     double cost = 0;
     check(lvx_evaluate(ctx_, state_->data(), LVX_EVAL_COST | LVX_EVAL_RESIDUALS, &cost, residuals ? residuals->data() : nullptr));
     return cost;
+  }
+  // printErrorStatistics' numbers at the current state, reduced on the device (lvx_error_statistics): counts, cost share, Huber outliers and raw-error sums per family;
+  // print them with FormatErrorStatistics.  The per-plane / per-landmark arrays of the same call: lvx_get_plane_stats / lvx_get_landmark_stats on context().
+  lvx_error_stats ErrorStatistics() {
+    upload();
+    lvx_error_stats st{};
+    check(lvx_error_statistics(ctx_, state_->data(), &st));
+    return st;
   }
   lvx_ctx* context() { return ctx_; }
 

@@ -53,6 +53,18 @@ def jacobian_block_cols(family, n_knots, width, key):
     return out
 
 
+class FamilyStats(C.Structure):
+    _fields_ = [("n_blocks", C.c_int64), ("n_evaluated", C.c_int64), ("n_outliers", C.c_int64), ("cost", C.c_double),
+                ("sum", C.c_double * 3), ("sum_abs", C.c_double * 3), ("sum_sq", C.c_double * 3), ("max_abs", C.c_double * 3)]
+
+
+class ErrorStats(C.Structure):
+    _fields_ = [("fam", FamilyStats * 6), ("cost", C.c_double)]
+
+
+FAMILY_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf"]
+
+
 class Layout(C.Structure):
     _fields_ = [("n_knots", C.c_int32), ("n_landmarks", C.c_int32), ("n_tangent", C.c_int32), ("n_band", C.c_int32),
                 ("bandwidth", C.c_int32), ("n_border", C.c_int32), ("border_ld", C.c_int32), ("n_hub_knots", C.c_int32), ("hub_knot0", C.c_int32),
@@ -156,6 +168,7 @@ class Context:
     def set_planes(self, pi3):
         pi3 = _d(pi3)
         self._ck(self._l.lvx_set_planes(self._h, C.c_int(len(pi3)), _p(pi3)))
+        self._n_planes = len(pi3)
 
     def set_surfel(self, pt, t, plane_id, t_map, huber, w):
         pt, t, plane_id = _d(pt), _d(t), _i(plane_id)
@@ -164,6 +177,7 @@ class Context:
     def set_landmarks(self, uv_ref, t0_ref):
         uv_ref, t0_ref = _d(uv_ref), _d(t0_ref)
         self._ck(self._l.lvx_set_landmarks(self._h, C.c_int(len(t0_ref)), _p(uv_ref), _p(t0_ref)))
+        self._n_landmarks = len(t0_ref)
 
     def set_reproj(self, lm, uv_obs, t0_obs, huber, w):
         lm, uv_obs, t0_obs = _i(lm), _d(uv_obs), _d(t0_obs)
@@ -175,6 +189,9 @@ class Context:
 
     def set_locks(self, mask):
         self._ck(self._l.lvx_set_locks(self._h, C.c_uint32(mask)))
+
+    def set_time_offset_bounds(self, imu_max, sensor_max):
+        self._ck(self._l.lvx_set_time_offset_bounds(self._h, C.c_double(imu_max), C.c_double(sensor_max)))
 
     def voxel_info(self):
         """Grid geometry and leaf count of the last voxel build (waits for an asynchronous lvx_voxel_build_d)."""
@@ -233,6 +250,41 @@ class Context:
             self._ck(self._l.lvx_get_normal_eq_dense(self._h, _p(H), _p(g)))
             out["H"], out["g"] = H, g
         return out
+
+    def error_statistics(self, state=None, raw=False):
+        """Per-family error statistics at `state` (None: the resident state of set_state), reduced on the device: a dict per family name (FAMILY_NAMES) with
+        n_blocks, n_evaluated, n_outliers, cost and the per-component sum / sum_abs / sum_sq / max_abs of the raw (unweighted) error, plus "cost" (the total).
+        A block that cannot be evaluated raises LvxError(E_RANGE / E_NONUNIT_QUAT) like evaluate(); raw=True returns (code, dict, the ctypes struct) instead."""
+        st = ErrorStats()
+        if state is None:
+            rc = self._l.lvx_error_statistics_d(self._h, None, C.byref(st))
+        else:
+            state = _d(state)
+            assert state.size == self.state_size
+            rc = self._l.lvx_error_statistics(self._h, _p(state), C.byref(st))
+        out = {"cost": st.cost}
+        for f, name in enumerate(FAMILY_NAMES):
+            fs = st.fam[f]
+            out[name] = dict(n_blocks=int(fs.n_blocks), n_evaluated=int(fs.n_evaluated), n_outliers=int(fs.n_outliers), cost=fs.cost,
+                             sum=np.array(fs.sum), sum_abs=np.array(fs.sum_abs), sum_sq=np.array(fs.sum_sq), max_abs=np.array(fs.max_abs))
+        if raw:
+            return rc, out, st
+        self._ck(rc)
+        return out
+
+    def plane_stats(self, n_planes=None):
+        """(n, sum_abs, max_abs) per surfel plane of the last error_statistics call: evaluated rows, sum and maximum of |point-to-plane distance| [m]."""
+        n_planes = getattr(self, "_n_planes", 0) if n_planes is None else n_planes
+        n = np.zeros(n_planes, dtype=np.int64); s = np.zeros(n_planes); m = np.zeros(n_planes)
+        self._ck(self._l.lvx_get_plane_stats(self._h, C.c_int(n_planes), _p(n), _p(s), _p(m)))
+        return n, s, m
+
+    def landmark_stats(self, n_landmarks=None):
+        """(n, sum_sq, max_norm) per landmark of the last error_statistics call: evaluated reprojection blocks, sum of the squared raw pixel error, largest error norm."""
+        n_landmarks = getattr(self, "_n_landmarks", 0) if n_landmarks is None else n_landmarks
+        n = np.zeros(n_landmarks, dtype=np.int64); s = np.zeros(n_landmarks); m = np.zeros(n_landmarks)
+        self._ck(self._l.lvx_get_landmark_stats(self._h, C.c_int(n_landmarks), _p(n), _p(s), _p(m)))
+        return n, s, m
 
     def jacobian_blocks(self, family):
         """(keys [n][3], vals [n][rows_per_block][width]) of the last EVAL_JACOBIAN_BLOCKS evaluation for one family: numpy copies of lvx_get_jacobian_blocks."""
