@@ -510,6 +510,41 @@ int lvx_evaluate_lidar_pose(lvx_ctx* ctx, const double* state, int n, const doub
 int lvx_undistort_scan(lvx_ctx* ctx, const double* state, int n, const lvx_point_xyzit* raw, const double* q_G_to_target_xyzw, const double* p_target_in_G3,
                        int correct_position, float* out_xyzi4);
 
+/* coloured map and LiDAR-to-image overlay ---------------------------------------------------------------------------------*/
+/* TrajectoryManagerLVI::evaluateCameraPose for a batch of times (trajectory_manager_lvi.cpp:430-440): q_CtoG (x,y,z,w), p_CinG, valid = 0 outside the spline */
+int lvx_evaluate_camera_pose(lvx_ctx* ctx, const double* state, int n, const double* t, double* q_xyzw4, double* p3, int32_t* valid);
+/* pcl::PointXYZRGB as LIinitializer::RenderMap fills it (src/lvi_exc/test/lvi_initialize_surfel_orb.cpp:759-762, 785-788), 16 bytes.  a = 255 for a coloured point and 0
+ * otherwise: "never coloured" and "sampled a black pixel" differ.  A skipped point (NaN coordinate, depth outside [z_min, z_max] in every image) is all zero, as the
+ * resize()'d cloud of the reference (:715); a point in depth range but outside the image keeps its xyz with colour 0. */
+typedef struct lvx_point_xyzrgb { float x, y, z; uint8_t b, g, r, a; } lvx_point_xyzrgb;
+#define LVX_RENDER_MAX_IMAGES 32
+typedef struct lvx_render_options { double z_min, z_max; int32_t reserved[2]; } lvx_render_options;   /* 0.1, 15 (:757) */
+int lvx_render_default_options(lvx_render_options* opt);
+/* LIinitializer::RenderMap (lvi_initialize_surfel_orb.cpp:711-811): every map point (LiDAR frame at map_time, float xyzi) goes through the calibrated chain
+ * T_L0inG (evaluateLidarPose(map_time), :720-727) and T_GtoC (evaluateCameraPose(image_t), :738-747, rigid inverse) and the inline radtan projection (:766-779) and takes the
+ * grey value of the pixel int(uv) (:781-788).  images: n_images (1 .. LVX_RENDER_MAX_IMAGES) grey images [rows][pitch] back to back, rows / cols from lvx_set_camera,
+ * pitch >= cols.  The reference colours from ONE image (the first candidate whose pose evaluates, :738-741,800); with several, a point takes its colour from the
+ * LOWEST-index image whose pose is valid and in which it is in depth range and inside the image — with one image that is the reference exactly.
+ * image_valid[i] = 0: image_t[i] lies outside the spline (the reference's `continue`, :738-741; not an error).  *n_colored = points with a = 255.
+ * LVX_E_RANGE: map_time outside the spline (the early return of :720-723); out is zeroed, image_valid and *n_colored are 0.  LVX_E_STATE: no spline / no camera.
+ * LVX_E_ARG: n_images outside 1 .. 32, pitch < cols, a required pointer is NULL.  n = 0: LVX_OK, nothing written.  opt may be NULL (defaults).
+ * map_xyzi4 == NULL: the cloud is the de-skewed scans the last lvx_data_association(_poses) of this context left on the device ([n_scans][H][W] points, nothing is
+ * uploaded; n is ignored and out holds that many records); LVX_E_STATE before any association. */
+int lvx_render_map(lvx_ctx* ctx, const double* state, double map_time, int n, const float* map_xyzi4, int n_images, const uint8_t* images, int pitch, const double* image_t,
+                   const lvx_render_options* opt, lvx_point_xyzrgb* out, int32_t* image_valid, int64_t* n_colored);
+/* The same with the cloud, the images and the records in device memory (state, image_t, image_valid, n_colored stay host pointers).  map_xyzi4_d == NULL: the cloud is the
+ * de-skewed scans of the last lvx_data_association(_poses) of this context ([n_scans][H][W] points; n is ignored, out_d holds that many records); LVX_E_STATE before any
+ * association. */
+int lvx_render_map_d(lvx_ctx* ctx, const double* state, double map_time, int n, const float* map_xyzi4_d, int n_images, const uint8_t* images_d, int pitch, const double* image_t,
+                     const lvx_render_options* opt, lvx_point_xyzrgb* out_d, int32_t* image_valid, int64_t* n_colored);
+/* LIinitializer::ReprojectPointCloudToImage (lvi_initialize_surfel_orb.cpp:1307-1363) for n_pairs (scan, image) pairs: scan scan_index[i] of lvx_set_scans (the scans the last
+ * data association ran on), rotation-only de-skewed into its own frame at scan_t[i] (ScanUndistortion::undistortScan, scan_undistortion.h:40-57 — the scan_data_ the
+ * reference iterates, :1314,1342), is moved with q_LtoC = q_CtoG* (x) q_LtoG, p_LinC = q_CtoG* (p_LinG - p_CinG) (:1333-1336; LiDAR pose at scan_t[i], camera pose at
+ * image_t[i]) and projected (:1343-1353: z < 0 skipped, uv < 0 outside, int(uv) > cols - 1 / rows - 1 outside; the projection is RenderMap's radtan formula).
+ * mask[i][rows][cols] (host): 1 where a point lands (what the reference paints green), 0 elsewhere.  valid[i] = 0 and an all-zero mask: a pose outside the spline.
+ * LVX_E_STATE: no spline / camera / scans; LVX_E_ARG: a scan index outside the scans, a NULL pointer.  n_pairs = 0: LVX_OK. */
+int lvx_overlay_scans(lvx_ctx* ctx, const double* state, int n_pairs, const int32_t* scan_index, const double* scan_t, const double* image_t, uint8_t* mask, int32_t* valid);
+
 #ifdef __cplusplus
 }
 #endif

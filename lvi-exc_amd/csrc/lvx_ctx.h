@@ -163,6 +163,8 @@ struct lvx_ctx {
   lvx::DevBuf d_st_state, d_st_part, d_st_val, d_st_out, d_st_plist;
   double* h_st = nullptr; size_t h_st_cap = 0;
   uint64_t st_cfg = 0, st_plist_cfg = 0; bool st_valid = false, st_plist_valid = false; int st_P = 0, st_L = 0;
+  // coloured map / overlay (lvx_render.hip): [0] times + pose table + counter, [1] state, [2] cloud or pair block, [3] images or poses, [4] records or masks
+  lvx::DevBuf d_rn[5];
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];
   size_t assoc_rings = 0; int assoc_wpr = 0, assoc_list_total = 0;

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "lvx_ctx.h"
+#include "lvx_pose.h"
 #include "lvx_stdsort.h"
 
 namespace lvx {
@@ -1746,41 +1747,7 @@ __global__ __launch_bounds__(SE_COLS) void k_assoc_emit_fused(const int* __restr
 // ------------------------------------------------------------------------------------------------------------------------
 // batched lidar pose evaluation + scan de-skew: HBM-streaming reuse of the spline evaluator (no Jacobians)
 // ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool lidar_pose_dev(const double* state, int N, double t0, double dt, double t, quat* q_LtoG, v3* p_LinG) {
-  const double* sl = state + 7 * (size_t)N + 16;
-  const double tt = t + sl[7];
-  const double tmax = t0 + (double)(N - 3) * dt;
-  if (t0 > tt || tmax <= tt) return false;                         // evaluateLidarPose range test (trajectory_manager_lvi.cpp:401-402)
-  const double s = (tt - t0) / dt;
-  const int i0 = (int)floor(s);
-  if (N < 4 || i0 < 0 || i0 > N - 4) return false;
-  const SplineRef sp{t0, dt, N, state, state + 3 * (size_t)N};
-  KnotRef k; k.i0 = i0; k.u = s - (double)i0;
-  PoseEval e;
-  if (!pose_eval<false>(sp, k, &e)) return false;
-  const quat qL = load_q(sl); const v3 pL = load_v3(sl + 4);
-  *q_LtoG = qmul(e.so3.q, qL);
-  *p_LinG = qrot(e.so3.q, pL) + e.p;
-  return true;
-}
-// evaluateCameraPose (trajectory_manager_lvi.cpp:430-440)
-__device__ __forceinline__ bool camera_pose_dev(const double* state, int N, double t0, double dt, double t, quat* q_CtoG, v3* p_CinG) {
-  const double* sc = state + 7 * (size_t)N + 24;
-  const double tt = t + sc[7];
-  const double tmax = t0 + (double)(N - 3) * dt;
-  if (t0 > tt || tmax <= tt) return false;
-  const double s = (tt - t0) / dt;
-  const int i0 = (int)floor(s);
-  if (N < 4 || i0 < 0 || i0 > N - 4) return false;
-  const SplineRef sp{t0, dt, N, state, state + 3 * (size_t)N};
-  KnotRef k; k.i0 = i0; k.u = s - (double)i0;
-  PoseEval e;
-  if (!pose_eval<false>(sp, k, &e)) return false;
-  const quat qC = load_q(sc); const v3 pC = load_v3(sc + 4);
-  *q_CtoG = qmul(e.so3.q, qC);
-  *p_CinG = qrot(e.so3.q, pC) + e.p;
-  return true;
-}
+// lidar_pose_dev / camera_pose_dev (evaluateLidarPose / evaluateCameraPose): lvx_pose.h, shared with lvx_render.hip
 // associateVisualPointsWithPlanes (surfel_association.cpp:161-214): thread = landmark; its reference observation is back-projected at depth 1 / rho with the
 // camera pose at the view's t0, moved into the LiDAR map frame (pose of the camera at the map time, q_LtoC / t_LinC), and tested against every surfel:
 // strictly inside the AABB and within 2 radius of the plane; the last (highest) matching surfel stays, as in the reference's loop.

@@ -63,6 +63,38 @@ struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_su
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
 struct AssociationRecord { std::vector<double> state; std::vector<lvx_surfel_plane> planes; std::vector<double> pt, pt_map, t; std::vector<int32_t> plane; std::vector<float> scans_in_map; };
 
+// LIinitializer::ReprojectPointCloudToImage's image choice (lvi_initialize_surfel_orb.cpp:1319-1327): per scan the FIRST image with img_t > scan_t and |img_t - scan_t| < 0.05,
+// or -1
+inline std::vector<int32_t> MatchScanImages(const std::vector<double>& scan_t, const std::vector<double>& image_t) {
+  std::vector<int32_t> idx(scan_t.size(), -1);
+  for (size_t j = 0; j < scan_t.size(); ++j)
+    for (size_t i = 0; i < image_t.size(); ++i)
+      if (image_t[i] > scan_t[j] && std::fabs(image_t[i] - scan_t[j]) < 0.05) { idx[j] = (int32_t)i; break; }
+  return idx;
+}
+// RenderMap's candidate images (:729-733): i = 50, 50 + step, ... with step = size / 10 (a step of 0 — fewer than 10 images — would never advance: one candidate then)
+inline std::vector<int32_t> RenderCandidates(size_t n_images) {
+  std::vector<int32_t> c;
+  const size_t step = n_images / 10;
+  for (size_t i = 50; i < n_images && c.size() < (size_t)LVX_RENDER_MAX_IMAGES; i += step) { c.push_back((int32_t)i); if (step == 0) break; }
+  return c;
+}
+// pcl::io::savePCDFileASCII of a PointXYZRGB cloud (:804): fields x y z rgb, unorganised (WIDTH n, HEIGHT 1).  The packed colour (a << 24 | r << 16 | g << 8 | b) is
+// written as PCL >= 1.9 does, an unsigned integer with TYPE U (older writers print the same four bytes as a float, which is a NaN pattern for a = 255 and does not
+// survive a text round trip); pcl::io::loadPCDFile reads both.
+inline bool WritePcdAscii(const std::string& path, const std::vector<lvx_point_xyzrgb>& cloud) {
+  std::FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return false;
+  std::fprintf(f, "# .PCD v0.7 - Point Cloud Data file format\nVERSION 0.7\nFIELDS x y z rgb\nSIZE 4 4 4 4\nTYPE F F F U\nCOUNT 1 1 1 1\nWIDTH %zu\nHEIGHT 1\nVIEWPOINT 0 0 0 1 0 0 0\nPOINTS %zu\nDATA ascii\n",
+               cloud.size(), cloud.size());
+  for (const lvx_point_xyzrgb& p : cloud) {
+    const uint32_t rgb = (uint32_t)p.b | ((uint32_t)p.g << 8) | ((uint32_t)p.r << 16) | ((uint32_t)p.a << 24);
+    std::fprintf(f, "%.9g %.9g %.9g %u\n", p.x, p.y, p.z, (unsigned)rgb);
+  }
+  return std::fclose(f) == 0;
+}
+struct RenderResult { std::vector<lvx_point_xyzrgb> cloud; std::vector<int32_t> candidates, valid; int64_t n_colored = 0; };
+
 class Calibrator {
  public:
   // `in` is copied: the calibrator may outlive the caller's object
@@ -106,6 +138,38 @@ class Calibrator {
     rep.push_back(Solve0(state));
     rep.push_back(SolveVisual(state));
     return rep;
+  }
+  // LIinitializer::RenderMap (lvi_initialize_surfel_orb.cpp:711-811) at `state`, on the de-skewed scans the last DataAssociation round left on the device (nothing is
+  // downloaded but the records).  images[i]: grey, [rows][cols] of CalibrateInput::camera; the candidates are the reference's (RenderCandidates); a candidate whose time
+  // lies outside the spline is passed over, the first valid one colours (with several valid ones: the lowest that sees the point).
+  RenderResult RenderMap(const std::vector<double>& state, const std::vector<std::vector<uint8_t>>& images, const std::vector<double>& image_t) {
+    if (images.size() != image_t.size()) throw std::invalid_argument("RenderMap: one time per image");
+    RenderResult r; r.candidates = RenderCandidates(images.size());
+    if (r.candidates.empty()) return r;
+    const size_t px = (size_t)in_.camera.rows * in_.camera.cols;
+    std::vector<uint8_t> pack(r.candidates.size() * px); std::vector<double> t(r.candidates.size());
+    for (size_t k = 0; k < r.candidates.size(); ++k) {
+      const std::vector<uint8_t>& im = images[(size_t)r.candidates[k]];
+      if (im.size() != px) throw std::invalid_argument("RenderMap: image size does not match the camera");
+      std::copy(im.begin(), im.end(), pack.begin() + k * px); t[k] = image_t[(size_t)r.candidates[k]];
+    }
+    r.cloud.assign(in_.scans.size() * (size_t)in_.H * in_.W, lvx_point_xyzrgb{});
+    r.valid.assign(r.candidates.size(), 0);
+    check(lvx_render_map(ctx_, state.data(), in_.map_time, 0, nullptr, (int)r.candidates.size(), pack.data(), in_.camera.cols, t.data(), nullptr, r.cloud.data(), r.valid.data(), &r.n_colored));
+    return r;
+  }
+  // LIinitializer::ReprojectPointCloudToImage (:1307-1363): every scan with a matching image (MatchScanImages) drawn into it; masks [pairs][rows][cols], 1 where a point
+  // lands; scan_of_pair / image_of_pair say which pair a mask belongs to, valid[i] = 0: a pose outside the spline (the mask is zero)
+  struct Overlay { std::vector<int32_t> scan_of_pair, image_of_pair, valid; std::vector<uint8_t> masks; };
+  Overlay OverlayScans(const std::vector<double>& state, const std::vector<double>& scan_t, const std::vector<double>& image_t) {
+    if (scan_t.size() != in_.scans.size()) throw std::invalid_argument("OverlayScans: one time per scan");
+    Overlay o;
+    const std::vector<int32_t> m = MatchScanImages(scan_t, image_t);
+    std::vector<double> st, it;
+    for (size_t j = 0; j < m.size(); ++j) if (m[j] >= 0) { o.scan_of_pair.push_back((int32_t)j); o.image_of_pair.push_back(m[j]); st.push_back(scan_t[j]); it.push_back(image_t[(size_t)m[j]]); }
+    o.valid.assign(st.size(), 0); o.masks.assign(st.size() * (size_t)in_.camera.rows * in_.camera.cols, 0);
+    if (!st.empty()) check(lvx_overlay_scans(ctx_, state.data(), (int)st.size(), o.scan_of_pair.data(), st.data(), it.data(), o.masks.data(), o.valid.data()));
+    return o;
   }
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }

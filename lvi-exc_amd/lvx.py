@@ -832,6 +832,74 @@ def undistort(ctx, state, raw, q_G_to_target, p_target_in_G, correct_position=Tr
     return out
 
 
+def eval_camera_pose(ctx, state, t):
+    """Batched evaluateCameraPose (lvx_evaluate_camera_pose): q_CtoG (x, y, z, w), p_CinG, valid."""
+    state, t = _d(state), _d(np.atleast_1d(t))
+    n = len(t)
+    q, p, ok = np.zeros((n, 4)), np.zeros((n, 3)), np.zeros(n, np.int32)
+    ctx._ck(ctx._l.lvx_evaluate_camera_pose(ctx._h, _p(state), C.c_int(n), _p(t), _p(q), _p(p), _p(ok)))
+    return q, p, ok.astype(bool)
+
+
+POINT_XYZRGB = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("b", "u1"), ("g", "u1"), ("r", "u1"), ("a", "u1")])   # lvx_point_xyzrgb (pcl::PointXYZRGB order)
+RENDER_MAX_IMAGES = 32
+
+
+class RenderOptions(C.Structure):
+    """lvx_render_options: the depth limits of RenderMap (0.1, 15)."""
+    _fields_ = [("z_min", C.c_double), ("z_max", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+def render_default_options(ctx, **kw):
+    o = RenderOptions()
+    ctx._ck(ctx._l.lvx_render_default_options(C.byref(o)))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def _render_images(images):
+    images = np.ascontiguousarray(images, dtype=np.uint8)
+    if images.ndim == 2:
+        images = images[None]
+    assert images.ndim == 3
+    return images
+
+
+def render_map(ctx, state, map_time, map_xyzi, images, image_t, options=None, n_resident=0):
+    """RenderMap with host buffers (lvx_render_map).  map_xyzi [n][4] float32, images [n_images][rows][pitch] uint8 (pitch >= cols), image_t [n_images].
+    map_xyzi = None: the de-skewed scans of the last data association, n_resident = n_scans * H * W records.
+    Returns (records POINT_XYZRGB [n], image_valid [n_images] bool, n_colored).  A map time outside the spline raises LvxError(E_RANGE)."""
+    pts = np.ascontiguousarray(map_xyzi, dtype=np.float32).reshape(-1, 4) if map_xyzi is not None else None
+    images, image_t = _render_images(images), _d(np.atleast_1d(image_t))
+    assert len(image_t) == images.shape[0]
+    out = np.zeros(len(pts) if pts is not None else n_resident, dtype=POINT_XYZRGB)
+    valid, ncol = np.zeros(len(image_t), np.int32), C.c_int64(0)
+    ctx._ck(ctx._l.lvx_render_map(ctx._h, _p(_d(state)), C.c_double(map_time), C.c_int(len(out)), _p(pts), C.c_int(len(image_t)), _p(images), C.c_int(images.shape[2]), _p(image_t),
+                                  C.byref(options) if options is not None else None, _p(out), _p(valid), C.byref(ncol)))
+    return out, valid.astype(bool), ncol.value
+
+
+def render_map_d(ctx, state, map_time, images_d_ptr, n_images, pitch, image_t, out_d_ptr, map_d_ptr=None, n=0, options=None):
+    """RenderMap on device-resident buffers (lvx_render_map_d): images_d_ptr / out_d_ptr / map_d_ptr are device addresses (e.g. torch.Tensor.data_ptr()).  map_d_ptr = None:
+    the de-skewed scans of the last data association of this context (n_scans * H * W records are written).  Returns (image_valid, n_colored)."""
+    image_t = _d(np.atleast_1d(image_t))
+    assert len(image_t) == n_images
+    valid, ncol = np.zeros(n_images, np.int32), C.c_int64(0)
+    ctx._ck(ctx._l.lvx_render_map_d(ctx._h, _p(_d(state)), C.c_double(map_time), C.c_int(n), C.c_void_p(map_d_ptr) if map_d_ptr else None, C.c_int(n_images), C.c_void_p(images_d_ptr),
+                                    C.c_int(pitch), _p(image_t), C.byref(options) if options is not None else None, C.c_void_p(out_d_ptr), _p(valid), C.byref(ncol)))
+    return valid.astype(bool), ncol.value
+
+
+def overlay_scans(ctx, state, scan_index, scan_t, image_t, rows, cols):
+    """ReprojectPointCloudToImage for (scan, image) pairs (lvx_overlay_scans); rows / cols as given to set_camera.  Returns (mask [n_pairs][rows][cols] uint8, valid bool)."""
+    idx, scan_t, image_t = _i(np.atleast_1d(scan_index)), _d(np.atleast_1d(scan_t)), _d(np.atleast_1d(image_t))
+    assert len(idx) == len(scan_t) == len(image_t)
+    mask, valid = np.zeros((len(idx), rows, cols), np.uint8), np.zeros(len(idx), np.int32)
+    ctx._ck(ctx._l.lvx_overlay_scans(ctx._h, _p(_d(state)), C.c_int(len(idx)), _p(idx), _p(scan_t), _p(image_t), _p(mask), _p(valid)))
+    return mask, valid.astype(bool)
+
+
 def load_problem(obj, P, locks=None):
     """Feed a synth.make_problem() dict into an lvx.Context or an oracle.Oracle (same setter names)."""
     obj.set_spline(P["t0"], P["dt"], P["n_knots"])
