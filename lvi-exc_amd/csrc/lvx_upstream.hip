@@ -955,6 +955,33 @@ __device__ __forceinline__ void ndt_block_reduce(double* acc, double* part, int*
 // reference's order of operations, double accumulation.  XF: the transformed point is computed here from the source point (the loop of lvx_ndt_align); otherwise it is
 // read from trn (lvx_ndt_derivatives: the caller transformed the cloud).
 struct NdtConst { float j_ang[8][3]; float h_ang[15][3]; float gd2; double gauss_d1; };
+// exp of a float as the host's libm rounds it, which the device's expf (1 ulp) does not: the well-known evaluation through double (exp(x) = 2^(k/32) * 2^r', k =
+// round(32 x / ln 2), a cubic in the remainder, one rounding to float at the end), stated here in IEEE double operations without contraction, so that it gives the same
+// bits on either side.  Compared with glibc 2.35's expf over every float of |x| < 87, it differs in 2 of 2.2e9.  The registration loop needs that: at 0.5 m its first
+// Hessians are indefinite and 1-ulp differences among the exponentials (5e-8 of an evaluation) move the final vector by up to 3e-6.
+// ndt_exp2_32[i] = bits of 2^(i/32) - (i << 47): the exponent that k's low five bits would add is taken off again.
+__constant__ unsigned long long ndt_exp2_32[32] = {
+    0x3ff0000000000000ull, 0x3fefd9b0d3158574ull, 0x3fefb5586cf9890full, 0x3fef9301d0125b51ull, 0x3fef72b83c7d517bull, 0x3fef54873168b9aaull, 0x3fef387a6e756238ull,
+    0x3fef1e9df51fdee1ull, 0x3fef06fe0a31b715ull, 0x3feef1a7373aa9cbull, 0x3feedea64c123422ull, 0x3feece086061892dull, 0x3feebfdad5362a27ull, 0x3feeb42b569d4f82ull,
+    0x3feeab07dd485429ull, 0x3feea47eb03a5585ull, 0x3feea09e667f3bcdull, 0x3fee9f75e8ec5f74ull, 0x3feea11473eb0187ull, 0x3feea589994cce13ull, 0x3feeace5422aa0dbull,
+    0x3feeb737b0cdc5e5ull, 0x3feec49182a3f090ull, 0x3feed503b23e255dull, 0x3feee89f995ad3adull, 0x3feeff76f2fb5e47ull, 0x3fef199bdd85529cull, 0x3fef3720dcef9069ull,
+    0x3fef5818dcfba487ull, 0x3fef7c97337b9b5full, 0x3fefa4afa2a490daull, 0x3fefd0765b6e4540ull};
+__device__ __forceinline__ float ndt_expf(float x) {
+  if (!(fabsf(x) < 87.0f)) return expf(x);   // overflow, underflow into the subnormals, NaN: the library's own handling
+  const double inv_ln2_n = 0x1.71547652b82fep+0 * 32, shift = 0x1.8p+52;
+  const double c0 = 0x1.c6af84b912394p-5 / 32 / 32 / 32, c1 = 0x1.ebfce50fac4f3p-3 / 32 / 32, c2 = 0x1.62e42ff0c52d6p-1 / 32;
+  double z = inv_ln2_n * (double)x;
+  double kd = z + shift;                     // round to nearest even in the low bits of the sum
+  const unsigned long long ki = (unsigned long long)__double_as_longlong(kd);
+  kd -= shift;
+  const double r = z - kd;
+  const double s = __longlong_as_double((long long)(ndt_exp2_32[ki & 31] + (ki << 47)));
+  z = c0 * r + c1;
+  const double r2 = r * r;
+  double y = c2 * r + 1;
+  y = z * r2 + y;
+  return (float)(y * s);
+}
 template <int NB, bool XF>
 __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, const float4* trn, NdtMat M, int n, float leaf, int min_pts, VxGrid g, const int* grid, const int* leaf_n,
                                                          const double* mean, const double* icov, NdtConst K, int compute_hessian, double* part, int* ticket, double* out43) {
@@ -1010,7 +1037,7 @@ __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, cons
 #pragma unroll
       for (int cc = 0; cc < 3; ++cc) xc[cc] = (x4[0] * ci[0][cc] + x4[1] * ci[1][cc]) + x4[2] * ci[2][cc];
       const float q = (x4[0] * xc[0] + x4[1] * xc[1]) + x4[2] * xc[2];
-      float e_x = expf(-K.gd2 * q * 0.5f);
+      float e_x = ndt_expf(-K.gd2 * q * 0.5f);
       const float score_inc = (float)(-K.gauss_d1 * e_x);
       e_x = K.gd2 * e_x;
       if (e_x > 1 || e_x < 0 || e_x != e_x) continue;
