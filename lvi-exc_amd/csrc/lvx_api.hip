@@ -18,6 +18,7 @@ const SwitchName* switch_table(int* count) {
     {"CLEAR_ALL", &Switches::clear_all, false}, {"SOLVER_SEQ", &Switches::solver_seq, false}, {"SOLVER_TIMING", &Switches::solver_timing, false},
     {"CHUNK_R", &Switches::chunk_r, true}, {"CHUNK_R_IMU", &Switches::chunk_r_imu, true}, {"CHUNK_R_REP", &Switches::chunk_r_rep, true}, {"CHUNK_ROWS", &Switches::chunk_rows, true}, {"REP_ROWS", &Switches::rep_rows, true}, {"REP_FUSED", &Switches::rep_fused, true}, {"SOLVER_ND", &Switches::solver_nd, false},
     {"DA_SYNC", &Switches::da_sync, false},   // lvx_data_association: always the synchronous chain (four host stops), never the speculative one
+    {"TEST_BAD_PIVOT", &Switches::test_bad_pivot, false},   // lvx_solve_step: declare a pivot failure where there was none (the tests' way into the sequential redo)
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;
@@ -62,6 +63,7 @@ int lvx_create(lvx_ctx** out, int device, uint32_t /*flags*/) {
   lvx_ctx* c = new (std::nothrow) lvx_ctx();
   if (!c) return LVX_E_ALLOC;
   c->device = device;
+  { int ncu = 0; if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->n_cu = ncu; }
   read_env_switches(c);
   if (hipStreamCreate(&c->own_stream) != hipSuccess) { delete c; return LVX_E_HIP; }
   c->stream = c->own_stream;

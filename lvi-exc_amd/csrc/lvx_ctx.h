@@ -65,9 +65,9 @@ struct DevBuf {
 };
 
 // Experiment / debug switches: read ONCE from the environment (LVX_<NAME>) when the context is created and changed afterwards only
-// through lvx_set_switch — the evaluation path never calls getenv.
+// through lvx_set_switch — the evaluation and solve paths never call getenv.
 struct Switches {
-  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0;   // rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
+  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0, test_bad_pivot = 0;   // test_bad_pivot: the tests' way into the solver's failed-pivot branch (a failure is declared where there was none); rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
 };
 struct SwitchName { const char* name; int Switches::*field; bool relayout; };
 const SwitchName* switch_table(int* count);
@@ -168,6 +168,7 @@ struct lvx_ctx {
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];
   size_t assoc_rings = 0; int assoc_wpr = 0, assoc_list_total = 0;
+  int n_cu = 256;   // compute units of the device (lvx_create): sizes the launches and schedules that want one workgroup per CU
   int coresident_compact = -1, coresident_emit = -1;   // workgroups of k_surfel_compact_mb / k_assoc_emit_fused the device holds at once (occupancy API x CUs, with a margin): both spin on words published by every other workgroup of their launch
   lvx::DevBuf d_pub; unsigned emit_epoch = 0, compact_epoch = 0;   // publication words (epoch | count) of the single-launch compactions: [0, 2048) k_assoc_emit_fused, [2048, 4096) k_surfel_compact_mb; zero once   // shape the association work buffer (d_assoc[3]) was cleared for
   const double* assoc_map_planes = nullptr; int assoc_map_P = 0; bool assoc_map_ready = false;   // lvx_surfel_map_prepare_d: the association grid of this plane table is built

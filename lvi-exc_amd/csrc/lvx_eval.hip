@@ -2023,9 +2023,7 @@ int host_i0(const lvx_ctx* c, double t) {
 // => 2.2; with it 13 intervals = 3.8 rounds beat 10 = 4.9 rounds, measured 0.232 vs 0.241 ms)
 static int pick_chunk(const lvx_ctx* ctx, int lo, int hi, int forced, int wg_per_cu = 1, double fixed = 0.0) {
   if (forced >= 4 && forced <= 64) return forced;
-  int ncu = 256;
-  hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
+  const int ncu = ctx->n_cu;
   int best = lo; long long best_cost = -1;
   for (int r = lo; r <= hi; ++r) {
     const long long nwg = (ctx->N + r - 1) / r + 1;
@@ -2161,8 +2159,7 @@ int ensure_layout(lvx_ctx* ctx) {
       if ((rc = upload_chunks(ctx, LVX_FAM_GYRO, sk, pick_chunk_batches(16, 64, ctx->sw.chunk_r_imu, (double)f.n / std::max(1, N - 3), 4 * (int)GyroAcc::LB)))) return rc;   // the gyroscope-only kernel of Solve #0
       // owner-computes schedule (k_imu_own): one workgroup per CU, equal row counts, boundaries on knot intervals; inside a workgroup batches of <= 256 rows spanning <= IMU_CR
       // intervals.  The workgroup keeps the tables of its whole knot range in LDS: more (smaller) ranges when the widest one does not fit (sparse sample streams).
-      int ncu = 256;
-      { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount; }
+      const int ncu = ctx->n_cu;
       const int cr = IMU_CR;
       std::vector<int> off, k0, wg_c0;
       int G = std::max(1, std::min(ncu, (f.n + 255) / 256)), span = 0;
@@ -2658,6 +2655,18 @@ static void launch_family(bool exp, dim3 grid, dim3 block, hipStream_t s, const 
   if (exp) hipLaunchKernelGGL((k_family<F, PW, true>), grid, block, 0, s, f, cm, pairs, row0, rows, nrows);
   else hipLaunchKernelGGL((k_family<F, PW>), grid, block, 0, s, f, cm, pairs, row0, rows, nrows);
 }
+// ---- kernel descriptors: each is built from the context in ONE place (a new field of a family struct is added here and nowhere else) ----
+static GyroFam gyro_fam(const lvx_ctx* c) { const Family& f = c->imu; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const int*)f.d_perm.p, f.weight, 0.0}; }
+static GyroAcc gyro_acc(const lvx_ctx* c) { const Family& f = c->imu; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const int*)f.d_perm.p, f.weight, 0.0}; }
+static AccelFam accel_fam(const lvx_ctx* c) { const Family& f = c->imu; return {f.n, (const double*)f.d_t.p, (const double*)f.d_b3.p, (const int*)f.d_perm.p, f.huber /* imu.huber carries w_acc */, 0.0}; }
+static ImuFused imu_fused(const lvx_ctx* c) { const Family& f = c->imu; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const double*)f.d_b3.p, (const int*)f.d_perm.p, f.weight, f.huber /* imu.huber carries w_acc */}; }
+// (d_zero: identity permutation for the single prior block, zeroed by ensure_layout)
+static PriorFam prior_fam(const lvx_ctx* c) { return {1, c->prior_t, mkq(c->prior_q[0], c->prior_q[1], c->prior_q[2], c->prior_q[3]), (const int*)c->d_zero.p, c->prior_w, 0.0}; }
+template <bool TAU> static SurfFamT<TAU> surf_fam(const lvx_ctx* c) { const Family& f = c->surf; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const int*)f.d_id0.p, (const int*)f.d_perm.p, (const double*)c->d_planes.p, c->t_map, f.weight, f.huber}; }
+template <bool TAU> static SurfAccT<TAU> surf_acc(const lvx_ctx* c) { const Family& f = c->surf; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const double*)f.d_b3.p, (const int*)f.d_perm.p, c->t_map, f.weight, f.huber}; }
+template <bool TAU> static CamSurfFamT<TAU> camsurf_fam(const lvx_ctx* c) { const Family& f = c->cs; return {f.n, (const int*)f.d_id0.p, (const int*)f.d_id1.p, (const int*)f.d_perm.p, (const double*)c->d_planes.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, c->t_map, f.weight, f.huber}; }
+template <bool TAU> static CamSurfAccT<TAU> camsurf_acc(const lvx_ctx* c) { const Family& f = c->cs; return {f.n, (const int*)f.d_id0.p, (const int*)f.d_id1.p, (const int*)f.d_perm.p, (const double*)c->d_planes.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, c->t_map, f.weight, f.huber}; }
+template <bool TAU> static ReprojFamT<TAU> reproj_fam(const lvx_ctx* c) { const Family& f = c->rep; return {f.n, (const int*)f.d_id0.p, (const double*)f.d_a3.p, (const double*)f.d_t.p, (const int*)f.d_perm.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, f.weight, f.huber}; }
 // LVX_EVAL_JACOBIAN_BLOCKS: per-family record geometry and device buffers (sized for this layout and lock mask); the family offsets of both buffers
 static int setup_blocks(lvx_ctx* ctx, DevCommon& cm) {
   static const int nrs[LVX_NUM_FAM] = {GYRO_NR, ACC_NR, PRI_NR, SURF_NR, REP_NR, CS_NR};
@@ -2695,7 +2704,349 @@ static int setup_blocks(lvx_ctx* ctx, DevCommon& cm) {
   return LVX_OK;
 }
 
-static bool fast_fb(const lvx_ctx* ctx, uint32_t what) { return ctx->fb_on && !ctx->force_legacy && !(what & LVX_EVAL_JACOBIAN) && !ctx->sw.force_legacy; }
+// One evaluation pass being enqueued: what every launch step reads (fixed when the pass starts) and the little that the steps hand on to each other.
+struct Pass {
+  lvx_ctx* ctx; DevCommon cm; uint32_t what;
+  // the chain (the caller's stream); exact kernels over the fallback lists (fam_stream[1]); reprojection reference pass (fam_stream[0]); record copies (fam_stream[2]).  SERIAL / DETERMINISTIC: s_fb = s_side = st
+  hipStream_t st, s_fb, s_side, s_cp;
+  bool xb;              // LVX_EVAL_JACOBIAN_BLOCKS requested
+  bool fast, fb;        // fused kernels; row-level exact fallback: the per-segment kernel follows every fused kernel over its fallback list
+  bool det, side_on;    // det: fixed order of every addition — one stream, coloured launches, one wavefront per workgroup
+  // free time offsets need d pose / d t at both evaluations: one more global column in the fused LiDAR / camera-surfel kernels (SurfAccT<true>, CamSurfAccT<true>);
+  // the reprojection path a time-offset column in its materialised rows; FORCE_LEGACY: the per-segment TAU kernels for everything
+  bool tauL, tauC, fast_surf, fast_cs;
+  bool imu_fused_on, imu_own;   // gyroscope + accelerometer blocks in one owner-computes kernel (k_imu_own), which STORES its band columns: they are not cleared
+  int fb_ev = 0; bool fb_used = false, side_used = false;   // next ev_fb to record; a side stream took work and joins in front of the fold
+  // rows a fused kernel put on family f's fallback list, their count (device error words 4 + f), and whether f has a list in this pass
+  const int* fb_rows(int f) const { return (const int*)ctx->d_fb.p + (size_t)f * LVX_FB_CAP; }
+  const int* fb_cnt(int f) const { return (const int*)cm.err + 4 + f; }
+  bool fb_fam(int f) const { return fb && ((ctx->fb_mask >> f) & 1); }
+  // The listed rows are evaluated by the (slow: 40-100 us for a single block) per-segment kernels on a SIDE stream, right behind the fused kernel that filled the list and
+  // beside the rest of the pass; they join in front of the fold and add to the same accumulators as everything else.  What the pass STORES instead of adding to is
+  // arranged accordingly: k_imu_own's columns are stored before the IMU lists run, the fold's store of the far hub rows is switched off when a LiDAR family has a list
+  // (hub_partial in step_clear), the landmark rows are stored by k_reproj_lmrows on the chain before the reprojection list runs there.
+  int fb_fork() {
+    if (s_fb != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_fb[fb_ev], st)); LVX_HIP(ctx, hipStreamWaitEvent(s_fb, ctx->ev_fb[fb_ev], 0)); fb_ev ^= 1; fb_used = true; }
+    return LVX_OK;
+  }
+  // LVX_EVAL_JACOBIAN_BLOCKS: family f's records go to the pinned host buffer on the copy stream, right behind the last kernel that writes them (on stream s),
+  // while the pass goes on; lvx_get_jacobian_blocks waits for ev_xb[f]
+  int xb_copy(int f, hipStream_t s) {
+    if (!xb) return LVX_OK;
+    LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s)); LVX_HIP(ctx, hipStreamWaitEvent(s_cp, ctx->ev_xb[f], 0));
+    if (ctx->xb_n[f] > 0) {
+      LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xkeys + 3 * ctx->xb_off[f], ctx->h_xtab.keys[f], (size_t)ctx->xb_n[f] * 12, hipMemcpyDeviceToHost, s_cp));
+      LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xvals + ctx->xb_voff[f], ctx->h_xtab.vals[f], (size_t)ctx->xb_n[f] * ctx->xb_nr[f] * ctx->xb_w[f] * 8, hipMemcpyDeviceToHost, s_cp));
+    }
+    LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s_cp));
+    return LVX_OK;
+  }
+  static dim3 grid(int n) { return dim3((unsigned)((n + 63) / 64)); }
+};
+static Pass make_pass(lvx_ctx* ctx, const DevCommon& cm, uint32_t what) {
+  Pass p{}; p.ctx = ctx; p.cm = cm; p.what = what; p.xb = (what & LVX_EVAL_JACOBIAN_BLOCKS) != 0;
+  p.fast = !ctx->force_legacy && !(what & LVX_EVAL_JACOBIAN) && !ctx->sw.force_legacy; p.fb = ctx->fb_on && p.fast;
+  p.det = ctx->sw.deterministic != 0; p.side_on = !ctx->sw.serial && !p.det;
+  p.tauL = !(ctx->locks & LVX_LOCK_LIDAR_TAU); p.tauC = !(ctx->locks & LVX_LOCK_CAM_TAU);
+  p.fast_surf = p.fast && ctx->surf.n > 0; p.fast_cs = p.fast && ctx->cs.n > 0;
+  p.imu_fused_on = p.fast && ctx->imu.n > 0 && !(ctx->locks & LVX_LOCK_R3) && ctx->imu_nch > 0 && imu_fused_lds_bytes(ctx->imu_span) <= 160 * 1024;
+  p.imu_own = p.imu_fused_on && (what & LVX_EVAL_NORMAL_EQ) && ctx->nb > 0 && ctx->imu_owned_cols > 0 && !ctx->sw.clear_all;
+  p.st = ctx->stream; p.s_fb = p.side_on ? ctx->fam_stream[1] : p.st; p.s_side = p.side_on ? ctx->fam_stream[0] : p.st; p.s_cp = ctx->fam_stream[2];
+  return p;
+}
+// k_family_mfma<FT, OCC, EXP> over the chunks of `chunk_slot`: the LDS attribute, then one launch — or, in deterministic mode, colour after colour
+// (no two workgroups of a launch touch the same knots)
+template <class FT, int OCC, bool EXP> static int launch_mfma_occ(Pass& p, const FT& fam, int chunk_slot, hipStream_t stream, long long row0) {
+  lvx_ctx* ctx = p.ctx; const size_t lds = mfma_lds_bytes<FT>(ctx->chunk_r[chunk_slot]);
+  LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_family_mfma<FT, OCC, EXP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int* chunks = (const int*)ctx->d_chunk[chunk_slot].p; const int cr = ctx->chunk_r[chunk_slot], nvar = ctx->chunk_var[chunk_slot] ? ctx->n_chunk[chunk_slot] : 0;
+  const std::vector<int>& dc = ctx->det_col[chunk_slot];
+  if (p.det && dc.size() > 1) {
+    for (size_t q = 0; q + 1 < dc.size(); ++q)
+      hipLaunchKernelGGL((k_family_mfma<FT, OCC, EXP>), dim3(dc[q + 1] - dc[q]), dim3(256), lds, stream, fam, p.cm, chunks, row0, cr, nvar, (const int*)ctx->d_det_list[chunk_slot].p + dc[q]);
+  } else
+    hipLaunchKernelGGL((k_family_mfma<FT, OCC, EXP>), dim3(ctx->n_chunk[chunk_slot]), dim3(256), lds, stream, fam, p.cm, chunks, row0, cr, nvar, (const int*)nullptr);
+  return LVX_OK;
+}
+// ... at the occupancy the family was written for (only that instantiation exists), with the per-block records when the pass wants them
+template <class FT> static int launch_mfma(Pass& p, const FT& fam, int chunk_slot, hipStream_t stream, long long row0) {
+  if constexpr ((int)FT::OCC == 1) return p.xb ? launch_mfma_occ<FT, 1, true>(p, fam, chunk_slot, stream, row0) : launch_mfma_occ<FT, 1, false>(p, fam, chunk_slot, stream, row0);
+  else return p.xb ? launch_mfma_occ<FT, 2, true>(p, fam, chunk_slot, stream, row0) : launch_mfma_occ<FT, 2, false>(p, fam, chunk_slot, stream, row0);
+}
+// the exact per-segment kernel over family f's fallback list, on stream s (row-level fallback: enabled after the first pass that needed it)
+template <class F, int PW> static void launch_family_list(Pass& p, int f, int list, hipStream_t s, const F& fam) {
+  launch_family<F, PW>(p.xb, dim3((unsigned)(LVX_FB_CAP / 64)) /* the list's capacity: the kernel reads the count */, dim3(64 * PW), s, fam, p.cm, (const uint16_t*)p.ctx->d_pairs[f].p, (long long)p.ctx->fam_row0[f], p.fb_rows(list), p.fb_cnt(list));
+}
+// the per-segment kernel over the whole of family f, on the chain
+template <class F, int PW> static void launch_family_all(Pass& p, int f, const F& fam) {
+  launch_family<F, PW>(p.xb, Pass::grid(fam.n), dim3(64 * PW), p.st, fam, p.cm, (const uint16_t*)p.ctx->d_pairs[f].p, (long long)p.ctx->fam_row0[f]);
+}
+// fn(std::true_type{}) or fn(std::false_type{}): the kernels' compile-time TAU from the lock mask
+template <class Fn> static int with_tau(bool tau, Fn&& fn) { return tau ? fn(std::true_type{}) : fn(std::false_type{}); }
+// one launch clears every accumulator of the pass (cost, error flags, and for the normal equations band, gradient, border rows, dense border)
+static int step_clear(Pass& p) {
+  lvx_ctx* ctx = p.ctx; DevCommon& cm = p.cm; const uint32_t what = p.what; hipStream_t st = p.st;
+  const bool fast = p.fast, fb = p.fb, fast_surf = p.fast_surf, fast_cs = p.fast_cs, imu_own = p.imu_own;
+  // the control-point-pair table and the shared t_map poses (one thread, ~25 us) depend on the state only: the first blocks of the clear kernel
+  const int nblk_tab = fast ? (ctx->N + 255) / 256 : 0, npre = fast ? nblk_tab + ((fast_surf || fast_cs) ? 1 : 0) : 0;
+  ClearList cl{}; BandClear bc{};
+  auto add = [&](void* ptr, size_t bytes) { if (cl.n < 16) { cl.p[cl.n] = (uint4*)ptr; cl.words[cl.n] = (bytes + 15) / 16; cl.n++; } };
+  add(cm.cost, (size_t)ctx->nrep * 8); add(cm.err, 64);
+  if (what & LVX_EVAL_NORMAL_EQ) {
+    const size_t nb1 = (size_t)std::max(ctx->nb, 1);
+    if (ctx->sw.clear_all || ctx->nb == 0) add(cm.Hb, nb1 * (ctx->bw + 1) * 8);
+    else { bc.Hb = cm.Hb; bc.colfull = (const uint8_t*)ctx->d_colfull.p; bc.nb = ctx->nb; bc.ld = ctx->bw + 1; bc.npre = ctx->clear_npre; bc.nblk = std::min((ctx->nb + 15) / 16, 2048); }
+    if (imu_own) {   // gradient and the IMU-calibration border rows: cleared column by column where nobody stores (the band loop of k_clear)
+      bc.own = (const int*)ctx->d_imu_own.p; bc.gb = cm.gb; bc.Bd_imu = cm.Bd + (size_t)6 * ctx->n_hub * nb1; bc.imu_rows = 0;
+      for (int c = 0; c < 8; ++c) if (ctx->bd_row_live[6 * ctx->n_hub + c]) bc.imu_rows |= 1u << c;
+      if (!bc.nblk) { bc.colfull = (const uint8_t*)ctx->d_colfull.p; bc.nb = ctx->nb; bc.ld = ctx->bw + 1; bc.npre = ctx->clear_npre; bc.nblk = std::min((ctx->nb + 15) / 16, 2048); }
+    } else add(cm.gb, nb1 * 8);
+    // hub rows of Bd: with the fused LiDAR kernels only the fold fills them beyond the near range — it stores there, the clear skips them
+    const bool fb_lidar = fb && (ctx->fb_mask & ((1 << LVX_FAM_SURFEL) | (1 << LVX_FAM_CAMSURF)));   // listed LiDAR rows add to the hub rows directly, anywhere
+    const bool hub_partial = !fb_lidar && !ctx->sw.clear_all && !(nb1 & 1) && ctx->nb > 0 && ctx->n_hub > 0 && (fast_surf || fast_cs) && (ctx->surf.n == 0 || fast_surf) && (ctx->cs.n == 0 || fast_cs);
+    cm.hub_lo = hub_partial ? ctx->hub_near_lo : 0; cm.hub_hi = hub_partial ? ctx->hub_near_hi : ctx->nb;
+    if (hub_partial) { bc.Bd = cm.Bd; bc.hub_rows = 6 * ctx->n_hub; bc.hub_lo = cm.hub_lo; bc.hub_hi = cm.hub_hi; bc.hub_blk = cm.hub_hi > cm.hub_lo ? 6 * ctx->n_hub : 0; if (!bc.nb) bc.nb = ctx->nb; }
+    // border rows: only the rows some residual can reach (a locked calibration scalar and an unused pseudo-pose set keep their zeros); 16-byte words: whole rows when nb is even
+    if (ctx->sw.clear_all || (nb1 & 1)) add(cm.Bd, (size_t)ctx->nbd_ext * nb1 * 8);
+    else for (int b0 = 0; b0 < ctx->nbd_ext;) {
+      const int first_live = hub_partial ? 6 * ctx->n_hub : 0;   // hub rows: HubClear
+      const int imu0 = imu_own ? 6 * ctx->n_hub : -1;   // the 8 IMU-calibration rows: BandClear
+      if (b0 < first_live || !ctx->bd_row_live[b0] || (imu0 >= 0 && b0 >= imu0 && b0 < imu0 + 8)) { ++b0; continue; }
+      int b1 = b0; while (b1 < ctx->nbd_ext && ctx->bd_row_live[b1] && !(imu0 >= 0 && b1 >= imu0 && b1 < imu0 + 8)) ++b1;
+      add(cm.Bd + (size_t)b0 * nb1, (size_t)(b1 - b0) * nb1 * 8);
+      b0 = b1;
+    }
+    add(cm.C, (size_t)ctx->nrep * ctx->nbd_ext * ctx->nbd_ext * 8); add(cm.gc, (size_t)ctx->nrep * ctx->nbd_ext * 8);
+    const bool rep_fast = fast && ctx->rep_groups > 0 && ctx->rep_fused_wg == 0;   // k_reproj_lmrows stores whole rows: nothing to clear (k_reproj_fused adds to them)
+    if (ctx->L > 0 && ctx->rep.n > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS) && !rep_fast) add(cm.lmH, (size_t)ctx->L * ctx->lm_ls * 8);
+  }
+  size_t total = 0; for (int i = 0; i < cl.n; ++i) total += cl.words[i];
+  const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 8);   // 8 per CU (round 5b, 37 MB to clear: 512 blocks 0.540 ms per pass, 1 024 0.542, 2 048 0.5396, 8 192 — one 16-byte store per thread — 0.5478)
+  ProfScope ps(ctx, LVX_KERNEL_CLEAR, st);
+  hipLaunchKernelGGL(k_clear, dim3(blocks + (unsigned)npre + (unsigned)bc.nblk + (unsigned)bc.hub_blk), dim3(256), 0, st, cl, bc, npre, cm, (So3Pre*)ctx->d_pre.p, nblk_tab, ctx->t_map, fast_surf ? 1 : 0, fast_cs ? 1 : 0,
+                     (HubShared*)ctx->d_hubs.p);
+  return LVX_OK;
+}
+// IMU blocks.  The fused kernel when it applies; otherwise Solve #0 (no R3 spline: gyroscope blocks only) on the MFMA path, everything else per segment.
+// The fallback list of LVX_FAM_GYRO holds SAMPLES: it serves both the gyroscope and the accelerometer exact kernel.
+static int step_imu(Pass& p) {
+  lvx_ctx* ctx = p.ctx; hipStream_t st = p.st; int rc;
+  const bool listed = p.fast && p.fb_fam(LVX_FAM_GYRO);
+  if (p.imu_fused_on) {   // gyroscope + accelerometer blocks in one owner-computes kernel, FIRST on the band: it stores what it owns (k_imu_own)
+    const ImuFused f = imu_fused(ctx); const size_t lds = imu_fused_lds_bytes(ctx->imu_span);
+    LVX_HIP(ctx, hipFuncSetAttribute(p.xb ? (const void*)k_imu_own<true> : (const void*)k_imu_own<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const ImuOwn ow{(const int*)ctx->d_imu_wg.p, p.imu_own ? (const int*)ctx->d_imu_own.p + ctx->imu_own_k_off : nullptr, ctx->imu_nch, ctx->imu_span};
+    ProfScope ps(ctx, LVX_FAM_GYRO, st);
+    if (p.xb) hipLaunchKernelGGL(k_imu_own<true>, dim3(ctx->imu_wg), dim3(256), lds, st, f, p.cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], p.det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
+    else hipLaunchKernelGGL(k_imu_own<false>, dim3(ctx->imu_wg), dim3(256), lds, st, f, p.cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], p.det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
+    if (listed) { if ((rc = p.fb_fork())) return rc;   // listed samples: both blocks by the exact kernels (they ADD to what k_imu_own stored)
+      ProfScope psf(ctx, LVX_KERNEL_FIXUP, p.s_fb);
+      launch_family_list<GyroFam, 1>(p, LVX_FAM_GYRO, LVX_FAM_GYRO, p.s_fb, gyro_fam(ctx));
+      launch_family_list<AccelFam, LVX_PW>(p, LVX_FAM_ACCEL, LVX_FAM_GYRO, p.s_fb, accel_fam(ctx));   // (the accelerometer kernel always runs with LVX_PW)
+    }
+    const hipStream_t s_imu = listed ? p.s_fb : st;
+    return (rc = p.xb_copy(LVX_FAM_GYRO, s_imu)) ? rc : p.xb_copy(LVX_FAM_ACCEL, s_imu);
+  }
+  if (ctx->imu.n <= 0) return LVX_OK;
+  if (p.fast) {
+    ProfScope ps(ctx, LVX_FAM_GYRO, st);
+    if ((rc = launch_mfma(p, gyro_acc(ctx), LVX_FAM_GYRO, st, ctx->fam_row0[0]))) return rc;
+    if (listed) { if ((rc = p.fb_fork())) return rc;
+      ProfScope psf(ctx, LVX_KERNEL_FIXUP, p.s_fb);
+      launch_family_list<GyroFam, 1>(p, LVX_FAM_GYRO, LVX_FAM_GYRO, p.s_fb, gyro_fam(ctx));
+    }
+  } else {
+    ProfScope ps(ctx, LVX_FAM_GYRO, st);
+    launch_family_all<GyroFam, 1>(p, LVX_FAM_GYRO, gyro_fam(ctx));
+  }
+  if (!(ctx->locks & LVX_LOCK_R3)) {
+    ProfScope ps(ctx, LVX_FAM_ACCEL, st);
+    launch_family_all<AccelFam, LVX_PW>(p, LVX_FAM_ACCEL, accel_fam(ctx));
+  }
+  return (rc = p.xb_copy(LVX_FAM_GYRO, listed ? p.s_fb : st)) ? rc : p.xb_copy(LVX_FAM_ACCEL, st);
+}
+static int step_prior(Pass& p) {
+  if (!p.ctx->has_prior) return LVX_OK;
+  ProfScope ps(p.ctx, LVX_FAM_PRIOR, p.st);
+  launch_family<PriorFam, 1>(p.xb, dim3(1), dim3(64), p.st, prior_fam(p.ctx), p.cm, (const uint16_t*)p.ctx->d_pairs[2].p, (long long)p.ctx->fam_row0[2]);
+  return p.xb_copy(LVX_FAM_PRIOR, p.st);
+}
+// LiDAR surfel blocks (f = LVX_FAM_SURFEL) and camera-landmark-to-surfel blocks (LVX_FAM_CAMSURF): the fused kernel `acc` with the exact kernel over its fallback
+// list behind it, or the per-segment kernel `fam` over everything; then the record copy behind whichever kernel wrote the family's records last.
+// The per-segment kernel runs with PW = 1 over the whole family and with LVX_PW over a list.
+template <class Acc, class Fam> static int step_lidar(Pass& p, int f, bool fused, const Acc& acc, const Fam& fam) {
+  lvx_ctx* ctx = p.ctx; int rc;
+  const bool listed = fused && p.fb_fam(f);
+  ProfScope ps(ctx, f, p.st);
+  if (fused) {
+    if ((rc = launch_mfma(p, acc, f, p.st, ctx->fam_row0[f]))) return rc;
+    if (listed) { if ((rc = p.fb_fork())) return rc;
+      ProfScope psf(ctx, LVX_KERNEL_FIXUP, p.s_fb);
+      launch_family_list<Fam, LVX_PW>(p, f, f, p.s_fb, fam);
+    }
+  } else launch_family_all<Fam, 1>(p, f, fam);
+  return p.xb_copy(f, listed ? p.s_fb : p.st);
+}
+static int step_surfel(Pass& p) {
+  return p.ctx->surf.n <= 0 ? LVX_OK : with_tau(p.tauL, [&](auto T) { return step_lidar(p, LVX_FAM_SURFEL, p.fast_surf, surf_acc<decltype(T)::value>(p.ctx), surf_fam<decltype(T)::value>(p.ctx)); });
+}
+static int step_camsurf(Pass& p) {
+  return p.ctx->cs.n <= 0 ? LVX_OK : with_tau(p.tauC, [&](auto T) { return step_lidar(p, LVX_FAM_CAMSURF, p.fast_cs, camsurf_acc<decltype(T)::value>(p.ctx), camsurf_fam<decltype(T)::value>(p.ctx)); });
+}
+// the reprojection chain (Jacobian rows materialised once, three MFMA assembly passes, landmark rows stored) for a locked AND for a free camera time offset
+template <bool T> static int rep_fused(Pass& p) {
+  lvx_ctx* ctx = p.ctx; hipStream_t st = p.st; int rc;
+  constexpr int RJ = REP_NC + (T ? 1 : 0);
+  const ReprojFamT<T> rf = reproj_fam<T>(ctx);
+  double* Jb = (double*)ctx->d_repB[0].p; double* rb = Jb + (size_t)2 * RJ * rf.n; int* kb = (int*)ctx->d_repB[1].p;
+  { ProfScope ps(ctx, LVX_KERNEL_REP_JAC, st);
+    double* trec = (ctx->L > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS) && ctx->rep_groups > 0 && (p.what & LVX_EVAL_NORMAL_EQ)) ? (double*)ctx->d_repT.p : (double*)nullptr;
+    const size_t lds_j = trec ? (size_t)64 * ((56 + (T ? 1 : 0)) | 1) * 8 : 0;
+    if (p.xb) hipLaunchKernelGGL((k_reproj_jac<T, true>), Pass::grid(rf.n), dim3(64), lds_j, st, rf, p.cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec);
+    else hipLaunchKernelGGL(k_reproj_jac<T>, Pass::grid(rf.n), dim3(64), lds_j, st, rf, p.cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec); }
+  if (!p.fb_fam(LVX_FAM_REPROJ) && (rc = p.xb_copy(LVX_FAM_REPROJ, st))) return rc;   // (listed blocks: behind the exact kernel, step_reproj_tau)
+  if (!(p.what & LVX_EVAL_NORMAL_EQ)) return LVX_OK;
+  const RepJac jac{Jb, rb, kb, rf.n};
+  if (p.s_side != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_jac, st)); LVX_HIP(ctx, hipStreamWaitEvent(p.s_side, ctx->ev_jac, 0)); p.side_used = true; }
+  { const RepSideAcc<0, T> rr{rf.n, jac, 0.0};   // the chunk slot of the prior (it has no chunks) carries the reference-side chunks
+    ProfScope ps(ctx, LVX_KERNEL_REP_REF, p.s_side);
+    if ((rc = launch_mfma_occ<RepSideAcc<0, T>, 1, false>(p, rr, LVX_FAM_PRIOR, p.s_side, ctx->fam_row0[4]))) return rc; }
+  { const RepSideAcc<1, T> ro{rf.n, jac, 0.0};
+    ProfScope ps(ctx, LVX_KERNEL_REP_OBS, st);
+    if ((rc = launch_mfma_occ<RepSideAcc<1, T>, 1, false>(p, ro, LVX_FAM_REPROJ, st, ctx->fam_row0[4]))) return rc; }
+  if (ctx->rep_groups <= 0) return LVX_OK;
+  const int* gt = (const int*)ctx->d_repB[2].p;
+  RepCross rx{jac, rf.lm, gt, gt + ctx->rep_groups + 1, ctx->rep_groups, (double*)ctx->d_repT.p, nullptr};
+  { ProfScope ps(ctx, LVX_KERNEL_REP_CROSS, st);
+    if (p.det && ctx->det_cross_col.size() > 1) {
+      for (size_t q = 0; q + 1 < ctx->det_cross_col.size(); ++q) {
+        rx.det_list = (const int*)ctx->d_det_cross.p + ctx->det_cross_col[q];
+        hipLaunchKernelGGL(k_reproj_cross<T>, dim3((unsigned)(ctx->det_cross_col[q + 1] - ctx->det_cross_col[q])), dim3(64 * RX_NW), 0, st, rx, p.cm);
+      }
+    } else
+      hipLaunchKernelGGL(k_reproj_cross<T>, dim3((unsigned)std::min((ctx->rep_groups + RX_NW - 1) / RX_NW, 256 * 8)), dim3(64 * RX_NW), 0, st, rx, p.cm); }
+  if (ctx->L > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS)) {
+    const int* lp = (const int*)ctx->d_repB[3].p;
+    const RepLmRows lq{(const double*)ctx->d_repT.p, kb, rf.n, lp, lp + ctx->L + 1, ctx->L};
+    const size_t lds = (size_t)4 * ctx->lm_ls * 8;
+    LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_reproj_lmrows<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    ProfScope ps(ctx, LVX_KERNEL_REP_LMROWS, st);
+    hipLaunchKernelGGL(k_reproj_lmrows<T>, dim3((unsigned)((ctx->L + 3) / 4)), dim3(256), lds, st, lq, p.cm);
+  }
+  return LVX_OK;
+}
+// ONE launch (round 6): evaluation, assembly and landmark rows per landmark-owning workgroup; nothing materialised
+template <bool T> static int rep_one(Pass& p) {
+  lvx_ctx* ctx = p.ctx;
+  const int* tab = (const int*)ctx->d_repF.p; const int ng = ctx->rep_fused_wg;
+  const RepFused q{tab, tab + ng, ng};
+  ProfScope ps(ctx, LVX_KERNEL_REP_FUSED, p.st);
+  hipLaunchKernelGGL(k_reproj_fused<T>, dim3((unsigned)std::min((ng + 3) / 4, ctx->n_cu)), dim3(256), 0, p.st, reproj_fam<T>(ctx), q, p.cm, (long long)ctx->fam_row0[4]);
+  return LVX_OK;
+}
+// Reprojection blocks.  Fused: the single-launch kernel (opt-in; it writes no records: with them the chain runs) or the chain, then the listed blocks by the exact
+// kernel ON THE CHAIN, behind the landmark rows' stores, and the record copy behind it.  Otherwise the per-segment kernel over everything; it always runs with LVX_PW.
+template <bool T> static int step_reproj_tau(Pass& p) {
+  lvx_ctx* ctx = p.ctx; int rc;
+  if (!p.fast) {
+    { ProfScope ps(ctx, LVX_FAM_REPROJ, p.st); launch_family_all<ReprojFamT<T>, LVX_PW>(p, LVX_FAM_REPROJ, reproj_fam<T>(ctx)); }
+    return p.xb_copy(LVX_FAM_REPROJ, p.st);
+  }
+  if ((rc = (ctx->rep_fused_wg > 0 && !p.xb) ? rep_one<T>(p) : rep_fused<T>(p))) return rc;
+  if (!p.fb_fam(LVX_FAM_REPROJ)) return LVX_OK;   // (rep_fused has queued the record copy behind k_reproj_jac)
+  { ProfScope psf(ctx, LVX_KERNEL_FIXUP, p.st); launch_family_list<ReprojFamT<T>, LVX_PW>(p, LVX_FAM_REPROJ, LVX_FAM_REPROJ, p.st, reproj_fam<T>(ctx)); }
+  return p.xb_copy(LVX_FAM_REPROJ, p.st);
+}
+static int step_reproj(Pass& p) { return p.ctx->rep.n <= 0 ? LVX_OK : with_tau(p.tauC, [&](auto T) { return step_reproj_tau<decltype(T)::value>(p); }); }
+// replica sums -> dense block (the last replica block to finish) and the border-row fold (Bd, streaming; disjoint buffers) in one launch
+static int step_fold(Pass& p) {
+  lvx_ctx* ctx = p.ctx; hipStream_t st = p.st; const DevCommon& cm = p.cm; const bool fast_surf = p.fast_surf, fast_cs = p.fast_cs;
+  ProfScope ps(ctx, LVX_KERNEL_FOLD);
+  const bool fold_fast = (p.what & LVX_EVAL_NORMAL_EQ) && (fast_surf || fast_cs);
+  const unsigned n_rep_blk = (unsigned)((ctx->nbd_ext * ctx->nbd_ext + 255) / 256);
+  if (fold_fast && ctx->nb > 0 && !ctx->sw.serial) {
+    const unsigned n_rows_blk = (unsigned)((ctx->nb + 255) / 256);
+    const int set0 = fast_surf ? 0 : 1, set1 = (fast_surf && fast_cs) ? 1 : -1;
+    const size_t lds = ((size_t)ctx->nbd_ext * ctx->nbd_ext + ctx->nbd_ext) * 8;
+    LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_fold_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_fold_all, dim3(n_rep_blk + n_rows_blk), dim3(256), lds, st, cm, (int)n_rep_blk, (int)n_rows_blk, set0, 1, set1, 0, (int*)ctx->d_zero.p + 1);
+    return LVX_OK;
+  }
+  hipStream_t s_fold = (fold_fast && p.side_on) ? ctx->fam_stream[0] : st;
+  if (s_fold != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_fork, st)); LVX_HIP(ctx, hipStreamWaitEvent(s_fold, ctx->ev_fork, 0)); }
+  hipLaunchKernelGGL(k_fold_replicas, dim3(n_rep_blk), dim3(256), 0, st, cm);
+  if (fold_fast) {
+    for (int set = 0; set < 2; ++set) if (ctx->nb > 0 && ((set == 0 && fast_surf) || (set == 1 && fast_cs)))
+      hipLaunchKernelGGL(k_fold_border_rows, dim3((unsigned)((ctx->nb + 255) / 256)), dim3(256), 0, s_fold, cm, set, (set == 0 || !fast_surf) ? 1 : 0);
+    const size_t lds = ((size_t)ctx->nbd_ext * ctx->nbd_ext + ctx->nbd_ext) * 8;
+    LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_fold_border_dense, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_fold_border_dense, dim3(1), dim3(256), lds, st, cm);
+    if (s_fold != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[1], s_fold)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[1], 0)); }
+  }
+  return LVX_OK;
+}
+// Schedule.  ONE chain on the caller's stream — clear -> fused IMU kernel (stores its band columns) -> prior -> LiDAR kernels -> reprojection Jacobian -> observation
+// pass -> cross terms -> landmark rows -> fold — and ONE side stream that takes the reprojection reference pass (it only reads the materialised rows and adds
+// atomically) behind the Jacobian kernel and joins in front of the fold.  A hand-over between streams costs 10-30 us on this stack, graph or no graph, so nothing
+// else forks (everything concurrent, a stream per family, the staged two-chain schedule of rounds 1-3 were measured and dropped).  SERIAL and
+// DETERMINISTIC keep everything on the chain.
+static int enqueue_pass(Pass& p) {
+  lvx_ctx* ctx = p.ctx; int rc;
+  if ((rc = step_clear(p)) || (rc = step_imu(p)) || (rc = step_prior(p)) || (rc = step_surfel(p)) || (rc = step_camsurf(p)) || (rc = step_reproj(p))) return rc;
+  if (p.side_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[0], p.s_side)); LVX_HIP(ctx, hipStreamWaitEvent(p.st, ctx->ev_join[0], 0)); }
+  if (p.fb_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[2], p.s_fb)); LVX_HIP(ctx, hipStreamWaitEvent(p.st, ctx->ev_join[2], 0)); }
+  if ((rc = step_fold(p))) return rc;
+  LVX_HIP(ctx, hipGetLastError());
+  return LVX_OK;
+}
+// The device error words of a finished pass (errw[0]: flags, errw[4 + f]: rows of family f on its fallback list).  *rerun: the fused kernels met rows they cannot
+// take exactly and the pass has to be repeated.  First with the ROW-LEVEL fallback: the same pass with fallback lists — the fused kernels skip those rows, the exact
+// per-segment kernel evaluates just them (a few small launches more per pass from now on).  Only when a list overflowed, or for a corner that is not a row's
+// (|tau_imu| >= dt), everything goes to the per-segment kernels.
+static int finish_pass_errors(lvx_ctx* ctx, const int* errw, bool* rerun) {
+  *rerun = false;
+  ctx->fallback_rows = 0; for (int f = 0; f < LVX_NUM_FAM; ++f) ctx->fallback_rows += errw[4 + f];
+  if ((errw[0] & LVX_ERR_FALLBACK) && !ctx->force_legacy) {
+    int need = 0; for (int f = 0; f < LVX_NUM_FAM; ++f) if (errw[4 + f] > 0) need |= 1 << f;
+    if (!ctx->sw.force_legacy && need && (need & ~ctx->fb_mask)) { ctx->fb_on = true; ctx->fb_mask |= need; }   // a family without a list yet: give it one
+    else ctx->force_legacy = true;                                                                              // a list overflowed, or the corner is not a row's
+    *rerun = true; return LVX_OK;
+  }
+  if (errw[0] & RES_RANGE) return fail(ctx, LVX_E_RANGE, "time span out of range for trajectory");
+  if (errw[0] & RES_NONUNIT) return fail(ctx, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
+  if (errw[0] & 4) return fail(ctx, LVX_E_STATE, "normal-equation entry outside the computed bandwidth");
+  return LVX_OK;
+}
+// Everything from the clears to the fold kernels is one static launch sequence for a given (state buffer, request, configuration):
+// it is captured once into a HIP graph and replayed — a pass is ~35 API calls (memsets, cross-stream events, ~12 launches), which bounds small
+// problems at ~370 us per evaluation when issued call by call.  LVX_NO_GRAPH=1 issues the calls directly; profiling and the debug
+// Jacobian always do.
+// Graph replay pays for small problems (launch-bound at ~0.37 ms issued call by call, 0.26 ms replayed); at config-4 size the kernels are long
+// enough for the host to stay ahead and the replayed graph is the SLOWER one (0.61 against 0.58 ms: its cross-stream edges become barrier packets between every node)
+static int launch_pass(Pass& p, const double* state_d, bool want_res_buffer) {
+  lvx_ctx* ctx = p.ctx; hipStream_t st = p.st; const uint32_t what = p.what;
+  const bool use_graph = !ctx->sw.no_graph && !ctx->profiling && !(what & (LVX_EVAL_JACOBIAN | LVX_EVAL_JACOBIAN_BLOCKS)) && ctx->n_blocks <= 400000;   // the records' copies are issued call by call
+  if (!use_graph) return enqueue_pass(p);
+  const int flags = (want_res_buffer ? 1 : 0) | (ctx->force_legacy ? 2 : 0) | (ctx->fb_on ? 4 : 0) | (ctx->fb_mask << 3);   // a switch change bumps cfg_version
+  hipGraphExec_t exec = nullptr;
+  for (const auto& e : ctx->graphs) if (e.state == state_d && e.what == what && e.flags == flags && e.cfg == ctx->cfg_version) { exec = (hipGraphExec_t)e.exec; break; }
+  if (!exec) {
+    if (ctx->graphs.size() >= 16) { for (auto& e : ctx->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec); ctx->graphs.clear(); }
+    hipGraph_t graph = nullptr;
+    LVX_HIP(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    const int rc = enqueue_pass(p);
+    const hipError_t ce = hipStreamEndCapture(st, &graph);
+    if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+    if (ce != hipSuccess || !graph) return fail(ctx, LVX_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
+    const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+    (void)hipGraphDestroy(graph);
+    if (ie != hipSuccess) return fail(ctx, LVX_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
+    ctx->graphs.push_back({state_d, what, flags, ctx->cfg_version, (void*)exec});
+  }
+  LVX_HIP(ctx, hipGraphLaunch(exec, st));
+  return LVX_OK;
+}
+
 int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cost, bool want_res_buffer) {
   ctx->xb_valid = false;   // (first: a call that fails anywhere below leaves no records to read)
   int rc = ensure_layout(ctx);
@@ -2720,345 +3071,9 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
     LVX_HIP(ctx, hipMemsetAsync(cm.jcols, 0xff, nrow * LVX_JAC_WIDTH * 4, st));
     LVX_HIP(ctx, hipMemsetAsync(cm.jvals, 0, nrow * LVX_JAC_WIDTH * 8, st));
   }
-  // Everything from the clears to the fold kernels is one static launch sequence for a given (state buffer, request, configuration):
-  // it is captured once into a HIP graph and replayed — a pass is ~35 API calls (memsets, cross-stream events, ~12 launches), which bounds small
-  // problems at ~370 us per evaluation when issued call by call.  LVX_NO_GRAPH=1 issues the calls directly; profiling and the debug
-  // Jacobian always do.
-  auto enqueue = [&]() -> int {
-    int rc = LVX_OK;
-    const bool fast = !ctx->force_legacy && !(what & LVX_EVAL_JACOBIAN) && !ctx->sw.force_legacy;
-    const bool fb = fast_fb(ctx, what);   // row-level exact fallback: the per-segment kernel follows every fused kernel over its fallback list
-    // free time offsets need d pose / d t at both evaluations: one more global column in the fused LiDAR / camera-surfel kernels (SurfAccT<true>, CamSurfAccT<true>);
-    // the reprojection path a time-offset column in its materialised rows; FORCE_LEGACY: the per-segment TAU kernels for everything
-    const bool tauL = !(ctx->locks & LVX_LOCK_LIDAR_TAU), tauC = !(ctx->locks & LVX_LOCK_CAM_TAU);
-    const bool fast_surf = fast && ctx->surf.n > 0, fast_cs = fast && ctx->cs.n > 0;
-    // the control-point-pair table and the shared t_map poses (one thread, ~25 us) depend on the state only: the first blocks of the clear kernel
-    const int nblk_tab = fast ? (ctx->N + 255) / 256 : 0, npre = fast ? nblk_tab + ((fast_surf || fast_cs) ? 1 : 0) : 0;
-    const lvx::Switches& sw = ctx->sw;
-    const bool det = sw.deterministic != 0;   // fixed order of every addition: one stream, coloured launches, one wavefront per workgroup
-    const bool imu_fused_on = fast && ctx->imu.n > 0 && !(ctx->locks & LVX_LOCK_R3) && ctx->imu_nch > 0 && imu_fused_lds_bytes(ctx->imu_span) <= 160 * 1024;
-    const bool imu_own = imu_fused_on && (what & LVX_EVAL_NORMAL_EQ) && ctx->nb > 0 && ctx->imu_owned_cols > 0 && !sw.clear_all;   // k_imu_own stores its band columns: they are not cleared
-    {   // one launch clears every accumulator of the pass (cost, error flags, and for the normal equations band, gradient, border rows, dense border)
-      ClearList cl{};
-      BandClear bc{};
-      auto add = [&](void* p, size_t bytes) { if (cl.n < 16) { cl.p[cl.n] = (uint4*)p; cl.words[cl.n] = (bytes + 15) / 16; cl.n++; } };
-      add(cm.cost, (size_t)ctx->nrep * 8); add(cm.err, 64);
-      if (what & LVX_EVAL_NORMAL_EQ) {
-        const size_t nb1 = (size_t)std::max(ctx->nb, 1);
-        if (ctx->sw.clear_all || ctx->nb == 0) add(cm.Hb, nb1 * (ctx->bw + 1) * 8);
-        else { bc.Hb = cm.Hb; bc.colfull = (const uint8_t*)ctx->d_colfull.p; bc.nb = ctx->nb; bc.ld = ctx->bw + 1; bc.npre = ctx->clear_npre; bc.nblk = std::min((ctx->nb + 15) / 16, 2048); }
-        if (imu_own) {   // gradient and the IMU-calibration border rows: cleared column by column where nobody stores (the band loop of k_clear)
-          bc.own = (const int*)ctx->d_imu_own.p; bc.gb = cm.gb; bc.Bd_imu = cm.Bd + (size_t)6 * ctx->n_hub * nb1; bc.imu_rows = 0;
-          for (int c = 0; c < 8; ++c) if (ctx->bd_row_live[6 * ctx->n_hub + c]) bc.imu_rows |= 1u << c;
-          if (!bc.nblk) { bc.colfull = (const uint8_t*)ctx->d_colfull.p; bc.nb = ctx->nb; bc.ld = ctx->bw + 1; bc.npre = ctx->clear_npre; bc.nblk = std::min((ctx->nb + 15) / 16, 2048); }
-        } else add(cm.gb, nb1 * 8);
-        // hub rows of Bd: with the fused LiDAR kernels only the fold fills them beyond the near range — it stores there, the clear skips them
-        const bool fb_lidar = fb && (ctx->fb_mask & ((1 << LVX_FAM_SURFEL) | (1 << LVX_FAM_CAMSURF)));   // listed LiDAR rows add to the hub rows directly, anywhere
-        const bool hub_partial = !fb_lidar && !ctx->sw.clear_all && !(nb1 & 1) && ctx->nb > 0 && ctx->n_hub > 0 && (fast_surf || fast_cs) && (ctx->surf.n == 0 || fast_surf) && (ctx->cs.n == 0 || fast_cs);
-        cm.hub_lo = hub_partial ? ctx->hub_near_lo : 0; cm.hub_hi = hub_partial ? ctx->hub_near_hi : ctx->nb;
-        if (hub_partial) { bc.Bd = cm.Bd; bc.hub_rows = 6 * ctx->n_hub; bc.hub_lo = cm.hub_lo; bc.hub_hi = cm.hub_hi; bc.hub_blk = cm.hub_hi > cm.hub_lo ? 6 * ctx->n_hub : 0; if (!bc.nb) bc.nb = ctx->nb; }
-        // border rows: only the rows some residual can reach (a locked calibration scalar and an unused pseudo-pose set keep their zeros); 16-byte words: whole rows when nb is even
-        if (ctx->sw.clear_all || (nb1 & 1)) add(cm.Bd, (size_t)ctx->nbd_ext * nb1 * 8);
-        else for (int b0 = 0; b0 < ctx->nbd_ext;) {
-          const int first_live = hub_partial ? 6 * ctx->n_hub : 0;   // hub rows: HubClear
-          const int imu0 = imu_own ? 6 * ctx->n_hub : -1;   // the 8 IMU-calibration rows: BandClear
-          if (b0 < first_live || !ctx->bd_row_live[b0] || (imu0 >= 0 && b0 >= imu0 && b0 < imu0 + 8)) { ++b0; continue; }
-          int b1 = b0; while (b1 < ctx->nbd_ext && ctx->bd_row_live[b1] && !(imu0 >= 0 && b1 >= imu0 && b1 < imu0 + 8)) ++b1;
-          add(cm.Bd + (size_t)b0 * nb1, (size_t)(b1 - b0) * nb1 * 8);
-          b0 = b1;
-        }
-        add(cm.C, (size_t)ctx->nrep * ctx->nbd_ext * ctx->nbd_ext * 8); add(cm.gc, (size_t)ctx->nrep * ctx->nbd_ext * 8);
-        const bool rep_fast = fast && ctx->rep_groups > 0 && ctx->rep_fused_wg == 0;   // k_reproj_lmrows stores whole rows: nothing to clear (k_reproj_fused adds to them)
-        if (ctx->L > 0 && ctx->rep.n > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS) && !rep_fast) add(cm.lmH, (size_t)ctx->L * ctx->lm_ls * 8);
-      }
-      size_t total = 0; for (int i = 0; i < cl.n; ++i) total += cl.words[i];
-      const unsigned blocks = (unsigned)std::min<size_t>((total + 255) / 256, 256 * 8);   // 8 per CU (round 5b, 37 MB to clear: 512 blocks 0.540 ms per pass, 1 024 0.542, 2 048 0.5396, 8 192 — one 16-byte store per thread — 0.5478)
-      ProfScope ps(ctx, LVX_KERNEL_CLEAR, st);
-      hipLaunchKernelGGL(k_clear, dim3(blocks + (unsigned)npre + (unsigned)bc.nblk + (unsigned)bc.hub_blk), dim3(256), 0, st, cl, bc, npre, cm, (So3Pre*)ctx->d_pre.p, nblk_tab, ctx->t_map, fast_surf ? 1 : 0, fast_cs ? 1 : 0,
-                         (HubShared*)ctx->d_hubs.p);
-    }
-    auto grid = [](int n) { return dim3((unsigned)((n + 63) / 64)); };
-    // exact per-segment kernel over the rows a fused kernel put on family f's fallback list (row-level fallback: enabled after the first pass that needed it)
-    const dim3 fb_grid((unsigned)(LVX_FB_CAP / 64));
-    const int* fb_rows_base = (const int*)ctx->d_fb.p;
-    auto fb_rows = [&](int f) { return fb_rows_base + (size_t)f * LVX_FB_CAP; };
-    auto fb_cnt = [&](int f) { return (const int*)cm.err + 4 + f; };
-    auto fb_fam = [&](int f) { return fb && ((ctx->fb_mask >> f) & 1); };
-    // The listed rows are evaluated by the (slow: 40-100 us for a single block) per-segment kernels on a SIDE stream, right behind the fused kernel that filled the list and
-    // beside the rest of the pass; they join in front of the fold and add to the same accumulators as everything else.  What the pass STORES instead of adding to is
-    // arranged accordingly: k_imu_own's columns are stored before the IMU lists run, the fold's store of the far hub rows is switched off when a LiDAR family has a list
-    // (hub_partial below), the landmark rows are stored by k_reproj_lmrows on the chain before the reprojection list runs there.
-    hipStream_t s_fb = (sw.serial || det) ? st : ctx->fam_stream[1];
-    // LVX_EVAL_JACOBIAN_BLOCKS: family f's records go to the pinned host buffer on a copy stream, right behind the last kernel that writes them (on stream s),
-    // while the pass goes on; lvx_get_jacobian_blocks waits for ev_xb[f]
-    hipStream_t s_cp = ctx->fam_stream[2];
-    auto xb_copy = [&](int f, hipStream_t s) -> int {
-      if (!xb) return LVX_OK;
-      LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s)); LVX_HIP(ctx, hipStreamWaitEvent(s_cp, ctx->ev_xb[f], 0));
-      if (ctx->xb_n[f] > 0) {
-        LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xkeys + 3 * ctx->xb_off[f], ctx->h_xtab.keys[f], (size_t)ctx->xb_n[f] * 12, hipMemcpyDeviceToHost, s_cp));
-        LVX_HIP(ctx, hipMemcpyAsync(ctx->h_xvals + ctx->xb_voff[f], ctx->h_xtab.vals[f], (size_t)ctx->xb_n[f] * ctx->xb_nr[f] * ctx->xb_w[f] * 8, hipMemcpyDeviceToHost, s_cp));
-      }
-      LVX_HIP(ctx, hipEventRecord(ctx->ev_xb[f], s_cp));
-      return LVX_OK;
-    };
-    bool fb_used = false;
-    int fb_ev = 0;
-    auto fb_fork = [&]() -> int { if (s_fb != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_fb[fb_ev], st)); LVX_HIP(ctx, hipStreamWaitEvent(s_fb, ctx->ev_fb[fb_ev], 0)); fb_ev ^= 1; fb_used = true; } return LVX_OK; };
-    if (imu_fused_on) {   // gyroscope + accelerometer blocks in one owner-computes kernel, FIRST on the band: it stores what it owns (k_imu_own)
-      const ImuFused f{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, ctx->imu.huber /*w_acc*/};
-      const size_t lds_ = imu_fused_lds_bytes(ctx->imu_span);
-      LVX_HIP(ctx, hipFuncSetAttribute(xb ? (const void*)k_imu_own<true> : (const void*)k_imu_own<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_));
-      const ImuOwn ow{(const int*)ctx->d_imu_wg.p, imu_own ? (const int*)ctx->d_imu_own.p + ctx->imu_own_k_off : nullptr, ctx->imu_nch, ctx->imu_span};
-      ProfScope ps(ctx, LVX_FAM_GYRO, st);
-      if (xb) hipLaunchKernelGGL(k_imu_own<true>, dim3(ctx->imu_wg), dim3(256), lds_, st, f, cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
-      else hipLaunchKernelGGL(k_imu_own<false>, dim3(ctx->imu_wg), dim3(256), lds_, st, f, cm, (const int*)ctx->d_imu_chunk.p, ow, (long long)ctx->fam_row0[0], (long long)ctx->fam_row0[1], det ? 1 : 0, (const int*)ctx->d_imu_rtab.p);
-      if (fb_fam(LVX_FAM_GYRO)) {   // listed samples: both blocks by the exact kernels (they ADD to what k_imu_own stored)
-        if ((rc = fb_fork())) return rc;
-        ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb);
-        GyroFam gf{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-        launch_family<GyroFam, 1>(xb, fb_grid, dim3(64), s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
-        AccelFam af{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.huber /*w_acc*/, 0.0};
-        launch_family<AccelFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, af, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO));
-      }
-      const hipStream_t s_imu = fb_fam(LVX_FAM_GYRO) ? s_fb : st;
-      if ((rc = xb_copy(LVX_FAM_GYRO, s_imu)) || (rc = xb_copy(LVX_FAM_ACCEL, s_imu))) return rc;
-    }
-    // Schedule.  ONE chain on the caller's stream — clear -> fused IMU kernel (stores its band columns) -> prior -> LiDAR kernels -> reprojection Jacobian -> observation
-    // pass -> cross terms -> landmark rows -> fold — and ONE side stream that takes the reprojection reference pass (it only reads the materialised rows and adds
-    // atomically) behind the Jacobian kernel and joins in front of the fold.  A hand-over between streams costs 10-30 us on this stack, graph or no graph, so nothing
-    // else forks (everything concurrent, a stream per family, the staged two-chain schedule of rounds 1-3 were measured and dropped).  SERIAL and
-    // DETERMINISTIC keep everything on the chain.
-    const bool side_on = !sw.serial && !det;
-    hipStream_t s_side = side_on ? ctx->fam_stream[0] : st;
-    bool side_used = false;
-  #define LVX_T2(...) __VA_ARGS__
-  #define LVX_LAUNCH_MFMA1(FT, OCCV, fam_obj, chunk_slot, stream, row0v) LVX_LAUNCH_MFMA1X(FT, OCCV, false, fam_obj, chunk_slot, stream, row0v)
-  #define LVX_LAUNCH_MFMA1X(FT, OCCV, EXPV, fam_obj, chunk_slot, stream, row0v)                                                                 \
-    do {                                                                                                                                     \
-      const size_t lds_ = mfma_lds_bytes<FT>(ctx->chunk_r[chunk_slot]);                                                                      \
-      LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_family_mfma<FT, OCCV, EXPV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_)); \
-      if (det && ctx->det_col[chunk_slot].size() > 1) {   /* colour after colour: no two workgroups of a launch touch the same knots */            \
-        const std::vector<int>& dc_ = ctx->det_col[chunk_slot];                                                                              \
-        for (size_t q_ = 0; q_ + 1 < dc_.size(); ++q_)                                                                                       \
-          hipLaunchKernelGGL((k_family_mfma<FT, OCCV, EXPV>), dim3(dc_[q_ + 1] - dc_[q_]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
-                             ctx->chunk_r[chunk_slot], ctx->chunk_var[chunk_slot] ? ctx->n_chunk[chunk_slot] : 0, (const int*)ctx->d_det_list[chunk_slot].p + dc_[q_]); \
-      } else                                                                                                                                 \
-      hipLaunchKernelGGL((k_family_mfma<FT, OCCV, EXPV>), dim3(ctx->n_chunk[chunk_slot]), dim3(256), lds_, stream, fam_obj, cm, (const int*)ctx->d_chunk[chunk_slot].p, (long long)(row0v), \
-                         ctx->chunk_r[chunk_slot], ctx->chunk_var[chunk_slot] ? ctx->n_chunk[chunk_slot] : 0, (const int*)nullptr);          \
-    } while (0)
-  #define LVX_LAUNCH_MFMA(FT, fam_obj, chunk_slot, stream, row0v)                                                                               \
-    do { if (xb) { if ((int)FT::OCC == 1) LVX_LAUNCH_MFMA1X(FT, 1, true, fam_obj, chunk_slot, stream, row0v); else LVX_LAUNCH_MFMA1X(FT, 2, true, fam_obj, chunk_slot, stream, row0v); }          \
-         else if ((int)FT::OCC == 1) LVX_LAUNCH_MFMA1(FT, 1, fam_obj, chunk_slot, stream, row0v); else LVX_LAUNCH_MFMA1(FT, 2, fam_obj, chunk_slot, stream, row0v); } while (0)
-    // ---- IMU blocks when the fused kernel does not apply: Solve #0 (no R3 spline: gyroscope blocks only) on the MFMA path, everything else per segment ----
-    if (ctx->imu.n > 0 && !imu_fused_on) {
-      if (fast) {
-        GyroAcc g{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-        ProfScope ps(ctx, LVX_FAM_GYRO, st); LVX_LAUNCH_MFMA(GyroAcc, g, LVX_FAM_GYRO, st, ctx->fam_row0[0]);
-        if (fb_fam(LVX_FAM_GYRO)) { if ((rc = fb_fork())) return rc;
-          ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb);
-          GyroFam gf{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-          launch_family<GyroFam, 1>(xb, fb_grid, dim3(64), s_fb, gf, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0], fb_rows(LVX_FAM_GYRO), fb_cnt(LVX_FAM_GYRO)); }
-      } else {
-        GyroFam g{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_a3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.weight, 0.0};
-        ProfScope ps(ctx, LVX_FAM_GYRO, st);
-        launch_family<GyroFam, 1>(xb, grid(g.n), dim3(64), st, g, cm, (const uint16_t*)ctx->d_pairs[0].p, (long long)ctx->fam_row0[0]);
-      }
-      if (!(ctx->locks & LVX_LOCK_R3)) {
-        AccelFam a{ctx->imu.n, (const double*)ctx->imu.d_t.p, (const double*)ctx->imu.d_b3.p, (const int*)ctx->imu.d_perm.p, ctx->imu.huber /*w_acc*/, 0.0};
-        ProfScope ps(ctx, LVX_FAM_ACCEL, st);
-        launch_family<AccelFam, LVX_PW>(xb, grid(a.n), dim3(64 * LVX_PW), st, a, cm, (const uint16_t*)ctx->d_pairs[1].p, (long long)ctx->fam_row0[1]);
-      }
-      if ((rc = xb_copy(LVX_FAM_GYRO, (fast && fb_fam(LVX_FAM_GYRO)) ? s_fb : st)) || (rc = xb_copy(LVX_FAM_ACCEL, st))) return rc;
-    }
-    if (ctx->has_prior) {
-      DevBuf& pb = ctx->d_zero;   // identity permutation for the single prior block (zeroed by ensure_layout)
-      PriorFam p{1, ctx->prior_t, mkq(ctx->prior_q[0], ctx->prior_q[1], ctx->prior_q[2], ctx->prior_q[3]), (const int*)pb.p, ctx->prior_w, 0.0};
-      ProfScope ps(ctx, LVX_FAM_PRIOR, st);
-      launch_family<PriorFam, 1>(xb, dim3(1), dim3(64), st, p, cm, (const uint16_t*)ctx->d_pairs[2].p, (long long)ctx->fam_row0[2]);
-      if ((rc = xb_copy(LVX_FAM_PRIOR, st))) return rc;
-    }
-    // ---- LiDAR surfel blocks ----
-    if (ctx->surf.n > 0) {
-      ProfScope ps(ctx, LVX_FAM_SURFEL, st);
-      if (fast_surf && tauL) {
-        SurfAccT<true> f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const double*)ctx->surf.d_b3.p, (const int*)ctx->surf.d_perm.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        LVX_LAUNCH_MFMA(SurfAccT<true>, f, LVX_FAM_SURFEL, st, ctx->fam_row0[3]);
-        if (fb_fam(LVX_FAM_SURFEL)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); SurfFamT<true> ff{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-          launch_family<SurfFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
-      } else if (fast_surf) {
-        SurfAcc f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const double*)ctx->surf.d_b3.p, (const int*)ctx->surf.d_perm.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        LVX_LAUNCH_MFMA(SurfAcc, f, LVX_FAM_SURFEL, st, ctx->fam_row0[3]);
-        if (fb_fam(LVX_FAM_SURFEL)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); SurfFam ff{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-          launch_family<SurfFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3], fb_rows(LVX_FAM_SURFEL), fb_cnt(LVX_FAM_SURFEL)); }
-      } else if (tauL) {
-        SurfFamT<true> f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        launch_family<SurfFamT<true>, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
-      } else {
-        SurfFam f{ctx->surf.n, (const double*)ctx->surf.d_t.p, (const double*)ctx->surf.d_a3.p, (const int*)ctx->surf.d_id0.p, (const int*)ctx->surf.d_perm.p, (const double*)ctx->d_planes.p, ctx->t_map, ctx->surf.weight, ctx->surf.huber};
-        launch_family<SurfFam, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[3].p, (long long)ctx->fam_row0[3]);
-      }
-      if ((rc = xb_copy(LVX_FAM_SURFEL, (fast_surf && fb_fam(LVX_FAM_SURFEL)) ? s_fb : st))) return rc;
-    }
-    // ---- camera-landmark-to-surfel blocks ----
-    if (ctx->cs.n > 0) {
-      ProfScope ps(ctx, LVX_FAM_CAMSURF, st);
-      if (fast_cs && tauC) {
-        CamSurfAccT<true> f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        LVX_LAUNCH_MFMA(CamSurfAccT<true>, f, LVX_FAM_CAMSURF, st, ctx->fam_row0[5]);
-        if (fb_fam(LVX_FAM_CAMSURF)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); CamSurfFamT<true> ff{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-          launch_family<CamSurfFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
-      } else if (fast_cs) {
-        CamSurfAcc f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        LVX_LAUNCH_MFMA(CamSurfAcc, f, LVX_FAM_CAMSURF, st, ctx->fam_row0[5]);
-        if (fb_fam(LVX_FAM_CAMSURF)) { if ((rc = fb_fork())) return rc; ProfScope psf(ctx, LVX_KERNEL_FIXUP, s_fb); CamSurfFam ff{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-          launch_family<CamSurfFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), s_fb, ff, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5], fb_rows(LVX_FAM_CAMSURF), fb_cnt(LVX_FAM_CAMSURF)); }
-      } else if (tauC) {
-        CamSurfFamT<true> f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        launch_family<CamSurfFamT<true>, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
-      } else {
-        CamSurfFam f{ctx->cs.n, (const int*)ctx->cs.d_id0.p, (const int*)ctx->cs.d_id1.p, (const int*)ctx->cs.d_perm.p, (const double*)ctx->d_planes.p, (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->t_map, ctx->cs.weight, ctx->cs.huber};
-        launch_family<CamSurfFam, 1>(xb, grid(f.n), dim3(64), st, f, cm, (const uint16_t*)ctx->d_pairs[5].p, (long long)ctx->fam_row0[5]);
-      }
-      if ((rc = xb_copy(LVX_FAM_CAMSURF, (fast_cs && fb_fam(LVX_FAM_CAMSURF)) ? s_fb : st))) return rc;
-    }
-    // ---- reprojection blocks ----
-    if (ctx->rep.n > 0) {
-      ReprojFam r{ctx->rep.n, (const int*)ctx->rep.d_id0.p, (const double*)ctx->rep.d_a3.p, (const double*)ctx->rep.d_t.p, (const int*)ctx->rep.d_perm.p,
-                  (const double*)ctx->d_lm_uv.p, (const double*)ctx->d_lm_t0.p, ctx->rep.weight, ctx->rep.huber};
-      // the fused path (Jacobian rows materialised once, three MFMA assembly passes, landmark rows stored) for a locked AND for a free camera time offset
-      auto rep_fused = [&](auto TAUC) -> int {
-        constexpr bool T = decltype(TAUC)::value;
-        constexpr int RJ = REP_NC + (T ? 1 : 0);
-        double* Jb = (double*)ctx->d_repB[0].p; double* rb = Jb + (size_t)2 * RJ * r.n; int* kb = (int*)ctx->d_repB[1].p;
-        { ProfScope ps(ctx, LVX_KERNEL_REP_JAC, st);
-          const ReprojFamT<T> rf{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-          double* trec = (ctx->L > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS) && ctx->rep_groups > 0 && (what & LVX_EVAL_NORMAL_EQ)) ? (double*)ctx->d_repT.p : (double*)nullptr;
-          const size_t lds_j = trec ? (size_t)64 * ((56 + (T ? 1 : 0)) | 1) * 8 : 0;
-          if (xb) hipLaunchKernelGGL((k_reproj_jac<T, true>), grid(r.n), dim3(64), lds_j, st, rf, cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec);
-          else hipLaunchKernelGGL(k_reproj_jac<T>, grid(r.n), dim3(64), lds_j, st, rf, cm, Jb, rb, kb, (long long)ctx->fam_row0[4], trec); }
-        if (!fb_fam(LVX_FAM_REPROJ)) { const int rcc = xb_copy(LVX_FAM_REPROJ, st); if (rcc) return rcc; }   // (listed blocks: behind the exact kernel, rep_fixup)
-        if (!(what & LVX_EVAL_NORMAL_EQ)) return LVX_OK;
-        const RepJac jac{Jb, rb, kb, r.n};
-        if (s_side != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_jac, st)); LVX_HIP(ctx, hipStreamWaitEvent(s_side, ctx->ev_jac, 0)); side_used = true; }
-        { RepSideAcc<0, T> rr{r.n, jac, 0.0};
-          ProfScope ps(ctx, LVX_KERNEL_REP_REF, s_side); LVX_LAUNCH_MFMA1X(LVX_T2(RepSideAcc<0, T>), 1, false, rr, LVX_FAM_PRIOR, s_side, ctx->fam_row0[4]); }
-        { RepSideAcc<1, T> ro{r.n, jac, 0.0};
-          ProfScope ps(ctx, LVX_KERNEL_REP_OBS, st); LVX_LAUNCH_MFMA1X(LVX_T2(RepSideAcc<1, T>), 1, false, ro, LVX_FAM_REPROJ, st, ctx->fam_row0[4]); }
-        if (ctx->rep_groups > 0) {
-          const int* gt = (const int*)ctx->d_repB[2].p;
-          RepCross rx{jac, r.lm, gt, gt + ctx->rep_groups + 1, ctx->rep_groups, (double*)ctx->d_repT.p, nullptr};
-          { ProfScope ps(ctx, LVX_KERNEL_REP_CROSS, st);
-            if (det && ctx->det_cross_col.size() > 1) {
-              for (size_t q = 0; q + 1 < ctx->det_cross_col.size(); ++q) {
-                rx.det_list = (const int*)ctx->d_det_cross.p + ctx->det_cross_col[q];
-                hipLaunchKernelGGL(k_reproj_cross<T>, dim3((unsigned)(ctx->det_cross_col[q + 1] - ctx->det_cross_col[q])), dim3(64 * RX_NW), 0, st, rx, cm);
-              }
-            } else
-            hipLaunchKernelGGL(k_reproj_cross<T>, dim3((unsigned)std::min((ctx->rep_groups + RX_NW - 1) / RX_NW, 256 * 8)), dim3(64 * RX_NW), 0, st, rx, cm); }
-          if (ctx->L > 0 && !(ctx->locks & LVX_LOCK_LANDMARKS)) {
-            const int* lp = (const int*)ctx->d_repB[3].p;
-            const RepLmRows lq{(const double*)ctx->d_repT.p, kb, r.n, lp, lp + ctx->L + 1, ctx->L};
-            const size_t lds = (size_t)4 * ctx->lm_ls * 8;
-            LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_reproj_lmrows<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            ProfScope ps(ctx, LVX_KERNEL_REP_LMROWS, st);
-            hipLaunchKernelGGL(k_reproj_lmrows<T>, dim3((unsigned)((ctx->L + 3) / 4)), dim3(256), lds, st, lq, cm);
-          }
-        }
-        return LVX_OK;
-      };
-      // ONE launch (round 6): evaluation, assembly and landmark rows per landmark-owning workgroup; nothing materialised
-      auto rep_one = [&](auto TAUC) -> int {
-        constexpr bool T = decltype(TAUC)::value;
-        const ReprojFamT<T> rf{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-        const int* tab = (const int*)ctx->d_repF.p;
-        const int ng = ctx->rep_fused_wg;
-        const RepFused q{tab, tab + ng, ng};
-        int ncu = 256;
-        { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, ctx->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount; }
-        ProfScope ps(ctx, LVX_KERNEL_REP_FUSED, st);
-        hipLaunchKernelGGL(k_reproj_fused<T>, dim3((unsigned)std::min((ng + 3) / 4, ncu)), dim3(256), 0, st, rf, q, cm, (long long)ctx->fam_row0[4]);
-        return LVX_OK;
-      };
-      auto rep_fixup = [&]() {   // listed blocks by the exact kernel, behind the landmark rows' stores
-        if (!fb_fam(LVX_FAM_REPROJ)) return;
-        ProfScope psf(ctx, LVX_KERNEL_FIXUP, st);
-        if (tauC) { ReprojFamT<true> rt{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-          launch_family<ReprojFamT<true>, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ)); }
-        else launch_family<ReprojFam, LVX_PW>(xb, fb_grid, dim3(64 * LVX_PW), st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4], fb_rows(LVX_FAM_REPROJ), fb_cnt(LVX_FAM_REPROJ));
-      };
-      if (fast && ctx->rep_fused_wg > 0 && !xb) {   // (k_reproj_fused writes no records: with them the chain runs)
-        const int rcf = tauC ? rep_one(std::true_type{}) : rep_one(std::false_type{});
-        if (rcf) return rcf;
-        rep_fixup();
-      } else if (fast) {
-        const int rcf = tauC ? rep_fused(std::true_type{}) : rep_fused(std::false_type{});
-        if (rcf) return rcf;
-        rep_fixup();
-        if (fb_fam(LVX_FAM_REPROJ) && (rc = xb_copy(LVX_FAM_REPROJ, st))) return rc;
-      } else if (tauC) {
-        ProfScope ps(ctx, LVX_FAM_REPROJ, st);
-        ReprojFamT<true> rt{r.n, r.lm, r.uv, r.t0o, r.perm, r.lm_uv, r.lm_t0, r.weight, r.huber};
-        launch_family<ReprojFamT<true>, LVX_PW>(xb, grid(r.n), dim3(64 * LVX_PW), st, rt, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
-      } else {
-        ProfScope ps(ctx, LVX_FAM_REPROJ, st);
-        launch_family<ReprojFam, LVX_PW>(xb, grid(r.n), dim3(64 * LVX_PW), st, r, cm, (const uint16_t*)ctx->d_pairs[4].p, (long long)ctx->fam_row0[4]);
-      }
-      if (!fast && (rc = xb_copy(LVX_FAM_REPROJ, st))) return rc;
-    }
-    if (side_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[0], s_side)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[0], 0)); }
-    if (fb_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[2], s_fb)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[2], 0)); }
-    { ProfScope ps(ctx, LVX_KERNEL_FOLD);
-      const bool fold_fast = (what & LVX_EVAL_NORMAL_EQ) && (fast_surf || fast_cs);
-      // replica sums -> dense block (the last replica block to finish) and the border-row fold (Bd, streaming; disjoint buffers) in one launch
-      const unsigned n_rep_blk = (unsigned)((ctx->nbd_ext * ctx->nbd_ext + 255) / 256);
-      if (fold_fast && ctx->nb > 0 && !sw.serial) {
-        const unsigned n_rows_blk = (unsigned)((ctx->nb + 255) / 256);
-        const int set0 = fast_surf ? 0 : 1, set1 = (fast_surf && fast_cs) ? 1 : -1;
-        const size_t lds = ((size_t)ctx->nbd_ext * ctx->nbd_ext + ctx->nbd_ext) * 8;
-        LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_fold_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(k_fold_all, dim3(n_rep_blk + n_rows_blk), dim3(256), lds, st, cm, (int)n_rep_blk, (int)n_rows_blk, set0, 1, set1, 0, (int*)ctx->d_zero.p + 1);
-      } else {
-        hipStream_t s_fold = (fold_fast && side_on) ? ctx->fam_stream[0] : st;
-        if (s_fold != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_fork, st)); LVX_HIP(ctx, hipStreamWaitEvent(s_fold, ctx->ev_fork, 0)); }
-        hipLaunchKernelGGL(k_fold_replicas, dim3(n_rep_blk), dim3(256), 0, st, cm);
-        if (fold_fast) {
-          for (int set = 0; set < 2; ++set) if (ctx->nb > 0 && ((set == 0 && fast_surf) || (set == 1 && fast_cs)))
-            hipLaunchKernelGGL(k_fold_border_rows, dim3((unsigned)((ctx->nb + 255) / 256)), dim3(256), 0, s_fold, cm, set, (set == 0 || !fast_surf) ? 1 : 0);
-          const size_t lds = ((size_t)ctx->nbd_ext * ctx->nbd_ext + ctx->nbd_ext) * 8;
-          LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_fold_border_dense, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-          hipLaunchKernelGGL(k_fold_border_dense, dim3(1), dim3(256), lds, st, cm);
-          if (s_fold != st) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[1], s_fold)); LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_join[1], 0)); }
-        }
-      } }
-    LVX_HIP(ctx, hipGetLastError());
-    return rc;
-  };
-  // graph replay pays for small problems (a pass is ~35 API calls: launch-bound at ~0.37 ms issued call by call, 0.26 ms replayed); at config-4 size the kernels are long
-  // enough for the host to stay ahead and the replayed graph is the SLOWER one (0.61 against 0.58 ms: its cross-stream edges become barrier packets between every node)
-  const bool use_graph = !ctx->sw.no_graph && !ctx->profiling && !(what & (LVX_EVAL_JACOBIAN | LVX_EVAL_JACOBIAN_BLOCKS)) && ctx->n_blocks <= 400000;   // the records' copies are issued call by call
-  if (!use_graph) { if ((rc = enqueue())) return rc; }
-  else {
-    const int flags = (want_res_buffer ? 1 : 0) | (ctx->force_legacy ? 2 : 0) | (ctx->fb_on ? 4 : 0) | (ctx->fb_mask << 3);   // a switch change bumps cfg_version
-    hipGraphExec_t exec = nullptr;
-    for (const auto& e : ctx->graphs) if (e.state == state_d && e.what == what && e.flags == flags && e.cfg == ctx->cfg_version) { exec = (hipGraphExec_t)e.exec; break; }
-    if (!exec) {
-      if (ctx->graphs.size() >= 16) { for (auto& e : ctx->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec); ctx->graphs.clear(); }
-      hipGraph_t graph = nullptr;
-      LVX_HIP(ctx, hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
-      rc = enqueue();
-      const hipError_t ce = hipStreamEndCapture(st, &graph);
-      if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-      if (ce != hipSuccess || !graph) return fail(ctx, LVX_E_HIP, std::string("hipStreamEndCapture: ") + hipGetErrorString(ce));
-      const hipError_t ie = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
-      if (ie != hipSuccess) return fail(ctx, LVX_E_HIP, std::string("hipGraphInstantiate: ") + hipGetErrorString(ie));
-      ctx->graphs.push_back({state_d, what, flags, ctx->cfg_version, (void*)exec});
-    }
-    LVX_HIP(ctx, hipGraphLaunch(exec, st));
-  }
-  ctx->last_what = what;
-  ctx->last_state_d = state_d; ctx->last_want_res = want_res_buffer;
+  Pass p = make_pass(ctx, cm, what);
+  if ((rc = launch_pass(p, state_d, want_res_buffer))) return rc;
+  ctx->last_what = what; ctx->last_state_d = state_d; ctx->last_want_res = want_res_buffer;
   ctx->err_unchecked = cost == nullptr;   // the device error word of this pass has not been looked at yet (check_last_eval)
   if (cost) {
     if (!ctx->pin) { LVX_HIP(ctx, hipHostMalloc((void**)&ctx->pin, 128 * 8, hipHostMallocDefault)); std::memset(ctx->pin, 0, 128 * 8); }
@@ -3067,22 +3082,11 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
     LVX_HIP(ctx, hipMemcpyAsync(ctx->pin + 1, cm.err, 4 * (4 + LVX_NUM_FAM), hipMemcpyDeviceToHost, st));
     if (ctx->before_eval_sync) ctx->before_eval_sync();   // (a pass repeated below calls it again: it then reads the repeated pass's results)
     LVX_HIP(ctx, hipStreamSynchronize(st));
-    const double c = ctx->pin[0];
+    *cost = ctx->pin[0];
     std::memcpy(err, ctx->pin + 1, 4 * (4 + LVX_NUM_FAM));
-    *cost = c;
-    ctx->fallback_rows = 0; for (int f = 0; f < LVX_NUM_FAM; ++f) ctx->fallback_rows += err[4 + f];
-    if ((err[0] & LVX_ERR_FALLBACK) && !ctx->force_legacy) {
-      // rows the fused kernels cannot take exactly.  First the ROW-LEVEL fallback: the same pass with fallback lists — the fused kernels skip those rows, the exact
-      // per-segment kernel evaluates just them (a few small launches more per pass from now on).  Only when the lists overflow, or for a corner that is not a row's
-      // (|tau_imu| >= dt), everything goes to the per-segment kernels.
-      int need = 0; for (int f = 0; f < LVX_NUM_FAM; ++f) if (err[4 + f] > 0) need |= 1 << f;
-      if (!ctx->sw.force_legacy && need && (need & ~ctx->fb_mask)) { ctx->fb_on = true; ctx->fb_mask |= need; }   // a family without a list yet: give it one
-      else ctx->force_legacy = true;                                                                              // a list overflowed, or the corner is not a row's
-      return run_evaluate(ctx, state_d, what, cost, want_res_buffer);
-    }
-    if (err[0] & RES_RANGE) return fail(ctx, LVX_E_RANGE, "time span out of range for trajectory");
-    if (err[0] & RES_NONUNIT) return fail(ctx, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
-    if (err[0] & 4) return fail(ctx, LVX_E_STATE, "normal-equation entry outside the computed bandwidth");
+    bool rerun = false;
+    if ((rc = finish_pass_errors(ctx, err, &rerun))) return rc;
+    if (rerun) return run_evaluate(ctx, state_d, what, cost, want_res_buffer);
   }
   ctx->xb_valid = xb;
   return LVX_OK;
@@ -3093,22 +3097,15 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
 // per-segment kernels, a range / unit-quaternion error is returned instead of a step computed from incomplete sums.
 int check_last_eval(lvx_ctx* c) {
   if (!c->err_unchecked || !c->d_err.p) return LVX_OK;
-  int err = 0;
-  LVX_HIP(c, hipMemcpyAsync(&err, c->d_err.p, 4, hipMemcpyDeviceToHost, c->stream));
+  int errw[4 + LVX_NUM_FAM] = {0};
+  LVX_HIP(c, hipMemcpyAsync(errw, c->d_err.p, sizeof(errw), hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
   c->err_unchecked = false;
-  if ((err & LVX_ERR_FALLBACK) && !c->force_legacy) {
-    int errw[4 + LVX_NUM_FAM] = {0}, need = 0;
-    LVX_HIP(c, hipMemcpy(errw, c->d_err.p, sizeof(errw), hipMemcpyDeviceToHost));
-    for (int f = 0; f < LVX_NUM_FAM; ++f) if (errw[4 + f] > 0) need |= 1 << f;
-    if (!c->sw.force_legacy && need && (need & ~c->fb_mask)) { c->fb_on = true; c->fb_mask |= need; } else c->force_legacy = true;
-    double cost = 0;
-    return run_evaluate(c, c->last_state_d, c->last_what, &cost, c->last_want_res);
-  }
-  if (err & RES_RANGE) return fail(c, LVX_E_RANGE, "time span out of range for trajectory");
-  if (err & RES_NONUNIT) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
-  if (err & 4) return fail(c, LVX_E_STATE, "normal-equation entry outside the computed bandwidth");
-  return LVX_OK;
+  bool rerun = false;
+  const int rc = finish_pass_errors(c, errw, &rerun);
+  if (rc || !rerun) return rc;
+  double cost = 0;
+  return run_evaluate(c, c->last_state_d, c->last_what, &cost, c->last_want_res);
 }
 
 }  // namespace lvx
