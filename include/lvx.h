@@ -545,6 +545,51 @@ int lvx_render_map_d(lvx_ctx* ctx, const double* state, double map_time, int n, 
  * LVX_E_STATE: no spline / camera / scans; LVX_E_ARG: a scan index outside the scans, a NULL pointer.  n_pairs = 0: LVX_OK. */
 int lvx_overlay_scans(lvx_ctx* ctx, const double* state, int n_pairs, const int32_t* scan_index, const double* scan_t, const double* image_t, uint8_t* mask, int32_t* valid);
 
+/* trajectory queries -------------------------------------------------------------------------------------------------------*/
+/* TrajectoryView::Evaluate(t, flags) for a batch of times (kontiki/trajectories/uniform_r3_spline_trajectory.h:36-103, uniform_so3_spline_trajectory.h:46-125).
+ * A sample at t in frame F is valid iff MinTime <= t + tau_F < MaxTime (MinTime = t0, MaxTime = t0 + (N - 3) dt: the test of evaluateLidarPose,
+ * trajectory_manager_lvi.cpp:401-402); the t - 1e-5 retry of SplineView::Evaluate (spline_base.h:196-203) is not part of a query.  NaN and +-inf are invalid.  An invalid
+ * sample writes zeros to every requested output and valid = 0.
+ *   LVX_FRAME_TRAJECTORY: the spline itself (tau = 0): p, v = p', a = p'', q (x, y, z, w), omega in the WORLD frame (Kontiki's convention: the gyroscope model rotates it
+ *     by q*, sensors/imu.h:87-91).
+ *   LVX_FRAME_LIDAR / LVX_FRAME_CAMERA: the sensor at t + tau_S with the extrinsics (q_S, p_S) of the state: q = q(tt) (x) q_S, p = q(tt) p_S + p(tt) — the same bits as
+ *     lvx_evaluate_lidar_pose / lvx_evaluate_camera_pose —, the velocity of the sensor origin v(tt) + omega(tt) x (q(tt) p_S), omega(tt).  The acceleration of a sensor frame
+ *     needs the angular acceleration, which Kontiki does not offer: requesting it is LVX_E_ARG.
+ * Any output pointer but valid may be NULL (not computed); arrays are [n][3] / [n][4].
+ * A sample inside the range whose four-knot window holds a control quaternion that fails logq's 1e-5 unit check (quaternion_math.h:19-23) gets valid = 0 and zeros; the
+ * call returns LVX_E_NONUNIT_QUAT with all other samples filled, as lvx_error_statistics reports.
+ * LVX_E_ARG: NULL context, NULL valid / out / t / state, n <= 0, unknown frame, sensor-frame acceleration.  LVX_E_STATE: before lvx_set_spline. */
+#define LVX_FRAME_TRAJECTORY 0
+#define LVX_FRAME_LIDAR 1
+#define LVX_FRAME_CAMERA 2
+typedef struct lvx_traj_samples {
+  double *position3, *velocity3, *acceleration3, *orientation_xyzw4, *angular_velocity3; int32_t* valid;
+} lvx_traj_samples;
+int lvx_sample_trajectory(lvx_ctx* ctx, const double* state, int frame, int n, const double* t, const lvx_traj_samples* out);
+/* The same on device memory: state_d (NULL: the state of lvx_set_state), t_d and the pointers inside *out_d (a host struct) are device addresses.  Only enqueues on the
+ * context's stream; the caller synchronises.  A non-unit quaternion is reported by the next lvx_synchronize, as the errors of a queued evaluation pass are. */
+int lvx_sample_trajectory_d(lvx_ctx* ctx, const double* state_d, int frame, int n, const double* t_d, const lvx_traj_samples* out_d);
+/* Imu::Gyroscope / Imu::Accelerometer with constant biases (sensors/imu.h:61-101, constant_bias_imu.h:51-61) at tt = t + tau_imu: gyro = q* omega + b_g,
+ * acc = q* (p'' + g(roll, pitch)) + b_a with G = -9.79 (imu.h:25) — what the gyroscope / accelerometer residuals subtract from the measurement.  Validity, zeros and error
+ * codes as lvx_sample_trajectory; gyro3 or acc3 may be NULL. */
+int lvx_predict_imu(lvx_ctx* ctx, const double* state, int n, const double* t, double* gyro3, double* acc3, int32_t* valid);
+int lvx_predict_imu_d(lvx_ctx* ctx, const double* state_d, int n, const double* t_d, double* gyro3_d, double* acc3_d, int32_t* valid_d);
+/* How far the trajectory is from reference poses (q' (x, y, z, w) — normalised on the way in —, p') at the stamps t, e.g. the LOAM poses the calibration started from:
+ * LIinitializer::PublishTrajectory (lvi_initialize_surfel_orb.cpp:834-902) lays the two paths side by side.  Per valid sample (validity as lvx_sample_trajectory, pose in
+ * `frame`): translation error |p - p'|, rotation error 2 atan2(|vec(d)|, |d.w|) with d = q* (x) q' (Eigen's angularDistance).
+ *   LVX_ALIGN_NONE: compared as given.  LVX_ALIGN_FIRST: with a the lowest valid index and A = T_a o R_a^-1, every reference pose becomes A o R_i (PublishTrajectory's
+ *   Twl * Tl, :850-861, for a first pose that need not be the identity).
+ * Relative errors: for each valid sample i and the NEXT valid one j, T_i^-1 T_j against R_i^-1 R_j (unaligned reference: they do not depend on align).
+ * A summary holds rmse, mean and max of its n terms; argmax is the lowest sample index of the maximum (of i for a relative step).  n_valid = 0: all-zero summaries and
+ * LVX_OK.  abs_trans_n / abs_rot_n (NULL or [n]): the per-sample absolute errors, 0 for an invalid sample.  Sums are formed in a fixed order: two calls return the same
+ * bits.  Error codes as lvx_sample_trajectory. */
+typedef struct lvx_err_summary { double rmse, mean, max; int32_t argmax, n; } lvx_err_summary;
+typedef struct lvx_pose_errors { int32_t n, n_valid; lvx_err_summary abs_trans, abs_rot, rel_trans, rel_rot; } lvx_pose_errors;
+#define LVX_ALIGN_NONE 0
+#define LVX_ALIGN_FIRST 1
+int lvx_compare_poses(lvx_ctx* ctx, const double* state, int frame, int n, const double* t, const double* q_xyzw4, const double* p3, int align, lvx_pose_errors* out,
+                      double* abs_trans_n, double* abs_rot_n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,7 @@ void lvx_destroy(lvx_ctx* c) {
   if (c->d_comm.p) (void)hipFree(c->d_comm.p);
   bcr_destroy(c);
   stats_destroy(c);
+  traj_destroy(c);
   for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv}) if (b->p) (void)hipFree(b->p);
   for (auto& e : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);
@@ -287,7 +288,7 @@ int lvx_synchronize(lvx_ctx* c) {
   if (!c) return LVX_E_ARG;
   LVX_HIP(c, hipSetDevice(c->device));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
-  if (!c->d_err.p) return LVX_OK;
+  if (!c->d_err.p || !c->last_state_d) return traj_check_d(c);   // no pass has run on this context: the layout allocates the error words, the first pass's clear kernel writes them
   int errw[4 + LVX_NUM_FAM] = {0};
   LVX_HIP(c, hipMemcpy(errw, c->d_err.p, sizeof(errw), hipMemcpyDeviceToHost));
   const int err = errw[0];
@@ -301,7 +302,7 @@ int lvx_synchronize(lvx_ctx* c) {
   if (err & RES_RANGE) return fail(c, LVX_E_RANGE, "time span out of range for trajectory");
   if (err & RES_NONUNIT) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
   if (err & 4) return fail(c, LVX_E_STATE, "normal-equation entry outside the computed bandwidth");
-  return LVX_OK;
+  return traj_check_d(c);   // the _d trajectory queries report a non-unit control quaternion here, after the pass's own errors
 }
 int lvx_set_profiling(lvx_ctx* c, int enable) { if (!c) return LVX_E_ARG; c->profiling = enable != 0; c->profile_only = enable >= 2 ? enable - 2 : -1; return LVX_OK; }
 int lvx_get_kernel_ms(lvx_ctx* c, double* ms_sum, int64_t* launches) {

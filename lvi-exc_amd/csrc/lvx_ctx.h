@@ -165,6 +165,9 @@ struct lvx_ctx {
   uint64_t st_cfg = 0, st_plist_cfg = 0; bool st_valid = false, st_plist_valid = false; int st_P = 0, st_L = 0;
   // coloured map / overlay (lvx_render.hip): [0] times + pose table + counter, [1] state, [2] cloud or pair block, [3] images or poses, [4] records or masks
   lvx::DevBuf d_rn[5];
+  // trajectory queries (lvx_traj.hip): [0] state, [1] times and reference poses, [2] sample outputs, [3] flag words {host-array calls, _d calls}, [4] pose-error work;
+  // pinned mirror of the small results; tj_d_unchecked: a _d query was enqueued since lvx_synchronize last looked at its flag word
+  lvx::DevBuf d_tj[5]; double* h_tj = nullptr; bool tj_d_unchecked = false;
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];
   size_t assoc_rings = 0; int assoc_wpr = 0, assoc_list_total = 0;
@@ -234,6 +237,8 @@ int bcr_backward(lvx_ctx* c, double* Zy, double* Zx, int ldz, int nrhs);
 int bcr_gram(lvx_ctx* c, const double* Z, int ldz, int n, double* M, int row_major_nz = 0);
 void bcr_destroy(lvx_ctx* c);
 void stats_destroy(lvx_ctx* c);   // lvx_stats.hip
+void traj_destroy(lvx_ctx* c);    // lvx_traj.hip
+int traj_check_d(lvx_ctx* c);      // lvx_traj.hip: the non-unit-quaternion flag of the _d trajectory queries (lvx_synchronize)
 // leaves + separators elimination (lvx_nd.h): nd_plan decides from the column profile whether it applies (nd_active afterwards) and sizes its buffers
 int nd_plan(lvx_ctx* c, int nrhs);
 bool nd_active(const lvx_ctx* c);

@@ -95,6 +95,61 @@ inline bool WritePcdAscii(const std::string& path, const std::vector<lvx_point_x
 }
 struct RenderResult { std::vector<lvx_point_xyzrgb> cloud; std::vector<int32_t> candidates, valid; int64_t n_colored = 0; };
 
+// ---- trajectory queries (lvx_sample_trajectory / lvx_compare_poses): what LIinitializer::PublishTrajectory (lvi_initialize_surfel_orb.cpp:834-902) builds on the host ----
+// its sampling loop (:875-891): `t = begin; while (t < end) { ...; t += step; }` — the ACCUMULATED sum, not begin + k * step
+inline std::vector<double> SampleTimes(double t_begin, double t_end, double step) {
+  std::vector<double> t;
+  if (!(step > 0.0)) return t;
+  for (double x = t_begin; x < t_end; x += step) t.push_back(x);
+  return t;
+}
+inline void ThrowOnError(lvx_ctx* ctx, int rc) {
+  if (rc == LVX_OK) return;
+  const std::string msg = ctx ? lvx_last_error(ctx) : "lvx error";
+  if (rc == LVX_E_RANGE) throw std::range_error(msg);
+  throw std::runtime_error(msg + " (lvx error " + std::to_string(rc) + ")");
+}
+// arrays [n][3] / [n][4] (x, y, z, w); acceleration stays empty for a sensor frame (lvx.h); an invalid sample holds zeros
+struct TrajectorySamples { std::vector<double> t, position, velocity, acceleration, orientation_xyzw, angular_velocity; std::vector<int32_t> valid; };
+inline TrajectorySamples SampleTrajectory(lvx_ctx* ctx, const std::vector<double>& state, int frame, const std::vector<double>& times) {
+  TrajectorySamples r; r.t = times;
+  const size_t n = times.size();
+  if (n == 0) return r;
+  r.position.assign(3 * n, 0.0); r.velocity.assign(3 * n, 0.0); r.orientation_xyzw.assign(4 * n, 0.0); r.angular_velocity.assign(3 * n, 0.0); r.valid.assign(n, 0);
+  if (frame == LVX_FRAME_TRAJECTORY) r.acceleration.assign(3 * n, 0.0);
+  lvx_traj_samples o{r.position.data(), r.velocity.data(), r.acceleration.empty() ? nullptr : r.acceleration.data(), r.orientation_xyzw.data(), r.angular_velocity.data(), r.valid.data()};
+  ThrowOnError(ctx, lvx_sample_trajectory(ctx, state.data(), frame, (int)n, times.data(), &o));
+  return r;
+}
+struct PoseComparison { lvx_pose_errors errors{}; std::vector<double> abs_trans, abs_rot; };
+// reference poses as ReadPoseGT returns them (stamp_ns, p, q w x y z): the stamps become stamp_ns * 1e-9 seconds
+inline PoseComparison ComparePoses(lvx_ctx* ctx, const std::vector<double>& state, int frame, const std::vector<PoseStamped>& poses, int align) {
+  PoseComparison r;
+  const size_t n = poses.size();
+  if (n == 0) return r;
+  std::vector<double> t(n), q(4 * n), p(3 * n);
+  for (size_t i = 0; i < n; ++i) {
+    t[i] = static_cast<double>(poses[i].stamp_ns) * 1e-9;
+    for (int k = 0; k < 3; ++k) { p[3 * i + k] = poses[i].p[k]; q[4 * i + k] = poses[i].q_wxyz[1 + k]; }
+    q[4 * i + 3] = poses[i].q_wxyz[0];
+  }
+  r.abs_trans.assign(n, 0.0); r.abs_rot.assign(n, 0.0);
+  ThrowOnError(ctx, lvx_compare_poses(ctx, state.data(), frame, (int)n, t.data(), q.data(), p.data(), align, &r.errors, r.abs_trans.data(), r.abs_rot.data()));
+  return r;
+}
+// LOAM's pose file, one line per pose: `stamp_ns tx ty tz qw qx qy qz`, 17 significant digits so that ReadPoseGT (lvx_loaders.hpp) reads back the same doubles.
+// p [n][3], q [n][4] (x, y, z, w)
+inline bool WritePoseFile(const std::string& path, const std::vector<int64_t>& stamps_ns, const std::vector<double>& p, const std::vector<double>& q_xyzw) {
+  if (p.size() != 3 * stamps_ns.size() || q_xyzw.size() != 4 * stamps_ns.size()) return false;
+  std::FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) return false;
+  for (size_t i = 0; i < stamps_ns.size(); ++i)
+    std::fprintf(f, "%lld %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", (long long)stamps_ns[i], p[3 * i], p[3 * i + 1], p[3 * i + 2], q_xyzw[4 * i + 3], q_xyzw[4 * i], q_xyzw[4 * i + 1],
+                 q_xyzw[4 * i + 2]);
+  return std::fclose(f) == 0;
+}
+
+
 class Calibrator {
  public:
   // `in` is copied: the calibrator may outlive the caller's object
@@ -170,6 +225,16 @@ class Calibrator {
     o.valid.assign(st.size(), 0); o.masks.assign(st.size() * (size_t)in_.camera.rows * in_.camera.cols, 0);
     if (!st.empty()) check(lvx_overlay_scans(ctx_, state.data(), (int)st.size(), o.scan_of_pair.data(), st.data(), it.data(), o.masks.data(), o.valid.data()));
     return o;
+  }
+  // the optimised path of PublishTrajectory (:873-891): `frame` sampled every `step` seconds from the first to the last IMU stamp (the reference: LiDAR frame, 0.05 s)
+  TrajectorySamples SampleTrajectory(const std::vector<double>& state, int frame = LVX_FRAME_LIDAR, double step = 0.05) {
+    if (in_.imu_t.empty()) return TrajectorySamples{};
+    return lvx_host::SampleTrajectory(ctx_, state, frame, SampleTimes(in_.imu_t.front(), in_.imu_t.back(), step));
+  }
+  // the LOAM path beside it (:849-870): LiDAR-frame pose errors against CalibrateInput::loam (every pose, or the key poses integration_frames_lidar_), anchored at the
+  // first valid pose with LVX_ALIGN_FIRST
+  PoseComparison CompareWithLoam(const std::vector<double>& state, int align = LVX_ALIGN_FIRST, bool key_only = false) {
+    return ComparePoses(ctx_, state, LVX_FRAME_LIDAR, key_only ? in_.loam.key : in_.loam.all, align);
   }
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }

@@ -900,6 +900,94 @@ def overlay_scans(ctx, state, scan_index, scan_t, image_t, rows, cols):
     return mask, valid.astype(bool)
 
 
+FRAME_TRAJECTORY, FRAME_LIDAR, FRAME_CAMERA = 0, 1, 2
+ALIGN_NONE, ALIGN_FIRST = 0, 1
+TRAJ_FIELDS = ("position", "velocity", "acceleration", "orientation", "angular_velocity")   # member order of lvx_traj_samples; orientation is (x, y, z, w)
+
+
+class TrajSamples(C.Structure):
+    """lvx_traj_samples: host or device addresses; a NULL member is not computed."""
+    _fields_ = [("position3", C.c_void_p), ("velocity3", C.c_void_p), ("acceleration3", C.c_void_p), ("orientation_xyzw4", C.c_void_p), ("angular_velocity3", C.c_void_p),
+                ("valid", C.c_void_p)]
+
+
+class ErrSummary(C.Structure):
+    _fields_ = [("rmse", C.c_double), ("mean", C.c_double), ("max", C.c_double), ("argmax", C.c_int32), ("n", C.c_int32)]
+
+
+class PoseErrors(C.Structure):
+    """lvx_pose_errors"""
+    _fields_ = [("n", C.c_int32), ("n_valid", C.c_int32), ("abs_trans", ErrSummary), ("abs_rot", ErrSummary), ("rel_trans", ErrSummary), ("rel_rot", ErrSummary)]
+
+
+def sample_trajectory(ctx, state, t, frame=FRAME_TRAJECTORY, fields=TRAJ_FIELDS):
+    """TrajectoryView::Evaluate for a batch of times (lvx_sample_trajectory).  Returns a dict with the requested fields ([n][3], orientation [n][4] x, y, z, w) and
+    "valid" (bool); an invalid sample holds zeros.  A non-unit control quaternion raises LvxError(E_NONUNIT_QUAT) whose `partial` attribute is that dict."""
+    t = _d(np.atleast_1d(t))
+    n = len(t)
+    for f in fields:
+        if f not in TRAJ_FIELDS:
+            raise ValueError("unknown field %r" % (f,))
+    out = {f: np.zeros((n, 4 if f == "orientation" else 3)) for f in TRAJ_FIELDS if f in fields}
+    valid = np.zeros(n, np.int32)
+    s = TrajSamples(*[out[f].ctypes.data if f in out else None for f in TRAJ_FIELDS], valid.ctypes.data)
+    rc = ctx._l.lvx_sample_trajectory(ctx._h, _p(_d(state)), C.c_int(frame), C.c_int(n), _p(t), C.byref(s))
+    out["valid"] = valid.astype(bool)
+    if rc == E_NONUNIT_QUAT:
+        e = LvxError(rc, ctx._l.lvx_last_error(ctx._h).decode())
+        e.partial = out
+        raise e
+    ctx._ck(rc)
+    return out
+
+
+def sample_trajectory_d(ctx, t_d_ptr, n, out_d_ptrs, valid_d_ptr, frame=FRAME_TRAJECTORY, state_d_ptr=None):
+    """lvx_sample_trajectory_d: device addresses (e.g. torch.Tensor.data_ptr()); out_d_ptrs maps field names to addresses.  state_d_ptr = None: the state of set_state.
+    Only enqueues; synchronize() reports a non-unit quaternion."""
+    s = TrajSamples(*[out_d_ptrs.get(f) for f in TRAJ_FIELDS], valid_d_ptr)
+    ctx._ck(ctx._l.lvx_sample_trajectory_d(ctx._h, C.c_void_p(state_d_ptr) if state_d_ptr else None, C.c_int(frame), C.c_int(n), C.c_void_p(t_d_ptr), C.byref(s)))
+
+
+def predict_imu(ctx, state, t):
+    """What the IMU model reads at the times t (lvx_predict_imu): (gyro [n][3], acc [n][3], valid bool)."""
+    t = _d(np.atleast_1d(t))
+    n = len(t)
+    gyro, acc, valid = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, np.int32)
+    rc = ctx._l.lvx_predict_imu(ctx._h, _p(_d(state)), C.c_int(n), _p(t), _p(gyro), _p(acc), _p(valid))
+    if rc == E_NONUNIT_QUAT:
+        e = LvxError(rc, ctx._l.lvx_last_error(ctx._h).decode())
+        e.partial = (gyro, acc, valid.astype(bool))
+        raise e
+    ctx._ck(rc)
+    return gyro, acc, valid.astype(bool)
+
+
+def predict_imu_d(ctx, t_d_ptr, n, gyro_d_ptr, acc_d_ptr, valid_d_ptr, state_d_ptr=None):
+    ctx._ck(ctx._l.lvx_predict_imu_d(ctx._h, C.c_void_p(state_d_ptr) if state_d_ptr else None, C.c_int(n), C.c_void_p(t_d_ptr), C.c_void_p(gyro_d_ptr) if gyro_d_ptr else None,
+                                     C.c_void_p(acc_d_ptr) if acc_d_ptr else None, C.c_void_p(valid_d_ptr)))
+
+
+def compare_poses(ctx, state, frame, t, q, p, align=ALIGN_NONE):
+    """Pose errors of the trajectory against reference poses q [n][4] (x, y, z, w), p [n][3] at the stamps t (lvx_compare_poses).  Returns a dict: n, n_valid, the four
+    summaries abs_trans / abs_rot / rel_trans / rel_rot (dicts rmse, mean, max, argmax, n) and the per-sample abs_trans_n / abs_rot_n."""
+    t, q, p = _d(np.atleast_1d(t)), _d(q).reshape(-1, 4), _d(p).reshape(-1, 3)
+    n = len(t)
+    assert len(q) == n and len(p) == n
+    o = PoseErrors()
+    at, ar = np.zeros(n), np.zeros(n)
+    rc = ctx._l.lvx_compare_poses(ctx._h, _p(_d(state)), C.c_int(frame), C.c_int(n), _p(t), _p(q), _p(p), C.c_int(align), C.byref(o), _p(at), _p(ar))
+    out = {"n": o.n, "n_valid": o.n_valid, "abs_trans_n": at, "abs_rot_n": ar}
+    for k in ("abs_trans", "abs_rot", "rel_trans", "rel_rot"):
+        s = getattr(o, k)
+        out[k] = {"rmse": s.rmse, "mean": s.mean, "max": s.max, "argmax": s.argmax, "n": s.n}
+    if rc == E_NONUNIT_QUAT:
+        e = LvxError(rc, ctx._l.lvx_last_error(ctx._h).decode())
+        e.partial = out
+        raise e
+    ctx._ck(rc)
+    return out
+
+
 def load_problem(obj, P, locks=None):
     """Feed a synth.make_problem() dict into an lvx.Context or an oracle.Oracle (same setter names)."""
     obj.set_spline(P["t0"], P["dt"], P["n_knots"])
