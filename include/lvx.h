@@ -590,6 +590,35 @@ typedef struct lvx_pose_errors { int32_t n, n_valid; lvx_err_summary abs_trans, 
 int lvx_compare_poses(lvx_ctx* ctx, const double* state, int frame, int n, const double* t, const double* q_xyzw4, const double* p3, int align, lvx_pose_errors* out,
                       double* abs_trans_n, double* abs_rot_n);
 
+/* Sensor-to-IMU rotation from odometry: InertialInitializer::EstimateRotation (src/lvi_exc/src/core/inertial_initializer.cpp:26-81), which CalibrHelperLVI::Initialization
+ * (src/lvi_exc/src/core/calib_helper_lvi.cpp:44-96) calls after Solve #0 on the odometry poses so far — from 30 poses on, at every 10th — until one prefix passes.  For
+ * consecutive odometry poses (t_i, q'_i), (t_j, q'_j) it pairs the SO3 spline's relative rotation d_i = q(t_i)* (x) q(t_j) with the odometry's d_s = q'_i* (x) q'_j (q'
+ * normalised on the way in, d_s with w >= 0), weights the pair by huber = delta > huber_deg ? huber_deg / delta : 1 (delta: difference of the two rotation angles, degrees)
+ * and solves q_s (x) x = x (x) q_i over all pairs: x is the right singular vector of the smallest singular value of the stacked huber (L(d_s) - R(d_i)).
+ *   x = q_ItoS; the mounting rotation of the state is its conjugate, q_LtoI = conj(q_ItoS) (calib_helper_lvi.cpp:67-68).  Reported with w >= 0.
+ *   sigma: the four singular values, descending.  ok = n_pairs >= min_pairs and sigma[2] > min_sigma (the reference's 15 and cov(2) > 0.25); with fewer pairs the record
+ *   holds the identity and zero sigmas, as the reference returns before the SVD.
+ *   Prefix k uses the poses 0 .. prefix_len[k] - 1.  Its pair list ends at the first j with t_j + tau >= MaxTime (:39-40) or a non-finite stamp.
+ * The call is sensor-agnostic: camera odometry quaternions give q_ItoC the same way.  The spline is evaluated in LVX_FRAME_TRAJECTORY: no sensor offset of the state enters.
+ * Two deviations from the reference: (1) a pair with an evaluation time outside [MinTime, MaxTime) — t_i + tau < MinTime — is skipped and counted in n_skipped, where the
+ * reference's Evaluate would throw std::range_error; (2) the list of shifts tau of the odometry stamps: the same system at t + tau[s] for every s, whose sigma[3] is
+ * smallest at the true time offset of the sensor (a coarse offset for lvx_set_time_offset_bounds' small interval); the reference has tau = 0 only.
+ * A pair whose spline window holds a control quaternion that fails logq's unit check is skipped (and counted in n_skipped); the call then returns LVX_E_NONUNIT_QUAT with
+ * everything else filled, as lvx_sample_trajectory does.  All sums are formed in a fixed order: two calls return the same bits.
+ * results: [n_tau][n_prefix]; first_ok: [n_tau], lowest prefix index with ok, or -1.  tau NULL / n_tau 0: one shift of 0.  prefix_len NULL / n_prefix 0: one prefix of n.
+ * LVX_E_ARG: NULL context / state / t / q / results / first_ok, n <= 0, a prefix list that is not non-decreasing with every entry in [1, n].  LVX_E_STATE: before
+ * lvx_set_spline. */
+typedef struct lvx_rotinit_options { double huber_deg; int32_t min_pairs; int32_t reserved; double min_sigma; } lvx_rotinit_options;   /* 1.0, 15, 0.25 */
+typedef struct lvx_rotinit_result { double q_ItoS_xyzw[4]; double sigma[4]; int32_t n_poses, n_pairs, n_skipped, ok; } lvx_rotinit_result;
+int lvx_rotinit_default_options(lvx_rotinit_options* opt);
+int lvx_estimate_rotation(lvx_ctx* ctx, const double* state, int n, const double* t, const double* q_xyzw4, int n_prefix, const int32_t* prefix_len, int n_tau, const double* tau,
+                          const lvx_rotinit_options* opt, lvx_rotinit_result* results, int32_t* first_ok);
+/* The same on device memory: state_d (NULL: the state of lvx_set_state), t_d, q_xyzw4_d, prefix_len_d, tau_d, results_d and first_ok_d are device addresses (opt is a host
+ * struct).  Only enqueues on the context's stream; a non-unit quaternion is reported by the next lvx_synchronize.  The device prefix list is not validated: an entry is
+ * read clamped to [1, n]. */
+int lvx_estimate_rotation_d(lvx_ctx* ctx, const double* state_d, int n, const double* t_d, const double* q_xyzw4_d, int n_prefix, const int32_t* prefix_len_d, int n_tau,
+                            const double* tau_d, const lvx_rotinit_options* opt, lvx_rotinit_result* results_d, int32_t* first_ok_d);
+
 #ifdef __cplusplus
 }
 #endif

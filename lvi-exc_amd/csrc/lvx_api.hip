@@ -111,6 +111,7 @@ void lvx_destroy(lvx_ctx* c) {
   bcr_destroy(c);
   stats_destroy(c);
   traj_destroy(c);
+  rotinit_destroy(c);
   for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv}) if (b->p) (void)hipFree(b->p);
   for (auto& e : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);

@@ -168,6 +168,9 @@ struct lvx_ctx {
   // trajectory queries (lvx_traj.hip): [0] state, [1] times and reference poses, [2] sample outputs, [3] flag words {host-array calls, _d calls}, [4] pose-error work;
   // pinned mirror of the small results; tj_d_unchecked: a _d query was enqueued since lvx_synchronize last looked at its flag word
   lvx::DevBuf d_tj[5]; double* h_tj = nullptr; bool tj_d_unchecked = false;
+  // rotation from odometry (lvx_rotinit.hip): [0] state, [1] stamps, quaternions, shifts, prefix list and the result records, [2] piece sums and per-tile drop lanes;
+  // its flag words and their pinned mirror are the trajectory queries'
+  lvx::DevBuf d_ri[3];
   // upstream kernels (lvx_upstream.hip)
   lvx::DevBuf d_up[8];
   size_t assoc_rings = 0; int assoc_wpr = 0, assoc_list_total = 0;
@@ -238,6 +241,7 @@ int bcr_gram(lvx_ctx* c, const double* Z, int ldz, int n, double* M, int row_maj
 void bcr_destroy(lvx_ctx* c);
 void stats_destroy(lvx_ctx* c);   // lvx_stats.hip
 void traj_destroy(lvx_ctx* c);    // lvx_traj.hip
+void rotinit_destroy(lvx_ctx* c); // lvx_rotinit.hip
 int traj_check_d(lvx_ctx* c);      // lvx_traj.hip: the non-unit-quaternion flag of the _d trajectory queries (lvx_synchronize)
 // leaves + separators elimination (lvx_nd.h): nd_plan decides from the column profile whether it applies (nd_active afterwards) and sizes its buffers
 int nd_plan(lvx_ctx* c, int nrhs);

@@ -12,6 +12,8 @@
 // The FIRST DataAssociation (InitializationDone branch, :1175-1178) takes its map from per-scan odometry poses — LOAM's, ReadPoseGT (lvx_loaders.hpp) — exactly as the
 // reference with using_loam: CalibrateInput::loam + scan_stamps select it (lvx_data_association_poses: rotation-only de-skew with the SO3 spline of Solve #0, key-scan
 // map, surfel map, association), so a recorded dataset starts from the reference's initial state (identity rotations, zero positions) with nothing hand-fitted.
+// CalibrateOptions::init_lidar_rotation adds Initialization()'s EstimateRotation loop (calib_helper_lvi.cpp:55-89) after Solve #0: the LiDAR mounting rotation itself then
+// starts from the odometry (lvx_estimate_rotation), e.g. for a LiDAR turned 90 degrees against the IMU, which the surfel stage alone does not recover from identity.
 // Not mirrored: LiDAROdometry's own NDT scan-to-map registration (using_loam = false; lvx_ndt_align is its align()).
 #pragma once
 #include <array>
@@ -42,6 +44,7 @@ struct CalibrateInput {
 };
 struct CalibrateOptions {
   bool solve0_so3_from_gyro = false;     // Initialization()
+  bool init_lidar_rotation = false;      // Initialization()'s EstimateRotation loop after Solve #0 (calib_helper_lvi.cpp:55-89), when LOAM poses are present: q_LtoI from the odometry (lvx_estimate_rotation)
   int refine_iterations = 2;             // DataAssociation + trajInitFromSurfel rounds (the reference runs batch + 2 refinements)
   bool lvi_stage = true;                 // trajInitFromLVIdata
   bool camera_surfel_stage = false;      // the third stage with camera-landmark-to-surfel blocks
@@ -58,7 +61,8 @@ struct CalibrateOptions {
 struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_surfel_points = 0, n_cam_surfel = 0;
                      std::vector<double> cost_history, radius_history; std::vector<int32_t> accepted;   // per-iteration trace of the stage's solve (lvx_lm_get_history)
                      std::vector<double> state_in;   // the state the stage's solve started from (CalibrateOptions::keep_history)
-                     bool has_stats = false; lvx_error_stats stats_before{}, stats_after{}; };   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
+                     bool has_stats = false; lvx_error_stats stats_before{}, stats_after{};   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
+                     int init_prefix = -1; lvx_rotinit_result init{}; };   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
 struct AssociationRecord { std::vector<double> state; std::vector<lvx_surfel_plane> planes; std::vector<double> pt, pt_map, t; std::vector<int32_t> plane; std::vector<float> scans_in_map; };
@@ -149,6 +153,58 @@ inline bool WritePoseFile(const std::string& path, const std::vector<int64_t>& s
   return std::fclose(f) == 0;
 }
 
+// ---- rotation initialisation (lvx_estimate_rotation): CalibrHelperLVI::Initialization's loop around InertialInitializer::EstimateRotation (calib_helper_lvi.cpp:55-89) ----
+// the odometry sizes at which the reference tries (:62-64): 30, 40, ... <= n
+inline std::vector<int32_t> InitializationPrefixes(int n) {
+  std::vector<int32_t> p;
+  for (int k = 30; k <= n; k += 10) p.push_back(k);
+  return p;
+}
+// records [taus][prefixes]; first_ok[tau]: the first prefix that passes (-1: none — the reference's "[Initialization] fails")
+struct RotationInit {
+  std::vector<int32_t> prefix_len; std::vector<double> taus; std::vector<lvx_rotinit_result> results; std::vector<int32_t> first_ok;
+  const lvx_rotinit_result& at(size_t tau, size_t prefix) const { return results[tau * prefix_len.size() + prefix]; }
+};
+// odometry stamps t [n] and rotations q [n][4] (x, y, z, w) on the reference's schedule, for every shift of `taus` (empty: the reference's single shift of 0).  Fewer than
+// 30 poses: nothing is tried, first_ok = -1.
+inline RotationInit EstimateRotation(lvx_ctx* ctx, const std::vector<double>& state, const std::vector<double>& t, const std::vector<double>& q_xyzw, const std::vector<double>& taus = {},
+                                     const lvx_rotinit_options* opt = nullptr) {
+  RotationInit r; r.prefix_len = InitializationPrefixes((int)t.size()); r.taus = taus.empty() ? std::vector<double>{0.0} : taus;
+  r.first_ok.assign(r.taus.size(), -1);
+  if (r.prefix_len.empty()) return r;
+  if (q_xyzw.size() != 4 * t.size()) throw std::invalid_argument("EstimateRotation: one quaternion per stamp");
+  r.results.assign(r.taus.size() * r.prefix_len.size(), lvx_rotinit_result{});
+  ThrowOnError(ctx, lvx_estimate_rotation(ctx, state.data(), (int)t.size(), t.data(), q_xyzw.data(), (int)r.prefix_len.size(), r.prefix_len.data(), (int)r.taus.size(), r.taus.data(), opt,
+                                          r.results.data(), r.first_ok.data()));
+  return r;
+}
+// odometry poses as ReadPoseGT returns them (stamp_ns, p, q w x y z)
+inline RotationInit EstimateRotation(lvx_ctx* ctx, const std::vector<double>& state, const std::vector<PoseStamped>& poses, const std::vector<double>& taus = {}) {
+  std::vector<double> t(poses.size()), q(4 * poses.size());
+  for (size_t i = 0; i < poses.size(); ++i) {
+    t[i] = static_cast<double>(poses[i].stamp_ns) * 1e-9;
+    for (int k = 0; k < 3; ++k) q[4 * i + k] = poses[i].q_wxyz[1 + k];
+    q[4 * i + 3] = poses[i].q_wxyz[0];
+  }
+  return EstimateRotation(ctx, state, t, q, taus);
+}
+// Eigen's Quaternion(Matrix3d) on the rotation block of a row-major 4 x 4 pose (x, y, z, w)
+inline void QuaternionOfPose(const double T[16], double q[4]) {
+  const double m[3][3] = {{T[0], T[1], T[2]}, {T[4], T[5], T[6]}, {T[8], T[9], T[10]}};
+  double tr = m[0][0] + m[1][1] + m[2][2];
+  if (tr > 0.0) {
+    double s = std::sqrt(tr + 1.0); q[3] = 0.5 * s; s = 0.5 / s;
+    q[0] = (m[2][1] - m[1][2]) * s; q[1] = (m[0][2] - m[2][0]) * s; q[2] = (m[1][0] - m[0][1]) * s;
+  } else {
+    int i = 0;
+    if (m[1][1] > m[0][0]) i = 1;
+    if (m[2][2] > m[i][i]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double s = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0); q[i] = 0.5 * s; s = 0.5 / s;
+    q[3] = (m[k][j] - m[j][k]) * s; q[j] = (m[j][i] + m[i][j]) * s; q[k] = (m[k][i] + m[i][k]) * s;
+  }
+}
+
 
 class Calibrator {
  public:
@@ -176,6 +232,7 @@ class Calibrator {
     if ((int)state->size() != lvx_state_size(ctx_)) throw std::invalid_argument("state size does not match the problem");
     std::vector<StageReport> rep;
     if (opt_.solve0_so3_from_gyro) rep.push_back(Solve0(state));
+    if (opt_.init_lidar_rotation && !in_.loam.all.empty()) rep.push_back(InitializeRotation(state));
     for (int it = 0; it < opt_.refine_iterations; ++it) {
       if (it == 0 && !in_.loam.all.empty()) FirstDataAssociation(*state); else
       DataAssociation(*state);
@@ -255,6 +312,27 @@ class Calibrator {
     return r;
   }
   bool pose_of_scan(int idx, double scan_t, double T[16]) const { return PoseOfScan(in_.loam, in_.simulation, idx, scan_t, T); }
+  // Initialization()'s loop (calib_helper_lvi.cpp:55-89) on the odometry poses of the scans (the poses PoseOfScan selects; a scan without one is left out): the first
+  // prefix of the schedule that passes sets q_LtoI = conj(q_ItoS); none: the reference's "[Initialization] fails"
+  StageReport InitializeRotation(std::vector<double>* state) {
+    if (in_.scan_stamps.empty()) throw std::invalid_argument("scan_stamps: the header stamps of the scans are needed for the rotation initialisation");
+    std::vector<double> t, q;
+    for (size_t s = 0; s < in_.scan_stamps.size(); ++s) {
+      double T[16], qs[4];
+      if (!pose_of_scan((int)s, in_.scan_stamps[s], T)) continue;
+      QuaternionOfPose(T, qs);
+      t.push_back(in_.scan_stamps[s]); q.insert(q.end(), qs, qs + 4);
+    }
+    const RotationInit ri = EstimateRotation(ctx_, *state, t, q);
+    if (ri.first_ok[0] < 0) throw std::runtime_error("[Initialization] fails: no prefix of the " + std::to_string(t.size()) + " odometry poses passes the singular-value test");
+    StageReport r{"Initialization", {}};
+    r.init_prefix = ri.first_ok[0]; r.init = ri.at(0, (size_t)ri.first_ok[0]);
+    double* ql = state->data() + 7 * (size_t)in_.n_knots + 16;
+    for (int k = 0; k < 3; ++k) ql[k] = -r.init.q_ItoS_xyzw[k];
+    ql[3] = r.init.q_ItoS_xyzw[3];
+    if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] Initialization: %d odometry poses, q_LtoI (x y z w) %.6f %.6f %.6f %.6f, sigma[2] %.4f\n", r.init.n_poses, ql[0], ql[1], ql[2], ql[3], r.init.sigma[2]);
+    return r;
+  }
   lvx_assoc_options assoc_options(double plane_lambda) const {
     lvx_assoc_options ao; lvx_assoc_default_options(&ao);
     ao.ndt_resolution = opt_.ndt_resolution; ao.plane_lambda = plane_lambda; ao.fit_threshold = opt_.fit_threshold; ao.min_leaf_points = opt_.min_leaf_points;

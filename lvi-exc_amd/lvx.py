@@ -988,6 +988,57 @@ def compare_poses(ctx, state, frame, t, q, p, align=ALIGN_NONE):
     return out
 
 
+class RotInitOptions(C.Structure):
+    """lvx_rotinit_options (defaults 1.0, 15, 0.25: default_rotinit_options)."""
+    _fields_ = [("huber_deg", C.c_double), ("min_pairs", C.c_int32), ("reserved", C.c_int32), ("min_sigma", C.c_double)]
+
+
+class RotInitResult(C.Structure):
+    """lvx_rotinit_result: q_ItoS (x, y, z, w; q_LtoI is its conjugate), the four singular values, counts and the reference's verdict."""
+    _fields_ = [("q_ItoS_xyzw", C.c_double * 4), ("sigma", C.c_double * 4), ("n_poses", C.c_int32), ("n_pairs", C.c_int32), ("n_skipped", C.c_int32), ("ok", C.c_int32)]
+
+
+ROTINIT_DTYPE = np.dtype([("q_ItoS_xyzw", np.float64, 4), ("sigma", np.float64, 4), ("n_poses", np.int32), ("n_pairs", np.int32), ("n_skipped", np.int32), ("ok", np.int32)])
+assert ROTINIT_DTYPE.itemsize == C.sizeof(RotInitResult) == 80
+
+
+def default_rotinit_options():
+    o = RotInitOptions()
+    rc = lib().lvx_rotinit_default_options(C.byref(o))
+    if rc:
+        raise LvxError(rc, "lvx_rotinit_default_options")
+    return o
+
+
+def estimate_rotation(ctx, state, t, q, prefix_len=None, tau=None, opt=None):
+    """InertialInitializer::EstimateRotation for every prefix and every shift of the odometry stamps (lvx_estimate_rotation): t [n], q [n][4] (x, y, z, w).  Returns
+    (results, first_ok): a record array [n_tau][n_prefix] of ROTINIT_DTYPE and, per shift, the lowest prefix index with ok or -1.  prefix_len None: one prefix of n;
+    tau None: one shift of 0.  A non-unit control quaternion raises LvxError(E_NONUNIT_QUAT) whose `partial` attribute is that pair."""
+    t, q = _d(np.atleast_1d(t)), _d(q).reshape(-1, 4)
+    n = len(t)
+    assert len(q) == n
+    pl = None if prefix_len is None else _i(np.atleast_1d(prefix_len))
+    ta = None if tau is None else _d(np.atleast_1d(tau))
+    n_prefix, n_tau = (0 if pl is None else len(pl)), (0 if ta is None else len(ta))
+    res, first = np.zeros((max(n_tau, 1), max(n_prefix, 1)), ROTINIT_DTYPE), np.zeros(max(n_tau, 1), np.int32)
+    rc = ctx._l.lvx_estimate_rotation(ctx._h, _p(_d(state)), C.c_int(n), _p(t), _p(q), C.c_int(n_prefix), _p(pl), C.c_int(n_tau), _p(ta), C.byref(opt) if opt is not None else None,
+                                      _p(res), _p(first))
+    if rc == E_NONUNIT_QUAT:
+        e = LvxError(rc, ctx._l.lvx_last_error(ctx._h).decode())
+        e.partial = (res, first)
+        raise e
+    ctx._ck(rc)
+    return res, first
+
+
+def estimate_rotation_d(ctx, t_d_ptr, q_d_ptr, n, results_d_ptr, first_ok_d_ptr, prefix_len_d_ptr=None, n_prefix=0, tau_d_ptr=None, n_tau=0, opt=None, state_d_ptr=None):
+    """lvx_estimate_rotation_d: device addresses (e.g. torch.Tensor.data_ptr()); results_d: [max(n_tau, 1)][max(n_prefix, 1)] records of 80 bytes.  state_d_ptr = None: the
+    state of set_state.  Only enqueues; synchronize() reports a non-unit quaternion."""
+    ctx._ck(ctx._l.lvx_estimate_rotation_d(ctx._h, C.c_void_p(state_d_ptr) if state_d_ptr else None, C.c_int(n), C.c_void_p(t_d_ptr), C.c_void_p(q_d_ptr), C.c_int(n_prefix),
+                                           C.c_void_p(prefix_len_d_ptr) if prefix_len_d_ptr else None, C.c_int(n_tau), C.c_void_p(tau_d_ptr) if tau_d_ptr else None,
+                                           C.byref(opt) if opt is not None else None, C.c_void_p(results_d_ptr), C.c_void_p(first_ok_d_ptr)))
+
+
 def load_problem(obj, P, locks=None):
     """Feed a synth.make_problem() dict into an lvx.Context or an oracle.Oracle (same setter names)."""
     obj.set_spline(P["t0"], P["dt"], P["n_knots"])
