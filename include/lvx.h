@@ -308,6 +308,9 @@ typedef struct lvx_scanreg_out {
   int32_t* sharp; int32_t* less_sharp; int32_t* flat; int32_t* less_flat;
   int32_t counts[4];
 } lvx_scanreg_out;
+/* n_rings: 1 .. 1024 (otherwise LVX_E_ARG).  Points whose ring id is >= n_rings are DROPPED like the points the range / NaN filter removes (the reference indexes its
+ * per-ring vector with the id unchecked).  A ring is cut into six sectors of at most 2048 points each, i.e. rings of up to 12299 kept points; a longer sector returns
+ * LVX_E_ARG "scan sector longer than the LDS sort capacity" and the context stays usable. */
 int lvx_scan_register(lvx_ctx* ctx, int n, const lvx_rs_point* pts, int n_rings, float min_range, lvx_scanreg_out* out);
 /* The same for n_sweeps sweeps in ONE call (laserCloudHandler is invoked once per sweep, scanRegistration.cpp:134; sweeps are independent): pts holds the sweeps
  * back to back, sweep s = pts[sweep_offsets[s] .. sweep_offsets[s + 1]) (sweep_offsets[0] = 0), outs[s] its caller-owned output buffers (capacity = its input count).
@@ -322,7 +325,9 @@ int lvx_scan_register_get(lvx_ctx* ctx, int sweep, lvx_scanreg_out* out);
  * for the sweep of the last lvx_scan_register of this context.  out_xyzi4 [max_out][4], ring_counts [n_rings] (may be NULL), *n_out = total
  * (also when larger than max_out).  Points of a voxel are averaged in their input order (pcl's std::sort leaves the order of equal keys open). */
 int lvx_scan_less_flat_downsample(lvx_ctx* ctx, float leaf_size, int max_out, float* out_xyzi4, int32_t* ring_counts, int32_t* n_out);
-/* the same for sweep `sweep` of the context's last lvx_scan_register_batch (sweep 0 = the call above) */
+/* the same for sweep `sweep` of the context's last lvx_scan_register_batch (sweep 0 = the call above).  A ring is down-sampled in one LDS sort of at most 4096 less-flat
+ * points (rings of about 4200 kept points): beyond that the call returns LVX_E_ARG "more less-flat points in one ring than the LDS sort capacity (4096)", writes nothing,
+ * and the context and its registration results stay usable. */
 int lvx_scan_less_flat_downsample_sweep(lvx_ctx* ctx, int sweep, float leaf_size, int max_out, float* out_xyzi4, int32_t* ring_counts, int32_t* n_out);
 
 /* pclomp::VoxelGridCovariance::applyFilter (src/ndt_omp/include/pclomp/voxel_grid_covariance_omp_impl.hpp:49-374): the grid stays on the

@@ -37,6 +37,7 @@ int orc_scan_register(int n_in, const void* pts_v, int n_rings, float min_range,
     const RsPoint& p = in[i];
     if (p.x * p.x + p.y * p.y + p.z * p.z < min_range * min_range) continue;
     if (std::isnan(p.x) || std::isnan(p.y) || std::isnan(p.z)) continue;
+    if (p.ring >= n_rings) continue;   // the reference indexes laserCloudScans with it unchecked (:199-279): undefined there, dropped here and in the library
     kept.push_back(p);
   }
   const int cloudSize = static_cast<int>(kept.size());

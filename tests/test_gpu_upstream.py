@@ -10,7 +10,9 @@ import pytest
 import lvx
 import synth
 from oracle import oracle as O
+from upstream_checks import check_scanreg as _check_scanreg
 from upstream_checks import check_voxels as _check_voxels
+from upstream_checks import tie_sectors as _tie_sectors
 
 pytestmark = pytest.mark.gpu
 
@@ -20,23 +22,6 @@ def ctx():
     c = lvx.Context(0)
     yield c
     c.close()
-
-
-def _check_scanreg(ctx, pts, n_rings, min_range, strict=True):
-    ro = O.scan_register(pts, n_rings, min_range)
-    rg = lvx.scan_register(ctx, pts, n_rings, min_range)
-    assert rg["n"] == ro["n"]
-    assert np.array_equal(rg["scan_start"], ro["scan_start"]) and np.array_equal(rg["scan_end"], ro["scan_end"])
-    assert np.array_equal(rg["cloud"].view(np.uint32), ro["cloud"].view(np.uint32))
-    assert np.array_equal(rg["curvature"].view(np.uint32), ro["curvature"].view(np.uint32))
-    if strict:
-        for k in ("label", "picked", "sort_ind", "sharp", "less_sharp", "flat", "less_flat"):
-            assert np.array_equal(rg[k], ro[k]), k
-    else:   # equal curvatures inside a sector: std::sort (unstable) may order them differently -> compare modulo tie permutation
-        c = ro["curvature"]
-        assert np.array_equal(c[rg["sort_ind"]].view(np.uint32), c[ro["sort_ind"]].view(np.uint32))
-        assert np.array_equal(np.sort(rg["sort_ind"]), np.sort(ro["sort_ind"]))
-    return ro
 
 
 @pytest.mark.parametrize("seed", [1, 3, 4])
@@ -50,16 +35,6 @@ def test_scan_register_vlp16_bit_exact(ctx, seed):
             sp, ep = s + (e - s) * j // 6, s + (e - s) * (j + 1) // 6 - 1
             assert len(np.unique(c[sp:ep + 1])) == ep - sp + 1
     assert len(ro["sharp"]) > 100 and len(ro["flat"]) > 300
-
-
-def _tie_sectors(ro):
-    c, n = ro["curvature"], 0
-    for i in range(len(ro["scan_start"])):
-        s, e = ro["scan_start"][i], ro["scan_end"][i]
-        for j in range(6):
-            sp, ep = s + (e - s) * j // 6, s + (e - s) * (j + 1) // 6 - 1
-            n += len(np.unique(c[sp:ep + 1])) < ep - sp + 1
-    return n
 
 
 @pytest.mark.parametrize("kw,min_tie_sectors", [(dict(seed=2), 1), (dict(seed=1, range_quantum=0.002, noise=0.003), 1), (dict(seed=1, xyz_quantum=0.004, noise=0.005), 20),
