@@ -451,8 +451,9 @@ int lvx_surfel_extract(lvx_ctx* ctx, double p_lambda, double dist_threshold, int
 typedef struct lvx_point_xyzit { float x, y, z, pad; float intensity; float pad2; double timestamp; } lvx_point_xyzit;
 /* The chronological SurfelPoint emission of getAssociation (src/lvi_exc/src/core/surfel_association.cpp:141-158) for n_scans associated scans (flags from
  * lvx_surfel_assoc_batch_d), all device-resident: per scan column-major (w outer, h inner), points with a flag and a non-zero raw timestamp; scans concatenated.
- * SurfelPoint fields as arrays: raw point (LiDAR frame), point in the map frame, timestamp, plane id.  *n_out = total (also when larger than max_out: nothing is
- * written then; size the outputs and call again); per_scan_counts[n_scans] may be NULL. */
+ * SurfelPoint fields as arrays: raw point (LiDAR frame), point in the map frame, timestamp, plane id.  *n_out = total and per_scan_counts are those of the whole
+ * list, also when it is longer than max_out: the entries below max_out are unspecified then (written in part, in full or not at all) and nothing at or beyond
+ * max_out is written; size the outputs from *n_out and call again.  max_out = 0 with NULL outputs only counts.  per_scan_counts[n_scans] may be NULL. */
 int lvx_surfel_emit_d(lvx_ctx* ctx, int n_scans, int H, int W, const int32_t* flags_d, const float* scans_map_d, const lvx_point_xyzit* scans_raw_d, int max_out,
                       double* pt3_d, double* pt_map3_d, double* t_d, int32_t* plane_d, int32_t* n_out, int32_t* per_scan_counts);
 /* getAssociation for n_scans scans with host buffers in and out (what DataAssociation's loop over the scans does, lvi_initialize_surfel_orb.cpp:1192-1199): flags

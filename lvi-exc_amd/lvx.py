@@ -598,19 +598,47 @@ def surfel_assoc_emit(ctx, scans_map, scans_raw, p4, box_min, box_max, radius=0.
                                            C.c_void_p(flags_d.data_ptr())))
     finally:
         l.lvx_surfel_map_release(ctx._h)
+    e = surfel_emit(ctx, flags_d, sm_d, raw_d)
+    return flags_d.cpu().numpy().reshape(S, H, W), dict(pt=e["pt"], pt_map=e["pt_map"], t=e["t"], plane=e["plane"], counts=e["counts"])
+
+
+def surfel_emit(ctx, flags, scans_map, scans_raw, max_out=None, out=None):
+    """lvx_surfel_emit_d: the chronological SurfelPoint list of S associated scans.  flags [S, H, W] int32, scans_map [S, H, W, 4] float32, scans_raw [S, H, W]
+    POINT_XYZIT: numpy arrays, or torch tensors already on the device (flags and scans_map shaped as above).
+    max_out = None: one call to count, one to write a list of exactly that size; returns dict(pt, pt_map, t, plane, counts, n).
+    max_out given: ONE call with that capacity.  out = dict(pt, pt_map, t, plane) of device tensors the call writes into (left there for the caller to look at), or
+    None for NULL outputs; returns dict(counts, n) — n is the length of the whole list, also when it exceeds max_out."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if isinstance(flags, np.ndarray):
+        flags = torch.from_numpy(np.array(flags, np.int32)).to(dev)
+    if isinstance(scans_map, np.ndarray):
+        scans_map = torch.from_numpy(np.array(scans_map, np.float32)).to(dev)
+    if isinstance(scans_raw, np.ndarray):
+        scans_raw = torch.from_numpy(np.array(scans_raw, dtype=POINT_XYZIT).view(np.uint8).reshape(-1)).to(dev)
+    S, H, W = scans_map.shape[0], scans_map.shape[1], scans_map.shape[2]
+    l = ctx._l
     n = C.c_int32(0)
     counts = np.zeros(S, np.int32)
-    ctx._ck(l.lvx_surfel_emit_d(ctx._h, C.c_int(S), C.c_int(H), C.c_int(W), C.c_void_p(flags_d.data_ptr()), C.c_void_p(sm_d.data_ptr()), C.c_void_p(raw_d.data_ptr()), C.c_int(0),
-                                None, None, None, None, C.byref(n), _p(counts)))
+
+    def call(cap, o):
+        ptr = [C.c_void_p(o[k].data_ptr()) if o is not None else None for k in ("pt", "pt_map", "t", "plane")]
+        ctx._ck(l.lvx_surfel_emit_d(ctx._h, C.c_int(S), C.c_int(H), C.c_int(W), C.c_void_p(flags.data_ptr()), C.c_void_p(scans_map.data_ptr()), C.c_void_p(scans_raw.data_ptr()), C.c_int(cap),
+                                    ptr[0], ptr[1], ptr[2], ptr[3], C.byref(n), _p(counts)))
+
+    if max_out is not None:
+        call(max_out, out)
+        ctx.synchronize()
+        return dict(counts=counts, n=n.value)
+    call(0, None)
     k = n.value
-    pt_d = torch.empty(max(k, 1) * 3, dtype=torch.float64, device=dev); pm_d = torch.empty_like(pt_d)
-    t_d = torch.empty(max(k, 1), dtype=torch.float64, device=dev); pid_d = torch.empty(max(k, 1), dtype=torch.int32, device=dev)
+    o = dict(pt=torch.empty(max(k, 1) * 3, dtype=torch.float64, device=dev), t=torch.empty(max(k, 1), dtype=torch.float64, device=dev), plane=torch.empty(max(k, 1), dtype=torch.int32, device=dev))
+    o["pt_map"] = torch.empty_like(o["pt"])
     if k:
-        ctx._ck(l.lvx_surfel_emit_d(ctx._h, C.c_int(S), C.c_int(H), C.c_int(W), C.c_void_p(flags_d.data_ptr()), C.c_void_p(sm_d.data_ptr()), C.c_void_p(raw_d.data_ptr()), C.c_int(k),
-                                    C.c_void_p(pt_d.data_ptr()), C.c_void_p(pm_d.data_ptr()), C.c_void_p(t_d.data_ptr()), C.c_void_p(pid_d.data_ptr()), C.byref(n), _p(counts)))
+        call(k, o)
     ctx.synchronize()
-    return flags_d.cpu().numpy().reshape(S, H, W), dict(pt=pt_d.cpu().numpy().reshape(-1, 3)[:k], pt_map=pm_d.cpu().numpy().reshape(-1, 3)[:k], t=t_d.cpu().numpy()[:k],
-                                                          plane=pid_d.cpu().numpy()[:k], counts=counts)
+    return dict(pt=o["pt"].cpu().numpy().reshape(-1, 3)[:k], pt_map=o["pt_map"].cpu().numpy().reshape(-1, 3)[:k], t=o["t"].cpu().numpy()[:k], plane=o["plane"].cpu().numpy()[:k],
+                counts=counts, n=k)
 
 
 def landmark_assoc(ctx, state, q_LtoC_xyzw, t_LinC, map_time, p4, box_min, box_max, radius=0.05):
