@@ -75,6 +75,7 @@ typedef struct lvx_ctx lvx_ctx;
 #define LVX_FAM_REPROJ 4
 #define LVX_FAM_CAMSURF 5
 #define LVX_NUM_FAM 6
+#define LVX_FAM_LIDAR_POS 6   /* LiDAR odometry position blocks (lvx_set_lidar_poses).  NOT counted in LVX_NUM_FAM: the six families of the default schedule keep their arrays */
 
 #define LVX_JAC_WIDTH 64   /* columns per row of the debug Jacobian */
 
@@ -131,6 +132,20 @@ int lvx_set_landmarks(lvx_ctx* ctx, int n_landmarks, const double* uv_ref2, cons
 int lvx_set_reproj(lvx_ctx* ctx, int n, const int32_t* landmark_id, const double* uv_obs2, const double* t0_obs, double huber, double weight);
 /* CameraSurfelLandmark blocks (trajectory_manager_lvi.cpp:584-606) */
 int lvx_set_camsurf(lvx_ctx* ctx, int n, const int32_t* landmark_id, const int32_t* plane_id, double t_map, double huber, double weight);
+/* LiDARPositionMeasurement blocks (kontiki/measurements/lidar_position_measurement.h:23-66, attached by addLidarPoses, trajectory_manager_lvi.cpp:533-559): LiDAR odometry
+ * positions p3[i] = p_Lk in L0 at times t[i], L0 the LiDAR frame at t_start; 3 rows per block, r = weight (q_L^* (q0^* (qk p_LI + pk - p0) - p_LI) - p) — the reference's
+ * Error = weight * Measure (:73), whose Measure ends in `v_L0Lk_L0 - p_Lk_L0` (:59-65: the measured position is subtracted INSIDE Measure) —, Huber on the
+ * block's norm (the reference: weight = global_opt_pos_weight = 1, huber = 5).  n = 0 clears the family.  The odometry's orientation is not used (the reference stores it
+ * and never reads it).  Rows are appended AFTER the camera-surfel rows, in input order: lvx_get_lidar_pose_rows; lvx_get_family_rows is unchanged (its last entry is also
+ * the first LiDAR-pose row); lvx_layout::n_blocks / n_residuals count them.  State, tangent and lock layouts do not change: the blocks touch the knots, the LiDAR
+ * extrinsics and (free) the LiDAR time offset.  lvx_evaluate, lvx_get_jacobian, lvx_get_gradient, lvx_get_normal_eq_dense, lvx_solve_step, lvx_lm_solve and the
+ * shared-extrinsics solve include them.  The start time shares the one hub range with t_map: with surfel or camera-surfel blocks set too, t_start must equal their
+ * t_map bit for bit (LVX_E_ARG from the next call that lays the problem out).  A pose time outside the spline: LVX_E_RANGE from the evaluation, like any other family.
+ * While LiDAR poses are set, LVX_EVAL_JACOBIAN_BLOCKS returns LVX_E_ARG (the family has no per-block record), and so does every evaluation with the
+ * DETERMINISTIC switch on (LVX_DETERMINISTIC=1): the family runs on the per-segment kernel only, whose additions are atomic. */
+int lvx_set_lidar_poses(lvx_ctx* ctx, int n, const double* t, const double* p3, double t_start, double huber, double weight);
+/* first residual row of the LiDAR-pose blocks and the total row count (either pointer may be NULL): block i owns rows row0 + 3 i .. + 2 */
+int lvx_get_lidar_pose_rows(lvx_ctx* ctx, int64_t* row0, int64_t* n_rows_total);
 int lvx_set_locks(lvx_ctx* ctx, uint32_t lock_mask);
 /* experiment / debug switches.  They are read once from the environment (LVX_<NAME>) by lvx_create; this call changes one on a
  * live context (name with or without the LVX_ prefix, e.g. "FORCE_LEGACY", 1).  Unknown name: LVX_E_ARG. */
@@ -166,6 +181,12 @@ typedef struct lvx_error_stats { lvx_family_stats fam[LVX_NUM_FAM]; double cost;
 int lvx_error_statistics(lvx_ctx* ctx, const double* state, lvx_error_stats* out);
 /* state already on the device (NULL: the state of lvx_set_state); one host stop */
 int lvx_error_statistics_d(lvx_ctx* ctx, const double* state_d, lvx_error_stats* out);
+/* the same record for the LiDAR-pose blocks (what printErrorStatistics(..., show_lidar_pos = true) prints): raw error = row / weight per component, n_outliers by the
+ * block's norm; a value-only pass of its own, reduced in a fixed order (identical bits from two calls on one state), one host stop.  lvx_error_stats keeps its six
+ * families.  _d: state already on the device (NULL: the state of lvx_set_state).
+ * lvx_error_stats::cost stays the sum over its six families: with poses set it is lvx_evaluate's cost MINUS this record's cost. */
+int lvx_lidar_pose_statistics(lvx_ctx* ctx, const double* state, lvx_family_stats* out);
+int lvx_lidar_pose_statistics_d(lvx_ctx* ctx, const double* state_d, lvx_family_stats* out);
 /* of the last statistics call; arrays of n_planes / n_landmarks as set by lvx_set_planes / lvx_set_landmarks; any pointer may be NULL.  A plane / landmark without
  * (evaluated) blocks reports n = 0 and zeros.  LVX_E_STATE: no statistics call yet, or the problem changed since; LVX_E_ARG: another count than the tables'. */
 int lvx_get_plane_stats(lvx_ctx* ctx, int n_planes, int64_t* n, double* sum_abs, double* max_abs);        /* surfel family: |point-to-plane distance|, metres */
@@ -237,11 +258,16 @@ int lvx_synchronize(lvx_ctx* ctx);
 #define LVX_KERNEL_REP_LMROWS 14
 #define LVX_KERNEL_REP_FUSED 15     /* round 6: the single-launch reprojection kernel (k_reproj_fused); the five above then stay at zero */
 #define LVX_KERNEL_FIXUP 16         /* the exact per-segment kernel over the fused kernels' fallback lists (lvx_layout::fallback_rows), all families */
-#define LVX_NUM_KERNELS 17
+#define LVX_NUM_KERNELS 17          /* entries lvx_get_kernel_ms writes: unchanged, callers size their arrays by it */
+#define LVX_KERNEL_LIDAR_POS 17     /* the per-segment kernel over the LiDAR-pose blocks: beyond LVX_NUM_KERNELS, read with lvx_get_kernel_ms_ext */
+#define LVX_NUM_KERNELS_EXT 18
 /* enable: 0 off | 1 every launch | 2 + k: only the launches of kernel k (e.g. 2 + LVX_FAM_SURFEL: the dominant kernel — two event
  * records per pass instead of ~20, which cost ~5 % of a config-4 pass).  While profiling is on, passes are issued launch by launch (no graph replay). */
 int lvx_set_profiling(lvx_ctx* ctx, int enable);
 int lvx_get_kernel_ms(lvx_ctx* ctx, double* ms_sum, int64_t* launches);
+/* same for the first n_kernels <= LVX_NUM_KERNELS_EXT ids (arrays of n_kernels).  Both calls read and clear ONE list of records: lvx_get_kernel_ms (and any call with
+ * n_kernels <= 17) discards the LiDAR-pose kernel's records without reporting them — to time that kernel, read with lvx_get_kernel_ms_ext(ctx, LVX_NUM_KERNELS_EXT, ..) only */
+int lvx_get_kernel_ms_ext(lvx_ctx* ctx, int n_kernels, double* ms_sum, int64_t* launches);
 /* Levenberg-Marquardt --------------------------------------------------------------------------------------------
  * Replaces ceres::Solve as configured by TrajectoryEstimator::Solve (kontiki/trajectory_estimator.h:38-68: TRUST_REGION,
  * LEVENBERG_MARQUARDT, SPARSE_SCHUR, max_num_iterations per stage; everything else Ceres defaults).  The trust-region loop,

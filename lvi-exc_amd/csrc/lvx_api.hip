@@ -80,7 +80,9 @@ static void free_family(Family& f) { for (DevBuf* b : {&f.d_t, &f.d_a3, &f.d_b3,
 void lvx_destroy(lvx_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  free_family(c->imu); free_family(c->surf); free_family(c->rep); free_family(c->cs);
+  free_family(c->imu); free_family(c->surf); free_family(c->rep); free_family(c->cs); free_family(c->lp);
+  for (DevBuf* b : {&c->d_pairs_lp, &c->d_lp_part, &c->d_lp_out}) if (b->p) (void)hipFree(b->p);
+  if (c->h_lp) (void)hipHostFree(c->h_lp);
   for (DevBuf* b : {&c->d_planes, &c->d_lm_uv, &c->d_lm_t0, &c->d_ord, &c->d_Hb, &c->d_gb, &c->d_Bd, &c->d_C, &c->d_gc, &c->d_cost, &c->d_err, &c->d_state,
                     &c->d_res, &c->d_jcols, &c->d_jvals, &c->d_L, &c->d_Y, &c->d_S, &c->d_delta, &c->d_diag, &c->d_scal, &c->d_state_try, &c->d_zero})
     if (b->p) (void)hipFree(b->p);
@@ -173,6 +175,19 @@ int lvx_set_camsurf(lvx_ctx* c, int n, const int32_t* lm, const int32_t* plane_i
   }
   Family& f = c->cs; f.n = n; f.id0.assign(lm, lm + n); f.id1.assign(plane_id, plane_id + n);
   f.huber = huber; f.weight = weight; c->t_map = t_map; c->layout_dirty = true; return LVX_OK;
+}
+int lvx_set_lidar_poses(lvx_ctx* c, int n, const double* t, const double* p3, double t_start, double huber, double weight) { if (c) c->cfg_version++;
+  if (!c || n < 0 || (n > 0 && (!t || !p3))) return c ? fail(c, LVX_E_ARG, "lvx_set_lidar_poses: n < 0 or a null array") : LVX_E_ARG;
+  if (n > 0 && !(weight != 0.0)) return fail(c, LVX_E_ARG, "lvx_set_lidar_poses: weight must not be zero");
+  Family& f = c->lp; f.n = n; f.t.assign(t, t + n); f.a3.assign(p3, p3 + 3 * (size_t)n);
+  f.huber = huber; f.weight = weight; c->lp_t_start = t_start; c->layout_dirty = true; return LVX_OK;
+}
+int lvx_get_lidar_pose_rows(lvx_ctx* c, int64_t* row0, int64_t* n_rows_total) {
+  if (!c) return LVX_E_ARG;
+  int rc = ensure_layout(c); if (rc) return rc;
+  if (row0) *row0 = c->fam_row0[LVX_NUM_FAM];
+  if (n_rows_total) *n_rows_total = c->n_residuals;
+  return LVX_OK;
 }
 int lvx_set_switch(lvx_ctx* c, const char* name, int value) {
   if (!c || !name) return LVX_E_ARG;
@@ -306,18 +321,19 @@ int lvx_synchronize(lvx_ctx* c) {
   return traj_check_d(c);   // the _d trajectory queries report a non-unit control quaternion here, after the pass's own errors
 }
 int lvx_set_profiling(lvx_ctx* c, int enable) { if (!c) return LVX_E_ARG; c->profiling = enable != 0; c->profile_only = enable >= 2 ? enable - 2 : -1; return LVX_OK; }
-int lvx_get_kernel_ms(lvx_ctx* c, double* ms_sum, int64_t* launches) {
-  if (!c || !ms_sum || !launches) return LVX_E_ARG;
+int lvx_get_kernel_ms_ext(lvx_ctx* c, int n_kernels, double* ms_sum, int64_t* launches) {
+  if (!c || !ms_sum || !launches || n_kernels < 0 || n_kernels > LVX_NUM_KERNELS_EXT) return LVX_E_ARG;
   LVX_HIP(c, hipSetDevice(c->device));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
-  for (int k = 0; k < LVX_NUM_KERNELS; ++k) { ms_sum[k] = 0.0; launches[k] = 0; }
+  for (int k = 0; k < n_kernels; ++k) { ms_sum[k] = 0.0; launches[k] = 0; }
   for (const auto& r : c->ev_recs) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev_pool[r.e0], c->ev_pool[r.e1]) == hipSuccess && r.kernel >= 0 && r.kernel < LVX_NUM_KERNELS) { ms_sum[r.kernel] += ms; launches[r.kernel] += 1; }
+    if (hipEventElapsedTime(&ms, c->ev_pool[r.e0], c->ev_pool[r.e1]) == hipSuccess && r.kernel >= 0 && r.kernel < n_kernels) { ms_sum[r.kernel] += ms; launches[r.kernel] += 1; }
   }
   c->ev_recs.clear(); c->ev_used = 0;
   return LVX_OK;
 }
+int lvx_get_kernel_ms(lvx_ctx* c, double* ms_sum, int64_t* launches) { return lvx_get_kernel_ms_ext(c, LVX_NUM_KERNELS, ms_sum, launches); }
 
 int lvx_get_jacobian(lvx_ctx* c, int32_t* cols, double* vals) {
   if (!c || !cols || !vals) return LVX_E_ARG;

@@ -100,6 +100,8 @@ struct lvx_ctx {
   double imu_mto = 0.01, sensor_mto = 0.001;
   lvx::CamIntr cam{};
   lvx::Family imu, surf, rep, cs;
+  lvx::Family lp; double lp_t_start = 0;   // LiDAR odometry position blocks (lvx_set_lidar_poses): t, a3 = measured position; their hub time (= t_map when surfel / camera-surfel blocks are set too)
+  lvx::DevBuf d_pairs_lp, d_lp_part, d_lp_out; double* h_lp = nullptr;   // their pair table; statistics: per-workgroup records, the reduced record + flag word, pinned mirror
   bool has_prior = false;
   double prior_t = 0, prior_q[4] = {1, 0, 0, 0}, prior_w = 1;
   double t_map = 0;

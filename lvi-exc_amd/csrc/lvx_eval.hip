@@ -138,6 +138,39 @@ template <bool TAU> struct CamSurfFamT {
   __device__ int col(int c, const Keys& k, int N) const { return cs_col(c, k.k0, k.k1, N); }
 };
 using CamSurfFam = CamSurfFamT<false>;
+// LiDAR odometry position blocks (lvx_resid.h: lidarpos_residual): the two-pose structure of the surfel family — the hub is the pose at the odometry's start time —
+// with 3 rows per block; per-segment kernel only (a LOAM run gives ~10 poses/s against thousands of surfel rows/s)
+template <bool TAU> struct LidarPosFamT {
+  enum { NC = LPOS_NC + (TAU ? 1 : 0), NR = LPOS_NR, USES_HUB = 1, FAM = LVX_FAM_LIDAR_POS, KEYS = 2 };
+  int n; const double* t; const double* pm; const int* perm; double t_start, weight, huber;
+  __device__ void make_hub(const DevCommon& cm, const SplineRef& sp, const Cal& cal, HubShared* h) const {
+    double s1[1][2]; hub_spans(t_start, (cm.locks & LVX_LOCK_LIDAR_TAU) != 0, cm.sensor_mto, s1);
+    Segs sg; KnotRef kh; h->ok = 0;
+    if (!build_segments(sp, s1, 1, &sg)) return;
+    if (!seg_lookup(sp, sg, t_start + cal.lidar.tau, &kh)) return;
+    if (!pose_eval<true, TAU>(sp, kh, &h->A)) { h->ok = -RES_NONUNIT; return; }
+    h->ok = 1;
+  }
+  __device__ int eval(const DevCommon& cm, const SplineRef& sp, const Cal& cal, const HubShared& hub, int si, double r[NR], double (*J)[NC], Keys& k) const {
+    const bool tl = (cm.locks & LVX_LOCK_LIDAR_TAU) != 0;
+    const double tk = t[si];
+    const double pad = tl ? 0.0 : cm.sensor_mto;
+    const double spans[2][2] = {{t_start - pad, t_start + pad}, {tk - pad, tk + pad}};
+    Segs segs;
+    if (!build_segments(sp, spans, 2, &segs)) return RES_RANGE;
+    KnotRef kh;
+    if (!seg_lookup(sp, segs, t_start + cal.lidar.tau, &kh)) return RES_RANGE;
+    const PoseEval* hp = &hub.A;
+    PoseEval own;
+    if (hub.ok != 1 || kh.i0 != hub.A.k.i0 || kh.u != hub.A.k.u) {   // merged-segment corner (spline_base.h:196-203)
+      if (!pose_eval<true, TAU>(sp, kh, &own)) return RES_NONUNIT;
+      hp = &own;
+    }
+    k.k0 = kh.i0; k.lm = 0;
+    return lidarpos_residual<true, TAU>(sp, *hp, segs, cal.lidar, tk, load_v3(pm + 3 * (size_t)si), weight, &k.k1, r, J);
+  }
+  __device__ int col(int c, const Keys& k, int N) const { return surf_col(c, k.k0, k.k1, N); }
+};
 template <bool TAU> struct ReprojFamT {
   enum { NC = REP_NC + (TAU ? 1 : 0), NR = REP_NR, USES_HUB = 0, FAM = LVX_FAM_REPROJ, KEYS = 3 };
   int n; const int* lm; const double* uv; const double* t0o; const int* perm; const double* lm_uv; const double* lm_t0; double weight, huber;
@@ -2337,17 +2370,31 @@ int ensure_layout(lvx_ctx* ctx) {
     if ((rc = upload_tmp(ctx, f.d_id1, pl.data(), pl.size() * 4))) return rc;
     if ((rc = upload_tmp(ctx, f.d_perm, perm.data(), perm.size() * 4))) return rc;
   }
+  {   // LiDAR odometry positions: sorted by knot interval, so that blocks with equal control points are neighbours in the per-segment kernel
+    Family& f = ctx->lp;
+    std::vector<int> key(f.n), perm(f.n);
+    for (int i = 0; i < f.n; ++i) key[i] = host_i0(ctx, f.t[i]);
+    stable_perm_by_key(key, perm);
+    auto ts = gather(f.t, perm, 1); auto pm = gather(f.a3, perm, 3);
+    if ((rc = upload_tmp(ctx, f.d_t, ts.data(), ts.size() * 8))) return rc;
+    if ((rc = upload_tmp(ctx, f.d_a3, pm.data(), pm.size() * 8))) return rc;
+    if ((rc = upload_tmp(ctx, f.d_perm, perm.data(), perm.size() * 4))) return rc;
+  }
   if ((rc = upload_tmp(ctx, ctx->d_planes, ctx->planes.data(), ctx->planes.size() * 8))) return rc;
   if ((rc = upload_tmp(ctx, ctx->d_lm_uv, ctx->lm_uv.data(), ctx->lm_uv.size() * 8))) return rc;
   if ((rc = upload_tmp(ctx, ctx->d_lm_t0, ctx->lm_t0.data(), ctx->lm_t0.size() * 8))) return rc;
   // ---- hub knots (all surfel / cam-surfel residuals evaluate the trajectory at t_map: arrowhead) ----
   ctx->n_hub = 0; ctx->hub0 = 0;
-  if (ctx->surf.n > 0 || ctx->cs.n > 0) {
+  const bool map_fams = ctx->surf.n > 0 || ctx->cs.n > 0;
+  if (map_fams && ctx->lp.n > 0 && std::memcmp(&ctx->lp_t_start, &ctx->t_map, sizeof(double)) != 0)   // one hub range: the odometry's start time shares it with t_map
+    return fail(ctx, LVX_E_ARG, "lvx_set_lidar_poses: t_start differs from the t_map of the surfel / camera-surfel blocks (one hub time per problem)");
+  if (map_fams || ctx->lp.n > 0) {
+    const double t_hub = map_fams ? ctx->t_map : ctx->lp_t_start;
     const bool any_free = !(locks & LVX_LOCK_LIDAR_TAU) || !(locks & LVX_LOCK_CAM_TAU);
     const double pad = any_free ? ctx->sensor_mto : 0.0;
-    const double tl = ctx->t_map - pad, th = ctx->t_map + pad;
+    const double tl = t_hub - pad, th = t_hub + pad;
     const double tmax = ctx->t0 + (double)(N - 3) * ctx->dt;
-    if (tl < ctx->t0 || th >= tmax) return fail(ctx, LVX_E_RANGE, "t_map outside the spline");
+    if (tl < ctx->t0 || th >= tmax) return fail(ctx, LVX_E_RANGE, map_fams ? "t_map outside the spline" : "lvx_set_lidar_poses: t_start outside the spline");
     const int i1 = (int)std::floor((tl - ctx->t0) / ctx->dt), i2 = (int)std::floor((th - ctx->t0) / ctx->dt);
     ctx->hub0 = i1;
     ctx->n_hub = std::min(N, i2 + 4 + 1) - i1;   // one spare knot for the merged-segment corner of spline_base.h:196-203
@@ -2548,6 +2595,7 @@ int ensure_layout(lvx_ctx* ctx) {
   if ((rc = upload_pairs(ctx, ctx->d_pairs[3], SURF_NC + tL, cat(range(0, 24), range(48, 54 + tL))))) return rc;
   if ((rc = upload_pairs(ctx, ctx->d_pairs[4], REP_NC + tC, cat(range(48, 54), range(55, 55 + tC))))) return rc;
   if ((rc = upload_pairs(ctx, ctx->d_pairs[5], CS_NC + tC, cat(range(0, 24), range(48, 60 + tC))))) return rc;
+  if (ctx->lp.n > 0 && (rc = upload_pairs(ctx, ctx->d_pairs_lp, LPOS_NC + tL, cat(range(0, 24), range(48, 54 + tL))))) return rc;
   ctx->force_legacy = false; ctx->fb_on = false; ctx->fb_mask = 0; ctx->fallback_rows = 0;
   { static const int zero[2] = {0, 0}; if ((rc = upload_tmp(ctx, ctx->d_zero, zero, 8))) return rc; }   // [0]: identity permutation of the single prior block, [1]: ticket of k_fold_all (returns to zero by itself)
   if ((rc = dev_alloc(ctx, ctx->d_imu_rtab, (size_t)64 * (ImuG::NTP * 4 + ImuA::NTP * 4) * 4))) return rc;
@@ -2558,7 +2606,8 @@ int ensure_layout(lvx_ctx* ctx) {
   const int nrs[LVX_NUM_FAM] = {3, 3, 1, 1, 2, 1};
   ctx->n_blocks = 0; ctx->fam_row0[0] = 0;
   for (int f = 0; f < LVX_NUM_FAM; ++f) { ctx->fam_row0[f + 1] = ctx->fam_row0[f] + cnt[f] * nrs[f]; ctx->n_blocks += cnt[f]; }
-  ctx->n_residuals = ctx->fam_row0[LVX_NUM_FAM];
+  ctx->n_residuals = ctx->fam_row0[LVX_NUM_FAM] + (int64_t)LPOS_NR * ctx->lp.n;   // the LiDAR-pose rows follow the six families'
+  ctx->n_blocks += ctx->lp.n;
   ctx->layout_dirty = false;
   return LVX_OK;
 }
@@ -2667,6 +2716,7 @@ template <bool TAU> static SurfAccT<TAU> surf_acc(const lvx_ctx* c) { const Fami
 template <bool TAU> static CamSurfFamT<TAU> camsurf_fam(const lvx_ctx* c) { const Family& f = c->cs; return {f.n, (const int*)f.d_id0.p, (const int*)f.d_id1.p, (const int*)f.d_perm.p, (const double*)c->d_planes.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, c->t_map, f.weight, f.huber}; }
 template <bool TAU> static CamSurfAccT<TAU> camsurf_acc(const lvx_ctx* c) { const Family& f = c->cs; return {f.n, (const int*)f.d_id0.p, (const int*)f.d_id1.p, (const int*)f.d_perm.p, (const double*)c->d_planes.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, c->t_map, f.weight, f.huber}; }
 template <bool TAU> static ReprojFamT<TAU> reproj_fam(const lvx_ctx* c) { const Family& f = c->rep; return {f.n, (const int*)f.d_id0.p, (const double*)f.d_a3.p, (const double*)f.d_t.p, (const int*)f.d_perm.p, (const double*)c->d_lm_uv.p, (const double*)c->d_lm_t0.p, f.weight, f.huber}; }
+template <bool TAU> static LidarPosFamT<TAU> lidarpos_fam(const lvx_ctx* c) { const Family& f = c->lp; return {f.n, (const double*)f.d_t.p, (const double*)f.d_a3.p, (const int*)f.d_perm.p, c->lp_t_start, f.weight, f.huber}; }
 // LVX_EVAL_JACOBIAN_BLOCKS: per-family record geometry and device buffers (sized for this layout and lock mask); the family offsets of both buffers
 static int setup_blocks(lvx_ctx* ctx, DevCommon& cm) {
   static const int nrs[LVX_NUM_FAM] = {GYRO_NR, ACC_NR, PRI_NR, SURF_NR, REP_NR, CS_NR};
@@ -2802,8 +2852,8 @@ static int step_clear(Pass& p) {
       if (!bc.nblk) { bc.colfull = (const uint8_t*)ctx->d_colfull.p; bc.nb = ctx->nb; bc.ld = ctx->bw + 1; bc.npre = ctx->clear_npre; bc.nblk = std::min((ctx->nb + 15) / 16, 2048); }
     } else add(cm.gb, nb1 * 8);
     // hub rows of Bd: with the fused LiDAR kernels only the fold fills them beyond the near range — it stores there, the clear skips them
-    const bool fb_lidar = fb && (ctx->fb_mask & ((1 << LVX_FAM_SURFEL) | (1 << LVX_FAM_CAMSURF)));   // listed LiDAR rows add to the hub rows directly, anywhere
-    const bool hub_partial = !fb_lidar && !ctx->sw.clear_all && !(nb1 & 1) && ctx->nb > 0 && ctx->n_hub > 0 && (fast_surf || fast_cs) && (ctx->surf.n == 0 || fast_surf) && (ctx->cs.n == 0 || fast_cs);
+    const bool fb_lidar = fb && (ctx->fb_mask & ((1 << LVX_FAM_SURFEL) | (1 << LVX_FAM_CAMSURF)));   // listed LiDAR rows add to the hub rows directly, anywhere; so do the LiDAR-pose rows (lp.n > 0)
+    const bool hub_partial = !fb_lidar && ctx->lp.n <= 0 && !ctx->sw.clear_all && !(nb1 & 1) && ctx->nb > 0 && ctx->n_hub > 0 && (fast_surf || fast_cs) && (ctx->surf.n == 0 || fast_surf) && (ctx->cs.n == 0 || fast_cs);
     cm.hub_lo = hub_partial ? ctx->hub_near_lo : 0; cm.hub_hi = hub_partial ? ctx->hub_near_hi : ctx->nb;
     if (hub_partial) { bc.Bd = cm.Bd; bc.hub_rows = 6 * ctx->n_hub; bc.hub_lo = cm.hub_lo; bc.hub_hi = cm.hub_hi; bc.hub_blk = cm.hub_hi > cm.hub_lo ? 6 * ctx->n_hub : 0; if (!bc.nb) bc.nb = ctx->nb; }
     // border rows: only the rows some residual can reach (a locked calibration scalar and an unused pseudo-pose set keep their zeros); 16-byte words: whole rows when nb is even
@@ -2892,6 +2942,17 @@ static int step_surfel(Pass& p) {
 }
 static int step_camsurf(Pass& p) {
   return p.ctx->cs.n <= 0 ? LVX_OK : with_tau(p.tauC, [&](auto T) { return step_lidar(p, LVX_FAM_CAMSURF, p.fast_cs, camsurf_acc<decltype(T)::value>(p.ctx), camsurf_fam<decltype(T)::value>(p.ctx)); });
+}
+// LiDAR odometry position blocks: the per-segment kernel over all of them, on the chain (no fused variant, no per-block records)
+static int step_lidarpos(Pass& p) {
+  lvx_ctx* ctx = p.ctx;
+  if (ctx->lp.n <= 0) return LVX_OK;
+  return with_tau(p.tauL, [&](auto T) {
+    using F = LidarPosFamT<decltype(T)::value>;
+    ProfScope ps(ctx, LVX_KERNEL_LIDAR_POS, p.st);
+    hipLaunchKernelGGL((k_family<F, LVX_PW>), Pass::grid(ctx->lp.n), dim3(64 * LVX_PW), 0, p.st, lidarpos_fam<decltype(T)::value>(ctx), p.cm, (const uint16_t*)ctx->d_pairs_lp.p, (long long)ctx->fam_row0[LVX_NUM_FAM]);
+    return (int)LVX_OK;
+  });
 }
 // the reprojection chain (Jacobian rows materialised once, three MFMA assembly passes, landmark rows stored) for a locked AND for a free camera time offset
 template <bool T> static int rep_fused(Pass& p) {
@@ -2992,7 +3053,7 @@ static int step_fold(Pass& p) {
 // DETERMINISTIC keep everything on the chain.
 static int enqueue_pass(Pass& p) {
   lvx_ctx* ctx = p.ctx; int rc;
-  if ((rc = step_clear(p)) || (rc = step_imu(p)) || (rc = step_prior(p)) || (rc = step_surfel(p)) || (rc = step_camsurf(p)) || (rc = step_reproj(p))) return rc;
+  if ((rc = step_clear(p)) || (rc = step_imu(p)) || (rc = step_prior(p)) || (rc = step_surfel(p)) || (rc = step_camsurf(p)) || (rc = step_lidarpos(p)) || (rc = step_reproj(p))) return rc;
   if (p.side_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[0], p.s_side)); LVX_HIP(ctx, hipStreamWaitEvent(p.st, ctx->ev_join[0], 0)); }
   if (p.fb_used) { LVX_HIP(ctx, hipEventRecord(ctx->ev_join[2], p.s_fb)); LVX_HIP(ctx, hipStreamWaitEvent(p.st, ctx->ev_join[2], 0)); }
   if ((rc = step_fold(p))) return rc;
@@ -3059,6 +3120,8 @@ int run_evaluate(lvx_ctx* ctx, const double* state_d, uint32_t what, double* cos
   }
   const bool xb = (what & LVX_EVAL_JACOBIAN_BLOCKS) != 0;
   if (xb && (what & LVX_EVAL_JACOBIAN)) return fail(ctx, LVX_E_ARG, "LVX_EVAL_JACOBIAN and LVX_EVAL_JACOBIAN_BLOCKS are exclusive");
+  if (ctx->lp.n > 0 && xb) return fail(ctx, LVX_E_ARG, "LVX_EVAL_JACOBIAN_BLOCKS: the LiDAR-pose blocks have no per-block record (lvx_set_lidar_poses)");
+  if (ctx->lp.n > 0 && ctx->sw.deterministic) return fail(ctx, LVX_E_ARG, "DETERMINISTIC: the LiDAR-pose blocks run on the per-segment kernel only (lvx_set_lidar_poses)");
   if (xb) {   // the previous pass's record copies read the buffers this pass writes (a pass without the bit does not touch them)
     for (int f = 0; f < LVX_NUM_FAM; ++f) if (ctx->ev_xb[f]) LVX_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_xb[f], 0));
     if ((rc = setup_blocks(ctx, cm))) return rc;

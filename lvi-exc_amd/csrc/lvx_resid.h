@@ -342,6 +342,48 @@ LVX_HD int surfel_residual(const SplineRef& sp, const PoseEval& hub, const Segs&
   return RES_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// LiDAR odometry position (measurements/lidar_position_measurement.h:23-66; attached by addLidarPoses, trajectory_manager_lvi.cpp:533-559)
+//   the position of the LiDAR at t_k in the LiDAR frame of the start time: the p_M of the surfel chain with p_L = 0, against the odometry's position
+//   r = w (q_L^* (q0^* (qk p_LI + pk - p0) - p_LI) - p_meas), 3 rows (v_L0I0_I0 = q_L (q_L^* (-p_LI)) of :55 is -p_LI; the measured orientation is never read)
+//   = Error (:73) = weight * Measure, where Measure (:29-66) already returns v_L0Lk_L0 - p_Lk_L0 (:63): the measured position is subtracted inside Measure, not in Error
+// two pose evaluations as the surfel: hub (t_start + tau_L) and k (t_k + tau_L).
+// local columns: [hub knot j: 6j..6j+5 | k knot j: 24+6j.. | lidar theta 48..50 | lidar p 51..53]; row a is the point-to-plane row of the normal e_a
+// ---------------------------------------------------------------------------------------------
+enum { LPOS_NC = 54, LPOS_NR = 3 };   // + 1 column (lidar time offset) in the TAU variant
+// TAU: the hub must have been evaluated with NEED_V; adds column LPOS_NC = d r / d tau_lidar (both poses move with the offset)
+template <bool NEED_J, bool TAU = false>
+LVX_HD int lidarpos_residual(const SplineRef& sp, const PoseEval& hub, const Segs& segs, const SensorCal& lidar, double t_k, v3 p_meas, double weight, int* i0_k,
+                             double r[LPOS_NR], double J[LPOS_NR][LPOS_NC + (TAU ? 1 : 0)]) {
+  KnotRef kr;
+  if (!seg_lookup(sp, segs, t_k + lidar.tau, &kr)) return RES_RANGE;
+  *i0_k = kr.i0;
+  PoseEval k;
+  if (!pose_eval<NEED_J, TAU>(sp, kr, &k)) return RES_NONUNIT;
+  const v3 p_I = lidar.p;
+  PlaneChain pc;
+  pc.ptemp = qrot_inv(hub.so3.q, qrot(k.so3.q, p_I) + k.p - hub.p);
+  pc.x = pc.ptemp - lidar.p;
+  const v3 pM = qrot_inv(lidar.q, pc.x);
+  r[0] = weight * (pM.x - p_meas.x); r[1] = weight * (pM.y - p_meas.y); r[2] = weight * (pM.z - p_meas.z);
+  if (NEED_J) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      pc.nL = qrot(lidar.q, mk(a == 0 ? 1.0 : 0.0, a == 1 ? 1.0 : 0.0, a == 2 ? 1.0 : 0.0));
+      pc.m = qrot_inv(k.so3.q, qrot(hub.so3.q, pc.nL));
+      const PlaneGrads g = plane_grads(hub, pc, p_I, weight);
+      pose_to_knots(hub, -g.gp, g.gx0, &J[a][0]);
+      pose_to_knots(k, g.gp, g.gxk, &J[a][24]);
+      const v3 jq = (2.0 * weight) * cross(pc.nL, pc.x);
+      const v3 jp = weight * (pc.m - pc.nL);
+      J[a][48] = jq.x; J[a][49] = jq.y; J[a][50] = jq.z;
+      J[a][51] = jp.x; J[a][52] = jp.y; J[a][53] = jp.z;
+      if (TAU) J[a][LPOS_NC] = plane_tau_jac(hub, k, g);
+    }
+  }
+  return RES_OK;
+}
+
 // Same residual with the hub pose represented by 6 PSEUDO variables (d p_0 (3), xi_0 (3)) instead of 24 hub-knot columns:
 // J_hub = g0^T M_hub with M_hub identical for every residual of a launch, so J^T J is assembled over g0 and folded back
 // with M_hub afterwards (lvx_eval.hip: k_fold_border).  local columns: [k knot j: 6j.. (24) | g0 24..29 | lidar theta 30..32 | lidar p 33..35]

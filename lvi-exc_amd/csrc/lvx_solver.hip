@@ -1317,7 +1317,7 @@ int lvx_lm_solve_shared(lvx_ctx* c, double* state, const lvx_lm_options* opt_in,
   // (a vote that rides on the first reduction); cost, directional derivatives and trial costs of the search are summed over the ranks, so every rank contracts by the
   // same factor — one more reduction per iteration to decide on the search, one per trial.
   const bool free_rho = c->L > 0 && c->rep.n + c->cs.n > 0 && !(c->locks & LVX_LOCK_LANDMARKS);
-  const bool free_tau = (!(c->locks & LVX_LOCK_LIDAR_TAU) && c->surf.n + c->cs.n > 0) || (!(c->locks & LVX_LOCK_CAM_TAU) && c->rep.n + c->cs.n > 0);
+  const bool free_tau = (!(c->locks & LVX_LOCK_LIDAR_TAU) && c->surf.n + c->cs.n + c->lp.n > 0) || (!(c->locks & LVX_LOCK_CAM_TAU) && c->rep.n + c->cs.n > 0);
   w.constrained = !lerr && (free_rho || free_tau);   // this rank's own view: its start point and its private gradient entries are projected
   double cons_votes = w.constrained ? 1.0 : 0.0;
   if (!lerr && !joint && w.lm && c->nb > 0) { w.inplace = true; w.Hs = (const double*)c->d_Hb.p; w.Bs = (const double*)c->d_Bd.p; c->p_Hs = w.Hs; }

@@ -58,6 +58,14 @@ LVX_HD int stat_surfel(const SplineRef& sp, const StatHub& hub, const SensorCal&
   int i0;
   return surfel_residual<false>(sp, h, segs, lidar, tk, p_L, Pi, weight, &i0, r, nullptr);
 }
+// LiDAR odometry position block (lvx_set_lidar_poses): the hub is the pose at the start time, with the LiDAR offset
+LVX_HD int stat_lidarpos(const SplineRef& sp, const StatHub& hub, const SensorCal& lidar, bool tau_locked, double mto, double t_start, double tk, v3 p_meas, double weight, double r[3]) {
+  Segs segs; PoseEval h;
+  const int st = stat_two_pose(sp, hub, t_start, tk, tau_locked, mto, lidar.tau, &segs, &h);
+  if (st != RES_OK) return st;
+  int i0;
+  return lidarpos_residual<false>(sp, h, segs, lidar, tk, p_meas, weight, &i0, r, nullptr);
+}
 LVX_HD int stat_reproj(const SplineRef& sp, const CamIntr& ci, const SensorCal& cam, bool tau_locked, double mto, double u_ref, double v_ref, double t0_ref,
                        double u_obs, double v_obs, double t0_obs, double rho, double weight, double r[2]) {
   int i0r, i0o;

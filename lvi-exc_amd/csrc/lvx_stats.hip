@@ -156,6 +156,72 @@ __global__ __launch_bounds__(256) void k_stats_reduce(StatsReduce q) {
   if (fam == 0 && threadIdx.x == 0) q.fam_out[LVX_NUM_FAM * ST_W] = (double)*q.err;
 }
 
+// LiDAR odometry position blocks (lvx_set_lidar_poses): one thread per block, a workgroup's 256 blocks to one record, then one workgroup adds the records in order
+struct LpStatsArgs { SplineRef sp; uint32_t locks; double mto, t_start; int n; const double* t; const double* pm; double w, huber; double* part; int nblk; double* out; int* err; };
+__global__ __launch_bounds__(256) void k_stats_lidarpos(LpStatsArgs q) {
+  __shared__ StatHub hub;
+  __shared__ double sh[4][ST_W];
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  const SplineRef sp = q.sp;
+  const double* s = sp.r3 + 7 * (size_t)sp.n;
+  SensorCal lidar; lidar.q = load_q(s + 16); lidar.p = load_v3(s + 20); lidar.tau = s[23];
+  const bool tl = (q.locks & LVX_LOCK_LIDAR_TAU) != 0;
+  if (threadIdx.x == 0) stat_hub(sp, q.t_start, tl, q.mto, lidar.tau, &hub);
+  __syncthreads();
+  double acc[ST_W];
+#pragma unroll
+  for (int k = 0; k < ST_W; ++k) acc[k] = 0.0;
+  if (i < q.n) {
+    double r[3];
+    const int status = stat_lidarpos(sp, hub, lidar, tl, q.mto, q.t_start, q.t[i], load_v3(q.pm + 3 * (size_t)i), q.w, r);
+    if (status == RES_OK) stat_block<3>(r, q.w, q.huber, acc); else atomicOr(q.err, status);   // (an integer flag word)
+  }
+  block_reduce(acc, sh, q.part + (size_t)blockIdx.x * ST_W);
+}
+__global__ __launch_bounds__(256) void k_stats_lidarpos_reduce(LpStatsArgs q) {
+  __shared__ double sh[4][ST_W];
+  double acc[ST_W];
+#pragma unroll
+  for (int s = 0; s < ST_W; ++s) acc[s] = 0.0;
+  for (int p = (int)threadIdx.x; p < q.nblk; p += 256) {   // a thread takes every 256th record, in order
+    const double* rec = q.part + (size_t)p * ST_W;
+#pragma unroll
+    for (int s = 0; s < ST_W - 1; ++s) acc[s] = s >= ST_MAX ? fmax(acc[s], rec[s]) : acc[s] + rec[s];
+  }
+  block_reduce(acc, sh, q.out);
+  if (threadIdx.x == 0) q.out[ST_W] = (double)*q.err;
+}
+static int run_lidarpos_stats(lvx_ctx* c, const double* state_d, lvx_family_stats* out) {
+  int rc = ensure_layout(c);
+  if (rc) return rc;
+  std::memset(out, 0, sizeof(*out));
+  const Family& f = c->lp;
+  out->n_blocks = f.n;
+  if (f.n <= 0) return LVX_OK;
+  hipStream_t st = c->stream;
+  LpStatsArgs a{};
+  a.sp = SplineRef{c->t0, c->dt, c->N, state_d, state_d + 3 * (size_t)c->N};
+  a.locks = c->locks; a.mto = c->sensor_mto; a.t_start = c->lp_t_start; a.n = f.n; a.t = (const double*)f.d_t.p; a.pm = (const double*)f.d_a3.p; a.w = f.weight; a.huber = f.huber;
+  a.nblk = (f.n + 255) / 256;
+  if ((rc = dev_alloc(c, c->d_lp_part, (size_t)a.nblk * ST_W * 8))) return rc;
+  if ((rc = dev_alloc(c, c->d_lp_out, (ST_W + 2) * 8))) return rc;
+  if (!c->h_lp) LVX_HIP(c, hipHostMalloc((void**)&c->h_lp, (ST_W + 2) * 8, hipHostMallocDefault));
+  a.part = (double*)c->d_lp_part.p; a.out = (double*)c->d_lp_out.p; a.err = (int*)(a.out + ST_W + 1);
+  LVX_HIP(c, hipMemsetAsync(a.err, 0, 8, st));
+  hipLaunchKernelGGL(k_stats_lidarpos, dim3((unsigned)a.nblk), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_stats_lidarpos_reduce, dim3(1), dim3(256), 0, st, a);
+  LVX_HIP(c, hipGetLastError());
+  LVX_HIP(c, hipMemcpyAsync(c->h_lp, a.out, (ST_W + 1) * 8, hipMemcpyDeviceToHost, st));
+  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
+  const double* rec = c->h_lp;
+  out->n_evaluated = (int64_t)rec[ST_EVAL]; out->n_outliers = (int64_t)rec[ST_OUT]; out->cost = rec[ST_COST];
+  for (int k = 0; k < 3; ++k) { out->sum[k] = rec[ST_SUM + k]; out->sum_abs[k] = rec[ST_ABS + k]; out->sum_sq[k] = rec[ST_SQ + k]; out->max_abs[k] = rec[ST_MAX + k]; }
+  const int err = (int)rec[ST_W];
+  if (err & RES_RANGE) return fail(c, LVX_E_RANGE, "time span out of range for trajectory");
+  if (err & RES_NONUNIT) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
+  return LVX_OK;
+}
+
 void stats_destroy(lvx_ctx* c) {
   for (DevBuf* b : {&c->d_st_state, &c->d_st_part, &c->d_st_val, &c->d_st_out, &c->d_st_plist}) if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->bytes = 0; }
   if (c->h_st) { (void)hipHostFree(c->h_st); c->h_st = nullptr; c->h_st_cap = 0; }
@@ -267,6 +333,22 @@ int lvx_error_statistics(lvx_ctx* c, const double* state, lvx_error_stats* out) 
   if ((rc = dev_alloc(c, c->d_st_state, bytes))) return rc;
   LVX_HIP(c, hipMemcpyAsync(c->d_st_state.p, state, bytes, hipMemcpyHostToDevice, c->stream));
   return run_stats(c, (const double*)c->d_st_state.p, out);
+}
+
+int lvx_lidar_pose_statistics_d(lvx_ctx* c, const double* state_d, lvx_family_stats* out) {
+  if (!c || !out) return LVX_E_ARG;
+  LVX_HIP(c, hipSetDevice(c->device));
+  if (!state_d) { int rc = ensure_layout(c); if (rc) return rc; state_d = (const double*)c->d_state.p; }
+  return run_lidarpos_stats(c, state_d, out);
+}
+int lvx_lidar_pose_statistics(lvx_ctx* c, const double* state, lvx_family_stats* out) {
+  if (!c || !state || !out) return LVX_E_ARG;
+  LVX_HIP(c, hipSetDevice(c->device));
+  int rc = ensure_layout(c); if (rc) return rc;
+  const size_t bytes = (size_t)lvx_state_size(c) * 8;
+  if ((rc = dev_alloc(c, c->d_st_state, bytes))) return rc;
+  LVX_HIP(c, hipMemcpyAsync(c->d_st_state.p, state, bytes, hipMemcpyHostToDevice, c->stream));
+  return run_lidarpos_stats(c, (const double*)c->d_st_state.p, out);
 }
 
 static int stats_ready(lvx_ctx* c) {

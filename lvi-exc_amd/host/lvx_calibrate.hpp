@@ -53,6 +53,7 @@ struct CalibrateOptions {
   double first_map_plane_lambda = 0.6, key_scan_dist = 0.2, key_scan_angle_deg = 5.0;   // plane_lambda_ of the constructor (:127); checkKeyScan (lidar_odometry.cpp:121-122)
   double associated_radius = 0.05; int selected_per_ring = 2, downsample_step = 10;
   double w_gyro = 28, w_acc = 18, w_surfel = 10, w_cam = 5, w_cam_surfel = 30;   // SetCalibWeights (lvi_initialize_surfel_orb.cpp:904-928)
+  double w_lidar_pos = 1;                // global_opt_pos_weight (calibration.hpp:68): the LiDAR odometry position blocks of RunLidarPoses
   bool opt_time_offset = false;
   bool keep_history = false, keep_clouds = false;   // AssociationRecord per DataAssociation round (tests, diagnostics)
   bool error_statistics = false;   // printErrorStatistics("Before optimization") / ("After optimization") around every stage's solve (trajectory_manager_lvi.cpp:339-342): StageReport::stats_before / stats_after
@@ -62,7 +63,8 @@ struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_su
                      std::vector<double> cost_history, radius_history; std::vector<int32_t> accepted;   // per-iteration trace of the stage's solve (lvx_lm_get_history)
                      std::vector<double> state_in;   // the state the stage's solve started from (CalibrateOptions::keep_history)
                      bool has_stats = false; lvx_error_stats stats_before{}, stats_after{};   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
-                     int init_prefix = -1; lvx_rotinit_result init{}; };   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
+                     int init_prefix = -1; lvx_rotinit_result init{};   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
+                     int n_lidar_poses = 0; lvx_family_stats lidar_pos_before{}, lidar_pos_after{}; };   // trajInitFromLidarPose: blocks attached; with error_statistics, lvx_lidar_pose_statistics around the solve
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
 struct AssociationRecord { std::vector<double> state; std::vector<lvx_surfel_plane> planes; std::vector<double> pt, pt_map, t; std::vector<int32_t> plane; std::vector<float> scans_in_map; };
@@ -251,6 +253,79 @@ class Calibrator {
     rep.push_back(SolveVisual(state));
     return rep;
   }
+  // LiDAR-IMU extrinsics from the LiDAR odometry alone, no surfel map (plane-poor scenes; a first p_LinI before DataAssociation): initialSO3TrajWithGyro, then
+  // trajInitFromLidarPose (trajectory_manager_lvi.cpp:353-388) on CalibrateInput::loam — every pose, re-expressed in the frame of the first one (PosesRelativeToFirst: a
+  // pose file need not start at the identity), whose stamp is the start time
+  std::vector<StageReport> RunLidarPoses(std::vector<double>* state) {
+    if ((int)state->size() != lvx_state_size(ctx_)) throw std::invalid_argument("state size does not match the problem");
+    if (in_.loam.all.empty()) throw std::invalid_argument("RunLidarPoses: no LiDAR odometry poses (CalibrateInput::loam)");
+    std::vector<StageReport> rep;
+    rep.push_back(Solve0(state));
+    rep.push_back(SolveLidarPose(state, PosesRelativeToFirst(in_.loam.all), (double)in_.loam.all.front().stamp_ns * 1e-9));
+    return rep;
+  }
+  // the poses in the frame of the first one: p' = R(q_0)^T (p - p_0), q' = q_0^* q with q_0 normalised; a first pose at the identity leaves every number as it is
+  static std::vector<PoseStamped> PosesRelativeToFirst(const std::vector<PoseStamped>& poses) {
+    std::vector<PoseStamped> out = poses;
+    if (poses.empty()) return out;
+    const PoseStamped& f = poses.front();
+    double w = f.q_wxyz[0], x = f.q_wxyz[1], y = f.q_wxyz[2], z = f.q_wxyz[3];
+    const double nq = std::sqrt(w * w + x * x + y * y + z * z);
+    if (!(nq > 0.0)) throw std::invalid_argument("PosesRelativeToFirst: the first pose has a zero quaternion");
+    if (f.p[0] == 0.0 && f.p[1] == 0.0 && f.p[2] == 0.0 && x == 0.0 && y == 0.0 && z == 0.0) return out;
+    w /= nq; x = -x / nq; y = -y / nq; z = -z / nq;   // conj(q_0)
+    for (PoseStamped& ps : out) {
+      const double d[3] = {ps.p[0] - f.p[0], ps.p[1] - f.p[1], ps.p[2] - f.p[2]};
+      const double ux = 2 * (y * d[2] - z * d[1]), uy = 2 * (z * d[0] - x * d[2]), uz = 2 * (x * d[1] - y * d[0]);
+      ps.p = {d[0] + w * ux + (y * uz - z * uy), d[1] + w * uy + (z * ux - x * uz), d[2] + w * uz + (x * uy - y * ux)};
+      const double bw = ps.q_wxyz[0], bx = ps.q_wxyz[1], by = ps.q_wxyz[2], bz = ps.q_wxyz[3];
+      ps.q_wxyz = {w * bw - x * bx - y * by - z * bz, w * bx + x * bw + y * bz - z * by, w * by + y * bw + z * bx - x * bz, w * bz + z * bw + x * by - y * bx};
+    }
+    return out;
+  }
+  // addLidarPoses (trajectory_manager_lvi.cpp:533-559): one position block per pose with both times inside [MinTime, MaxTime) (the two `continue`s of :544-545),
+  // weight global_opt_pos_weight, HuberLoss(5.0); returns the blocks attached.  The blocks stay set until the next call (an empty list clears them).
+  int AddLidarPoses(const std::vector<PoseStamped>& poses, double lidar_start_time) {
+    const double tmin = in_.t0, tmax = in_.t0 + (double)(in_.n_knots - 3) * in_.dt;
+    std::vector<double> t, p;
+    for (const PoseStamped& ps : poses) {
+      const double tk = (double)ps.stamp_ns * 1e-9;
+      if (tmin > tk || tmax <= tk) continue;
+      if (tmin > lidar_start_time || tmax <= lidar_start_time) continue;
+      t.push_back(tk); p.insert(p.end(), ps.p.begin(), ps.p.end());
+    }
+    check(lvx_set_lidar_poses(ctx_, (int)t.size(), t.data(), p.data(), lidar_start_time, 5.0, opt_.w_lidar_pos));
+    return (int)t.size();
+  }
+  // trajInitFromLidarPose: gyroscope + accelerometer + LiDAR position blocks, <= 50 iterations
+  StageReport SolveLidarPose(std::vector<double>* state, const std::vector<PoseStamped>& poses, double lidar_start_time) {
+    check(lvx_set_imu(ctx_, (int)in_.imu_t.size(), in_.imu_t.data(), in_.gyro.data(), in_.acc.data(), opt_.w_gyro, opt_.w_acc));
+    clear_families(true, true, true);
+    const int n = AddLidarPoses(poses, lidar_start_time);
+    const PoseBlocksGuard guard{ctx_};   // a fresh estimator per stage: the blocks leave the shared context however this stage ends
+    check(lvx_set_locks(ctx_, StageLocks(Stage::TrajFromLidarPose, opt_.opt_time_offset)));
+    StageReport r{"trajInitFromLidarPose", {}};
+    if (opt_.error_statistics) check(lvx_lidar_pose_statistics(ctx_, state->data(), &r.lidar_pos_before));
+    r.lm = solve(state, 50);
+    attach_history(&r);
+    if (opt_.error_statistics) check(lvx_lidar_pose_statistics(ctx_, state->data(), &r.lidar_pos_after));
+    r.n_lidar_poses = n;
+    return r;
+  }
+  // the four-argument trajInitFromLVIdata (:259-309): gyroscope + accelerometer + LiDAR position + reprojection blocks, everything free, <= 80 iterations
+  StageReport SolveLVIPoses(std::vector<double>* state, const std::vector<PoseStamped>& poses, double lidar_start_time) {
+    check(lvx_set_imu(ctx_, (int)in_.imu_t.size(), in_.imu_t.data(), in_.gyro.data(), in_.acc.data(), opt_.w_gyro, opt_.w_acc));
+    clear_families(true, false, true);
+    check(lvx_set_reproj(ctx_, (int)in_.obs_landmark.size(), in_.obs_landmark.data(), in_.obs_uv.data(), in_.obs_t0.data(), /*huber*/ opt_.w_cam, /*weight*/ 1.0));   // argument swap of :525
+    const int n = AddLidarPoses(poses, lidar_start_time);
+    const PoseBlocksGuard guard{ctx_};
+    check(lvx_set_locks(ctx_, StageLocks(Stage::TrajFromLVI, opt_.opt_time_offset)));
+    StageReport r{"trajInitFromLVIdata(lidar_poses)", {}};
+    r.lm = solve(state, 80);
+    attach_history(&r);
+    r.n_lidar_poses = n;
+    return r;
+  }
   // LIinitializer::RenderMap (lvi_initialize_surfel_orb.cpp:711-811) at `state`, on the de-skewed scans the last DataAssociation round left on the device (nothing is
   // downloaded but the records).  images[i]: grey, [rows][cols] of CalibrateInput::camera; the candidates are the reference's (RenderCandidates); a candidate whose time
   // lies outside the spline is passed over, the first valid one colours (with several valid ones: the lowest that sees the point).
@@ -299,6 +374,7 @@ class Calibrator {
   lvx_ctx* context() { return ctx_; }
 
  private:
+  struct PoseBlocksGuard { lvx_ctx* c; ~PoseBlocksGuard() { (void)lvx_set_lidar_poses(c, 0, nullptr, nullptr, 0.0, 5.0, 1.0); } };   // clears the LiDAR-pose blocks when a stage ends, by return or by exception
   StageReport Solve0(std::vector<double>* state) {   // initialSO3TrajWithGyro: gyro blocks + one orientation prior at MinTime, SO3 spline only
     std::vector<double> zero(in_.acc.size(), 0.0);
     check(lvx_set_imu(ctx_, (int)in_.imu_t.size(), in_.imu_t.data(), in_.gyro.data(), zero.data(), opt_.w_gyro, opt_.w_acc));

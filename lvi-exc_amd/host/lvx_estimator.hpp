@@ -27,6 +27,7 @@ struct LiDARSurfelPoint { std::array<double, 3> lidar_point; int32_t plane_id; d
 struct StaticRsCameraMeasurement { int32_t landmark_id; std::array<double, 2> uv; double view_t0; };   // static_rscamera_measurement.h:66-67
 struct CameraSurfelLandmark { int32_t landmark_id; int32_t plane_id; };      // camera_surfel_landmark.h:19-27
 struct OrientationMeasurement { double t; std::array<double, 4> q_wxyz; double weight; };   // orientation_measurement.h:23-27
+struct LidarPositionMeasurement { double t; std::array<double, 3> p; };      // lidar_position_measurement.h:23-26: p_Lk in L0 (the odometry's orientation is stored there and never read)
 
 struct Summary { lvx_lm_summary lm; std::string BriefReport() const {
   static const char* term[] = {"NO_CONVERGENCE", "CONVERGENCE (function tolerance)", "CONVERGENCE (parameter tolerance)", "CONVERGENCE (gradient tolerance)", "NO_CONVERGENCE (max iterations)", "FAILURE"};
@@ -90,6 +91,7 @@ class TrajectoryEstimator {
   void AddMeasurement(const StaticRsCameraMeasurement& m, double huber, double weight) { rep_.push_back(m); huber_rep_ = huber; w_rep_ = weight; }
   void AddMeasurement(const CameraSurfelLandmark& m, double map_time, double huber, double weight) { cs_.push_back(m); t_map_ = map_time; huber_cs_ = huber; w_cs_ = weight; }
   void AddMeasurement(const OrientationMeasurement& m) { prior_ = m; has_prior_ = true; }
+  void AddMeasurement(const LidarPositionMeasurement& m, double lidar_start_time, double huber, double weight) { lpos_.push_back(m); t_lstart_ = lidar_start_time; huber_lpos_ = huber; w_lpos_ = weight; }
 
   // TrajectoryEstimator::Solve(max_iterations, progress, num_threads) — num_threads has no meaning on the GPU
   Summary Solve(int max_iterations = 30, bool progress = true, int /*num_threads*/ = -1) {
@@ -117,6 +119,13 @@ class TrajectoryEstimator {
     check(lvx_error_statistics(ctx_, state_->data(), &st));
     return st;
   }
+  // printErrorStatistics(..., show_lidar_pos = true): the same record for the LiDAR position blocks (lvx_lidar_pose_statistics)
+  lvx_family_stats LidarPoseStatistics() {
+    upload();
+    lvx_family_stats st{};
+    check(lvx_lidar_pose_statistics(ctx_, state_->data(), &st));
+    return st;
+  }
   lvx_ctx* context() { return ctx_; }
 
  private:
@@ -137,6 +146,9 @@ class TrajectoryEstimator {
     std::vector<int32_t> clm(cs_.size()), cpl(cs_.size());
     for (size_t i = 0; i < cs_.size(); ++i) { clm[i] = cs_[i].landmark_id; cpl[i] = cs_[i].plane_id; }
     check(lvx_set_camsurf(ctx_, (int)clm.size(), clm.data(), cpl.data(), t_map_, huber_cs_, w_cs_));
+    std::vector<double> lt(lpos_.size()), lp(3 * lpos_.size());
+    for (size_t i = 0; i < lpos_.size(); ++i) { lt[i] = lpos_[i].t; for (int k = 0; k < 3; ++k) lp[3 * i + k] = lpos_[i].p[k]; }
+    check(lvx_set_lidar_poses(ctx_, (int)lt.size(), lt.data(), lp.data(), t_lstart_, huber_lpos_, w_lpos_));
     check(lvx_set_locks(ctx_, locks_ | (acc_.empty() && !gyro_.empty() ? LVX_LOCK_R3 : 0u)));   // gyro-only estimator == SO3-only Solve #0
   }
   void check(int rc) {
@@ -149,7 +161,8 @@ class TrajectoryEstimator {
   std::vector<double>* state_;
   uint32_t locks_ = LVX_LOCK_LIDAR_TAU | LVX_LOCK_CAM_TAU;
   std::vector<GyroscopeMeasurement> gyro_; std::vector<AccelerometerMeasurement> acc_; std::vector<LiDARSurfelPoint> surf_;
-  std::vector<StaticRsCameraMeasurement> rep_; std::vector<CameraSurfelLandmark> cs_;
+  std::vector<StaticRsCameraMeasurement> rep_; std::vector<CameraSurfelLandmark> cs_; std::vector<LidarPositionMeasurement> lpos_;
+  double t_lstart_ = 0, huber_lpos_ = 5, w_lpos_ = 1;
   OrientationMeasurement prior_{}; bool has_prior_ = false;
   double w_gyro_ = 1, w_acc_ = 1, w_surf_ = 1, w_rep_ = 1, w_cs_ = 1, huber_surf_ = 5, huber_rep_ = 5, huber_cs_ = 5, t_map_ = 0;
 };

@@ -163,7 +163,7 @@ inline bool PoseOfScan(const LoamPoses& loam, bool simulation, int idx, double s
 
 // Lock masks of the reference's solve stages (TrajectoryManagerLVI, src/lvi_exc/src/core/trajectory_manager_lvi.cpp): which Lock* calls each
 // stage makes before building its estimator.  opt_time_offset = calib_param_manager->opt_time_offset (lvi.yaml:32).
-enum class Stage { SO3FromGyro, TrajFromSurfel, TrajFromLVI, TrajFromLVILandmarksOnly, TrajFromVisualFrames };
+enum class Stage { SO3FromGyro, TrajFromSurfel, TrajFromLVI, TrajFromLVILandmarksOnly, TrajFromVisualFrames, TrajFromLidarPose };
 inline uint32_t StageLocks(Stage s, bool opt_time_offset) {
   const uint32_t tau = opt_time_offset ? 0u : (LVX_LOCK_LIDAR_TAU | LVX_LOCK_CAM_TAU);
   switch (s) {
@@ -177,6 +177,8 @@ inline uint32_t StageLocks(Stage s, bool opt_time_offset) {
       return tau | LVX_LOCK_TRAJ | LVX_LOCK_LIDAR_Q | LVX_LOCK_LIDAR_P;
     case Stage::TrajFromVisualFrames:     // trajInitFromVisualFrames (:99-136; LIinitializer::CIoptimize): IMU + reprojection blocks only, LiDAR extrinsics locked, its offset untouched (locked)
       return LVX_LOCK_LIDAR_Q | LVX_LOCK_LIDAR_P | LVX_LOCK_LIDAR_TAU | (opt_time_offset ? 0u : LVX_LOCK_CAM_TAU);
+    case Stage::TrajFromLidarPose:        // trajInitFromLidarPose (:353-388): IMU + LiDAR odometry position blocks; lidar and biases free, nothing reads the camera or a landmark
+      return LVX_LOCK_CAM_Q | LVX_LOCK_CAM_P | LVX_LOCK_CAM_TAU | LVX_LOCK_LANDMARKS | (opt_time_offset ? 0u : LVX_LOCK_LIDAR_TAU);
   }
   return tau;
 }

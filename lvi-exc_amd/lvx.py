@@ -29,6 +29,9 @@ EVAL_COST, EVAL_RESIDUALS, EVAL_NORMAL_EQ, EVAL_JACOBIAN, EVAL_JACOBIAN_BLOCKS =
 (FAM_GYRO, FAM_ACCEL, FAM_PRIOR, FAM_SURFEL, FAM_REPROJ, FAM_CAMSURF, KERNEL_FOLD, KERNEL_SOLVE, KERNEL_UPSTREAM, KERNEL_CLEAR, KERNEL_REP_JAC, KERNEL_REP_OBS,
  KERNEL_REP_REF, KERNEL_REP_CROSS, KERNEL_REP_LMROWS, KERNEL_REP_FUSED, KERNEL_FIXUP) = range(17)
 KERNEL_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf", "fold", "solve", "upstream", "clear", "reproj_jac", "reproj_obs", "reproj_ref", "reproj_cross", "reproj_lmrows", "reproj_fused", "fixup"]
+FAM_LIDAR_POS = 6       # LiDAR odometry position blocks (set_lidar_poses): not one of the six families of FAMILY_NAMES / family_rows()
+KERNEL_LIDAR_POS = 17   # beyond KERNEL_NAMES: kernel_ms_ext() returns it
+KERNEL_NAMES_EXT = KERNEL_NAMES + ["lidar_pos"]
 JAC_WIDTH = 64
 
 
@@ -186,6 +189,35 @@ class Context:
     def set_camsurf(self, lm, plane_id, t_map, huber, w):
         lm, plane_id = _i(lm), _i(plane_id)
         self._ck(self._l.lvx_set_camsurf(self._h, C.c_int(len(lm)), _p(lm), _p(plane_id), C.c_double(t_map), C.c_double(huber), C.c_double(w)))
+
+    def set_lidar_poses(self, t, p_meas, t_start, huber=5.0, w=1.0):
+        """LiDAR odometry positions p_meas[i] (the LiDAR at t[i] in its frame at t_start) as 3-row blocks behind the camera-surfel rows; empty arrays clear the family."""
+        t, p_meas = _d(t).reshape(-1), _d(p_meas).reshape(-1, 3)
+        assert len(t) == len(p_meas)
+        self._ck(self._l.lvx_set_lidar_poses(self._h, C.c_int(len(t)), _p(t), _p(p_meas), C.c_double(t_start), C.c_double(huber), C.c_double(w)))
+
+    def lidar_pose_rows(self):
+        """(first residual row of the LiDAR-pose blocks, total residual rows), as lvx_get_lidar_pose_rows."""
+        r0, n = C.c_int64(0), C.c_int64(0)
+        self._ck(self._l.lvx_get_lidar_pose_rows(self._h, C.byref(r0), C.byref(n)))
+        return int(r0.value), int(n.value)
+
+    def lidar_pose_statistics(self, state=None, raw=False):
+        """The error-statistics record of the LiDAR-pose blocks at `state` (None: the resident state): the dict error_statistics() gives per family.
+        raw=True returns (code, dict) instead of raising."""
+        fs = FamilyStats()
+        if state is None:
+            rc = self._l.lvx_lidar_pose_statistics_d(self._h, None, C.byref(fs))
+        else:
+            state = _d(state)
+            assert state.size == self.state_size
+            rc = self._l.lvx_lidar_pose_statistics(self._h, _p(state), C.byref(fs))
+        out = dict(n_blocks=int(fs.n_blocks), n_evaluated=int(fs.n_evaluated), n_outliers=int(fs.n_outliers), cost=fs.cost,
+                   sum=np.array(fs.sum), sum_abs=np.array(fs.sum_abs), sum_sq=np.array(fs.sum_sq), max_abs=np.array(fs.max_abs))
+        if raw:
+            return rc, out
+        self._ck(rc)
+        return out
 
     def set_locks(self, mask):
         self._ck(self._l.lvx_set_locks(self._h, C.c_uint32(mask)))
@@ -345,6 +377,13 @@ class Context:
         ms = np.zeros(len(KERNEL_NAMES))
         n = np.zeros(len(KERNEL_NAMES), dtype=np.int64)
         self._ck(self._l.lvx_get_kernel_ms(self._h, _p(ms), _p(n)))
+        return ms, n
+
+    def kernel_ms_ext(self):
+        """kernel_ms() with the ids beyond KERNEL_NAMES (KERNEL_NAMES_EXT: the LiDAR-pose kernel)."""
+        ms = np.zeros(len(KERNEL_NAMES_EXT))
+        n = np.zeros(len(KERNEL_NAMES_EXT), dtype=np.int64)
+        self._ck(self._l.lvx_get_kernel_ms_ext(self._h, C.c_int(len(KERNEL_NAMES_EXT)), _p(ms), _p(n)))
         return ms, n
 
     def solve_step(self, radius, jacobi_scaling=True):

@@ -3,6 +3,7 @@
 Lock masks: which Lock* calls TrajectoryManagerLVI makes before building each stage's estimator (src/lvi_exc/src/core/trajectory_manager_lvi.cpp):
   initialSO3TrajWithGyro (:43-62)    SO3 spline + one orientation prior; R3 absent, biases locked                                      <= 30 iterations
   trajInitFromSurfel (:311-351)      gyro + accel + surfel blocks; camera and landmarks constant                                        <= 30
+  trajInitFromLidarPose (:353-388)   gyro + accel + LiDAR odometry position blocks (Context.set_lidar_poses); camera and landmarks constant  <= 50
   trajInitFromLVIdata (:138-195)     + reprojection blocks, everything free (lvi.yaml: lock_traj_lidar_in_2nd_stage false)              <= 80
   trajInitFromLVIdata + lm_splane (:197-257)  + camera-landmark-to-surfel blocks; trajectory and LiDAR locked (lock_traj_lidar_in_3rd_stage) <= 80
 Time offsets stay locked unless opt_time_offset (lvi.yaml:32).  A fresh problem is built for every stage, as the reference does
@@ -21,6 +22,8 @@ def stage_locks(stage, opt_time_offset=False):
     if stage == "SO3FromGyro":
         return lvx.LOCK_R3 | lvx.LOCK_ACC_BIAS | lvx.LOCK_GYRO_BIAS | lvx.LOCK_LIDAR_TAU | lvx.LOCK_CAM_TAU
     if stage == "TrajFromSurfel":
+        return lvx.LOCK_CAM_Q | lvx.LOCK_CAM_P | lvx.LOCK_CAM_TAU | lvx.LOCK_LANDMARKS | (0 if opt_time_offset else lvx.LOCK_LIDAR_TAU)
+    if stage == "TrajFromLidarPose":   # LiDAR extrinsics and both biases free; no block reads the camera or a landmark
         return lvx.LOCK_CAM_Q | lvx.LOCK_CAM_P | lvx.LOCK_CAM_TAU | lvx.LOCK_LANDMARKS | (0 if opt_time_offset else lvx.LOCK_LIDAR_TAU)
     if stage == "TrajFromLVI":
         return tau
