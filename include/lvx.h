@@ -468,7 +468,13 @@ int lvx_ndt_fitness(lvx_ctx* ctx, int n_src, const float* src_xyzi4, const float
 /* SurfelAssociation::setSurfelMap + checkPlaneType (src/lvi_exc/src/core/surfel_association.cpp:50-86, 246-266) over the leaves of the last
  * lvx_voxel_build of this context (the cloud passed to it must still be alive): leaves with >= min_leaf_points points and planarity >= p_lambda,
  * plane fit, Pi = -d n, AABB of the leaf's points; output in voxel-key (std::map) order.  The reference fits with pcl RANSAC (random); this is
- * the deterministic variant documented in DESIGN.md: leaf PCA plane -> inliers within dist_threshold -> PCA refit -> reselect. */
+ * the deterministic variant documented in DESIGN.md: leaf PCA plane -> inliers strictly within dist_threshold -> PCA refit (three inliers or more) -> reselect;
+ * p4 is signed so that d <= 0 (at d == 0: the first non-zero component of the normal positive).
+ * *n_planes is the number of planes whatever max_planes is; the first min(*n_planes, max_planes) are written and nothing behind them (max_planes = 0: planes may be NULL).
+ * Without a voxel build on this context, and after a build that found no leaf (an empty cloud), the map is empty: *n_planes = 0 and LVX_OK.
+ * min_leaf_points below the min_points_per_voxel of the build: a leaf with fewer points than min_points_per_voxel has no eigen data (the reference never gets there,
+ * its 10 is hard-coded above ndt_omp's 6); it has no planarity and is never a surfel, whatever p_lambda is.  min_leaf_points <= 0 means 1: a leaf the build rejected
+ * (nr_points = -1) is never fitted.  Both hold for lvx_assoc_options::min_leaf_points as well. */
 typedef struct lvx_surfel_plane { double p4[4]; double Pi[3]; double box_min[3]; double box_max[3]; int32_t leaf, n_points, n_inliers, plane_type; } lvx_surfel_plane;
 int lvx_surfel_extract(lvx_ctx* ctx, double p_lambda, double dist_threshold, int min_leaf_points, int min_inliers, int max_planes, lvx_surfel_plane* planes, int32_t* n_planes);
 
@@ -503,7 +509,7 @@ typedef struct lvx_assoc_options {
   double min_covar_eigvalue_mult;    /* :208, 0.01 */
   double plane_lambda;               /* 0.7 (lvi_initialize_surfel_orb.cpp:1183) */
   double fit_threshold;              /* RANSAC distance threshold 0.05 (surfel_association.cpp:279) */
-  int32_t min_leaf_points, min_inliers;   /* 10 (:61), 20 (:283) */
+  int32_t min_leaf_points, min_inliers;   /* 10 (:61), 20 (:283); min_leaf_points <= 0 means 1, leaves below min_points_per_voxel are never surfels (lvx_surfel_extract) */
   double radius;                     /* associated_radius_ 0.05 */
   int32_t selected_per_ring, reserved;    /* getAssociation(..., 2) */
 } lvx_assoc_options;

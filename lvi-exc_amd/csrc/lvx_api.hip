@@ -19,6 +19,7 @@ const SwitchName* switch_table(int* count) {
     {"CHUNK_R", &Switches::chunk_r, true}, {"CHUNK_R_IMU", &Switches::chunk_r_imu, true}, {"CHUNK_R_REP", &Switches::chunk_r_rep, true}, {"CHUNK_ROWS", &Switches::chunk_rows, true}, {"REP_ROWS", &Switches::rep_rows, true}, {"REP_FUSED", &Switches::rep_fused, true}, {"SOLVER_ND", &Switches::solver_nd, false},
     {"DA_SYNC", &Switches::da_sync, false},   // lvx_data_association: always the synchronous chain (four host stops), never the speculative one
     {"TEST_BAD_PIVOT", &Switches::test_bad_pivot, false},   // lvx_solve_step: declare a pivot failure where there was none (the tests' way into the sequential redo)
+    {"TEST_COMPACT_ONE", &Switches::test_compact_one, false},   // surfel_compact_launch: k_surfel_compact (one workgroup) whatever the co-residency bound says
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;

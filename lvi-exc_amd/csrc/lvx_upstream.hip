@@ -1194,13 +1194,13 @@ __global__ __launch_bounds__(256) void k_surfel_extract(const float4* __restrict
   if (li >= nl) return;
   if (lane == 0) flag[li] = 0;
   const int n = leaf_n[li];
-  if (n < min_leaf) return;
+  if (n < max(min_leaf, 1)) return;   // (min_leaf_points <= 0 is 1: a leaf k_vx_leaf rejected carries n = -1 and is never fitted)
   const double* ev = evals + 3 * (size_t)li;
   int i0 = 0, i1 = 1, i2 = 2;   // descending by value (Eigen::sort_vec)
   if (ev[i1] > ev[i0]) { const int t = i0; i0 = i1; i1 = t; }
   if (ev[i2] > ev[i1]) { const int t = i1; i1 = i2; i2 = t; if (ev[i1] > ev[i0]) { const int u = i0; i0 = i1; i1 = u; } }
   const double pl = 2.0 * (ev[i1] - ev[i2]) / (ev[i2] + ev[i1] + ev[i0]);
-  if (pl < p_lambda) return;
+  if (!(pl >= p_lambda)) return;   // (a leaf below min_points_per_voxel has no eigen data: 0 / 0, never a surfel)
   const double* V = evecs + 9 * (size_t)li;
   double nrm[3] = {V[0 + i2], V[3 + i2], V[6 + i2]};
   const double an[3] = {fabs(nrm[0]), fabs(nrm[1]), fabs(nrm[2])};
@@ -1211,6 +1211,9 @@ __global__ __launch_bounds__(256) void k_surfel_extract(const float4* __restrict
   double d = -(nrm[0] * mean[3 * (size_t)li] + nrm[1] * mean[3 * (size_t)li + 1] + nrm[2] * mean[3 * (size_t)li + 2]);
   int nin = 0;
   float bmin[3] = {3.402823466e38f, 3.402823466e38f, 3.402823466e38f}, bmax[3] = {-3.402823466e38f, -3.402823466e38f, -3.402823466e38f};
+  // The refit's sums run over x - (leaf mean): cc / n - mu mu^T of raw coordinates cancels as |x|^2 / spread^2 (six digits 100 m from the origin, 1e-8 m in the
+  // plane's d); about the leaf mean nothing cancels.
+  const double lm[3] = {mean[3 * (size_t)li], mean[3 * (size_t)li + 1], mean[3 * (size_t)li + 2]};
   for (int pass = 0; pass < 2; ++pass) {
     double sm[3] = {0, 0, 0}, cc[6] = {0, 0, 0, 0, 0, 0};
     int my = 0;
@@ -1239,8 +1242,9 @@ __global__ __launch_bounds__(256) void k_surfel_extract(const float4* __restrict
         if (!(fabs(nrm[0] * x[0] + nrm[1] * x[1] + nrm[2] * x[2] + d) < thr)) continue;
         ++my;
         if (pass == 0) {
-          sm[0] += x[0]; sm[1] += x[1]; sm[2] += x[2];
-          cc[0] += x[0] * x[0]; cc[1] += x[0] * x[1]; cc[2] += x[0] * x[2]; cc[3] += x[1] * x[1]; cc[4] += x[1] * x[2]; cc[5] += x[2] * x[2];
+          const double y[3] = {x[0] - lm[0], x[1] - lm[1], x[2] - lm[2]};
+          sm[0] += y[0]; sm[1] += y[1]; sm[2] += y[2];
+          cc[0] += y[0] * y[0]; cc[1] += y[0] * y[1]; cc[2] += y[0] * y[2]; cc[3] += y[1] * y[1]; cc[4] += y[1] * y[2]; cc[5] += y[2] * y[2];
         }
       }
     }
@@ -1249,10 +1253,11 @@ __global__ __launch_bounds__(256) void k_surfel_extract(const float4* __restrict
     if (pass == 1 || nin < 3) break;
     for (int a = 0; a < 3; ++a) sm[a] = wave_sum(sm[a]);
     for (int a = 0; a < 6; ++a) cc[a] = wave_sum(cc[a]);
-    const double mu[3] = {sm[0] / nin, sm[1] / nin, sm[2] / nin};
+    const double ms[3] = {sm[0] / nin, sm[1] / nin, sm[2] / nin};          // inlier mean - leaf mean
+    const double mu[3] = {lm[0] + ms[0], lm[1] + ms[1], lm[2] + ms[2]};
     const double cs[9] = {cc[0], cc[1], cc[2], cc[1], cc[3], cc[4], cc[2], cc[4], cc[5]};
     double C[9];
-    for (int a = 0; a < 3; ++a) for (int bb = 0; bb < 3; ++bb) C[3 * a + bb] = cs[3 * a + bb] / nin - mu[a] * mu[bb];
+    for (int a = 0; a < 3; ++a) for (int bb = 0; bb < 3; ++bb) C[3 * a + bb] = cs[3 * a + bb] / nin - ms[a] * ms[bb];
     // The refit needs ONE eigenvector of C, the smallest one's, and the leaf's own normal is within a few degrees of it: Rayleigh-quotient iteration from there
     // (y = adj(C - lambda I) n by cross products of the rows: no division, cubic convergence — three rounds reach the last bit), checked to be the SMALLEST eigenvalue
     // through the characteristic polynomial's other two roots; anything else (a leaf whose inliers turn the plane over) takes the full Jacobi solve as before.
@@ -2526,7 +2531,7 @@ int lvx_undistort_scan(lvx_ctx* c, const double* state, int n, const lvx_point_x
 static int surfel_compact_launch(lvx_ctx* c, const SurfelPlaneDev* all, const int* flag, int nl, SurfelPlaneDev* recs, int* d_cnt, const VxInfo* info) {
   const int nb = (nl + 1023) / 1024;
   if (c->coresident_compact < 0) c->coresident_compact = coresident_bound(c, (const void*)k_surfel_compact_mb, 256, SC_MAXB);
-  if (nb > c->coresident_compact) {   // (every workgroup of the multi-block kernel must be resident on THIS device)
+  if (nb > c->coresident_compact || c->sw.test_compact_one) {   // (every workgroup of the multi-block kernel must be resident on THIS device; switch TEST_COMPACT_ONE: the tests' way here on a full part)
     hipLaunchKernelGGL(k_surfel_compact, dim3(1), dim3(1024), 0, c->stream, all, flag, nl, recs, d_cnt, info);
     return LVX_OK;
   }
@@ -2541,8 +2546,7 @@ static int surfel_extract_device(lvx_ctx* c, double p_lambda, double dist_thresh
   { const int rc0 = vox_info(c); if (rc0) return rc0; }
   const lvx_ctx::Voxels& V = c->vox;
   const int nl = V.n_leaves, n = V.n_points; const size_t cap = (size_t)V.cap;
-  if (nl == 0) return LVX_OK;
-  if (!V.d_pts) return fail(c, LVX_E_STATE, "lvx_voxel_build has not been called");
+  if (nl == 0) return LVX_OK;   // no voxel build yet, or one that found no leaf: an empty map (include/lvx.h)
   int rc;
   if ((rc = dev_alloc(c, c->d_up[4], (size_t)nl * sizeof(SurfelPlaneDev)))) return rc;
   if ((rc = dev_alloc(c, c->d_up[5], (size_t)nl * 4))) return rc;

@@ -269,13 +269,13 @@ int orc_surfel_extract(int n_leaves, const float* xyzi, const int32_t* leaf_n, c
   int np = 0;
   for (int li = 0; li < n_leaves; ++li) {
     const int n = leaf_n[li];
-    if (n < min_leaf_points) continue;
+    if (n < std::max(min_leaf_points, 1)) continue;   // min_leaf_points <= 0 is 1: rejected leaves (n = -1) are never fitted
     const double* ev = evals + 3 * li;
     // Eigen::sort_vec: indices sorted by DESCENDING value (std::sort on 3 elements)
     int ind[3] = {0, 1, 2};
     std::sort(ind, ind + 3, [&](int a, int b) { return ev[a] > ev[b]; });
     const double p = 2.0 * (ev[ind[1]] - ev[ind[2]]) / (ev[ind[2]] + ev[ind[1]] + ev[ind[0]]);
-    if (p < p_lambda) continue;
+    if (!(p >= p_lambda)) continue;   // a leaf below min_points_per_voxel has zero eigenvalues: 0 / 0 is no planarity, never a surfel
     const double* V = evecs + 9 * li;   // row-major, eigenvector k = column k
     double nrm[3] = {V[0 + ind[2]], V[3 + ind[2]], V[6 + ind[2]]};
     double an[3] = {std::fabs(nrm[0]), std::fabs(nrm[1]), std::fabs(nrm[2])};
@@ -293,11 +293,13 @@ int orc_surfel_extract(int n_leaves, const float* xyzi, const int32_t* leaf_n, c
         const double x[3] = {q[0], q[1], q[2]};
         if (!(std::fabs(nrm[0] * x[0] + nrm[1] * x[1] + nrm[2] * x[2] + d) < dist_threshold)) continue;
         ++nin;
-        for (int a = 0; a < 3; ++a) { sm[a] += x[a]; for (int b = 0; b < 3; ++b) cc[3 * a + b] += x[a] * x[b]; }
+        const double y[3] = {x[0] - mean[3 * li], x[1] - mean[3 * li + 1], x[2] - mean[3 * li + 2]};   // sums about the leaf mean: cc / n - mu mu^T of raw coordinates cancels as |x|^2 / spread^2
+        for (int a = 0; a < 3; ++a) { sm[a] += y[a]; for (int b = 0; b < 3; ++b) cc[3 * a + b] += y[a] * y[b]; }
       }
       if (pass == 1 || nin < 3) break;
-      double mu[3] = {sm[0] / nin, sm[1] / nin, sm[2] / nin}, C[9];
-      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) C[3 * a + b] = cc[3 * a + b] / nin - mu[a] * mu[b];
+      const double ms[3] = {sm[0] / nin, sm[1] / nin, sm[2] / nin};
+      double mu[3] = {mean[3 * li] + ms[0], mean[3 * li + 1] + ms[1], mean[3 * li + 2] + ms[2]}, C[9];
+      for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) C[3 * a + b] = cc[3 * a + b] / nin - ms[a] * ms[b];
       double e2[3], V2[9];
       eig3(C, e2, V2);                                 // ascending: column 0 = normal
       nrm[0] = V2[0]; nrm[1] = V2[3]; nrm[2] = V2[6];
