@@ -2816,13 +2816,20 @@ int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* sc
       if (key_scan) key_scan[s] = 1;
     }
   }
-  if (key.empty()) return LVX_OK;   // no scan with a pose inside the spline: an empty map
+  // the scans in the map frame are written before any return: absent scans are NaN there, so with no scan present the buffer is all NaN and nothing of an earlier round
+  // stays readable through lvx_get_scans_in_map / lvx_render_map_d
   LVX_HIP(c, hipMemcpyAsync(d_present, present.data(), (size_t)S * 4, hipMemcpyHostToDevice, st));
-  LVX_HIP(c, hipMemcpyAsync(d_key, key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
   if ((rc = dev_alloc(c, c->d_da[4], npt * 16))) return rc;
   if ((rc = dev_alloc(c, c->d_da[6], npt * 4))) return rc;
   hipLaunchKernelGGL(k_deskew_pose, dim3((unsigned)((npt + 255) / 256)), dim3(256), 0, st, (const double*)c->d_da[1].p, c->N, c->t0, c->dt, HW, (int)npt, (const PointXYZIT*)c->d_da[0].p,
                      (const double*)d_q, (const int*)d_present, (const double*)d_pose, (float4*)c->d_da[4].p, (int*)c->d_da[6].p);
+  if (key.empty()) {   // no scan with a pose inside the spline: an empty map
+    LVX_HIP(c, hipGetLastError());
+    LVX_HIP(c, hipStreamSynchronize(st));   // (the host vector above goes out of scope)
+    lvx_surfel_map_release(c);
+    return LVX_OK;
+  }
+  LVX_HIP(c, hipMemcpyAsync(d_key, key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
   const size_t nmap = key.size() * (size_t)HW;
   if ((rc = dev_alloc(c, c->d_da_key, nmap * 16))) return rc;
   hipLaunchKernelGGL(k_gather_scans, dim3((unsigned)((nmap + 255) / 256)), dim3(256), 0, st, (const float4*)c->d_da[4].p, (const int*)d_key, HW, (int)nmap, (float4*)c->d_da_key.p);
@@ -2867,7 +2874,7 @@ int lvx_get_surfel_points(lvx_ctx* c, int max_points, double* pt3, double* pt_ma
 int lvx_get_scans_in_map(lvx_ctx* c, float* xyzi4) {
   if (!c || !xyzi4) return LVX_E_ARG;
   const size_t npt = (size_t)c->da_S * c->da_H * c->da_W;
-  if (npt == 0 || !c->d_da[4].p) return fail(c, LVX_E_STATE, "lvx_data_association has not been called");
+  if (npt == 0 || !c->d_da[4].p || c->d_da[4].bytes < npt * 16) return fail(c, LVX_E_STATE, "lvx_data_association has not been called");   // (as lvx_render_map_d: scans set after the last round)
   LVX_HIP(c, hipSetDevice(c->device));
   LVX_HIP(c, hipMemcpyAsync(xyzi4, c->d_da[4].p, npt * 16, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
