@@ -369,7 +369,9 @@ int lvx_voxel_get_info(lvx_ctx* ctx, lvx_voxel_info* info);
  * as offsets[n_leaves + 1] into point_ids (input indices, input order inside a leaf); any pointer may be NULL */
 int lvx_voxel_get(lvx_ctx* ctx, int32_t* leaf_key, int32_t* leaf_n, double* mean3, double* cov9, double* icov9, double* evecs9, double* evals3, float* centroid3,
                   int32_t* offsets, int32_t* point_ids);
-/* getNeighborhoodAtPoint7 (:423-438): leaf index per displacement {0,+x,-x,+y,-y,+z,-z} or -1 */
+/* getNeighborhoodAtPoint7 (:423-438): leaf index per displacement {0,+x,-x,+y,-y,+z,-z} or -1.
+ * A query with a non-finite coordinate (NaN, +-inf) has no neighbour: every id is -1, in lvx_voxel_lookup1 / 7 (_d) and in lvx_voxel_lookup_rel alike (the reference
+ * casts floor(NaN) to int, which is undefined).  A leaf that the build rejected (nr_points -1) is never returned. */
 int lvx_voxel_lookup7(lvx_ctx* ctx, int nq, const float* xyzi4, int32_t* leaf_ids7);
 int lvx_voxel_lookup7_d(lvx_ctx* ctx, int nq, const float* xyzi4_d, int32_t* leaf_ids7_d);
 /* getNeighborhoodAtPoint1 (:440-446): the leaf of the query's own cell or -1 */
@@ -438,7 +440,8 @@ int64_t lvx_collective_count(lvx_ctx* ctx, int reset);
 /* pclomp::NormalDistributionsTransform::computeDerivatives with DIRECT7 search (src/ndt_omp/include/pclomp/ndt_omp_impl.hpp:180-285, 289-430, 484-536)
  * against the voxel grid of the last lvx_voxel_build of this context (resolution = its leaf size): score, 6-gradient and 6 x 6 Hessian (row-major)
  * of the NDT objective at the transform vector p6 = (tx, ty, tz, rx, ry, rz); input = source cloud, trans = the same cloud already transformed by p6
- * (pcl::transformPointCloud, as the caller does before every call).  Per-point arithmetic in float like the reference, accumulation in double. */
+ * (pcl::transformPointCloud, as the caller does before every call).  Per-point arithmetic in float like the reference, accumulation in double.
+ * The NDT calls (lvx_ndt_derivatives, lvx_ndt_align, lvx_ndt_fitness) require a finite source cloud: their kernels do not carry the lookups' non-finite guard. */
 int lvx_ndt_derivatives(lvx_ctx* ctx, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian,
                         double* score, double* gradient6, double* hessian36);
 

@@ -1171,7 +1171,7 @@ __global__ __launch_bounds__(256) void k_vx_lookup_rel(const float4* q, int nq, 
   const float4 p = q[i];
   const int ijk[3] = {(int)floorf(p.x / leaf), (int)floorf(p.y / leaf), (int)floorf(p.z / leaf)};   // :383-385
   const int d[3] = {rel3[3 * r], rel3[3 * r + 1], rel3[3 * r + 2]};
-  bool ok = true;
+  bool ok = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);   // a non-finite query has no neighbour (include/lvx.h): (int)floorf(NaN) is cell 0 here and INT_MIN on the host
 #pragma unroll
   for (int a = 0; a < 3; ++a) ok = ok & (g.min_b[a] - ijk[a] <= d[a]) & (g.max_b[a] - ijk[a] >= d[a]);   // :386-387, 396
   int id = -1;
@@ -1403,10 +1403,11 @@ __global__ void k_vx_lookup(const float4* q, int nq, float leaf, int min_pts, Vx
   const int disp[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
   // all K cell probes in flight, then all K leaf counts: two memory round trips per query.  (Probe by probe — load the cell, wait, load its leaf's count, wait, store —
   // the compiler kept the 2 K loads of a query strictly one behind the other.)
+  const bool fin = isfinite(p.x) && isfinite(p.y) && isfinite(p.z);   // a non-finite query has no neighbour (include/lvx.h): (int)floorf(NaN) is cell 0 here and INT_MIN on the host
   bool in[K]; int li[K], cn[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
-    bool ok = true;
+    bool ok = fin;
 #pragma unroll
     for (int a = 0; a < 3; ++a) ok = ok & (g.min_b[a] - ijk[a] <= disp[k][a]) & (g.max_b[a] - ijk[a] >= disp[k][a]);
     in[k] = ok;

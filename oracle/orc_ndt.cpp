@@ -31,11 +31,12 @@ void orc_voxel_lookup_rel(int nq, const float* xyzi, float leaf, int min_pts, co
   for (int i = 0; i < n_leaves; ++i) key2leaf[leaf_key[i]] = i;
   for (int q = 0; q < nq; ++q) {
     const float* p = xyzi + 4 * q;
-    const int ijk[3] = {static_cast<int>(std::floor(p[0] / leaf)), static_cast<int>(std::floor(p[1] / leaf)), static_cast<int>(std::floor(p[2] / leaf))};   // :383-385
+    const bool fin = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);   // a non-finite query has no neighbour (include/lvx.h); its cell is undefined
+    const int ijk[3] = {fin ? static_cast<int>(std::floor(p[0] / leaf)) : 0, fin ? static_cast<int>(std::floor(p[1] / leaf)) : 0, fin ? static_cast<int>(std::floor(p[2] / leaf)) : 0};   // :383-385
     for (int r = 0; r < n_rel; ++r) {
       const int32_t* d = rel3 + 3 * r;
       int id = -1;
-      bool in = true;
+      bool in = fin;
       for (int a = 0; a < 3; ++a) in = in && (grid[a] - ijk[a] <= d[a]) && (grid[3 + a] - ijk[a] >= d[a]);                                                  // :386-387, 396
       if (in) {
         const int key = (ijk[0] + d[0] - grid[0]) * grid[9] + (ijk[1] + d[1] - grid[1]) * grid[10] + (ijk[2] + d[2] - grid[2]) * grid[11];                  // :398

@@ -215,10 +215,11 @@ void orc_voxel_lookup7(int nq, const float* xyzi, float leaf, int min_pts, const
   static const int disp[7][3] = {{0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 1, 0}, {0, -1, 0}, {0, 0, 1}, {0, 0, -1}};
   for (int q = 0; q < nq; ++q) {
     const float* p = xyzi + 4 * q;
-    const int ijk[3] = {static_cast<int>(std::floor(p[0] / leaf)), static_cast<int>(std::floor(p[1] / leaf)), static_cast<int>(std::floor(p[2] / leaf))};
+    const bool fin = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);   // a non-finite query has no neighbour (include/lvx.h); its cell is undefined
+    const int ijk[3] = {fin ? static_cast<int>(std::floor(p[0] / leaf)) : 0, fin ? static_cast<int>(std::floor(p[1] / leaf)) : 0, fin ? static_cast<int>(std::floor(p[2] / leaf)) : 0};
     for (int k = 0; k < 7; ++k) {
       int id = -1;
-      bool in = true;
+      bool in = fin;
       for (int a = 0; a < 3; ++a) in = in && (grid[a] - ijk[a] <= disp[k][a]) && (grid[3 + a] - ijk[a] >= disp[k][a]);
       if (in) {
         const int key = (ijk[0] + disp[k][0] - grid[0]) * grid[9] + (ijk[1] + disp[k][1] - grid[1]) * grid[10] + (ijk[2] + disp[k][2] - grid[2]) * grid[11];
