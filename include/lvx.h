@@ -467,6 +467,46 @@ int lvx_ndt_align(lvx_ctx* ctx, int n, const float* src_xyzi4, const float* gues
  * under `transform16` to its nearest target point (float L2, exact search), counting distances <= max_range; DBL_MAX when nothing is counted. */
 int lvx_ndt_fitness(lvx_ctx* ctx, int n_src, const float* src_xyzi4, const float* transform16, int n_tgt, const float* tgt_xyzi4, double max_range, double* fitness);
 
+/* LiDAR odometry: NDT scan-to-map poses without A-LOAM ---------------------------------------------------------------------------------------------*/
+/* downsampleCloud (include/utils/pcl_utils.h:46-53) = pcl::VoxelGrid<VPoint> with one leaf size on all axes, all fields averaged, over an UNORGANISED cloud: float
+ * min / max of the cloud, min_b = floor(min / leaf), voxel index = sum over axes of int(floor(x * (1 / leaf)) - float(min_b)) * mul, points ordered by index (equal
+ * indices in input order), one output point per run in index order = the float sum of x, y, z, intensity in that order divided by the float count.  Points with a
+ * non-finite x, y or z are left out (pcl::VoxelGrid on a non-dense cloud).  n = 0: 0 points.  LVX_E_ARG: NULL / negative arguments, leaf <= 0, or a leaf so small that
+ * div_x * div_y * div_z exceeds int32 ("Leaf size is too small for the input dataset", as PCL refuses it).  The host form writes at most max_out points and reports
+ * the full count in *n_out; the _d form takes device pointers (out_xyzi4_d holds n points) and still returns the count to the host, so it waits for the stream. */
+int lvx_voxelgrid_downsample(lvx_ctx* ctx, int n, const float* xyzi4, float leaf_size, int64_t max_out, float* out_xyzi4, int32_t* n_out);
+int lvx_voxelgrid_downsample_d(lvx_ctx* ctx, int n, const float* xyzi4_d, float leaf_size, float* out_xyzi4_d, int32_t* n_out);
+/* LiDAROdometry::feedScan(t, scan, predict, update_map = true, using_loam = false) (src/core/lidar_odometry.cpp:45-128) over the scans of lvx_set_scans, in order —
+ * what CalibrHelperLVI::Initialization runs before EstimateRotation (calib_helper_lvi.cpp:55-60, there with an identity prediction).  Per scan k:
+ *   the first scan (empty map, :56-57): pose = identity, no registration (its step record is zero but converged = 1);
+ *   otherwise registration() (:76-87): guess = pose[k-1] * predict[k] formed in double and cast to float (predict16 NULL: pose[k-1]); source = the filter above at
+ *     downsample_leaf over the scan's x, y, z, intensity; pose = final_transformation of lvx_ndt_align's loop against the current grid, cast to double;
+ *   updateKeyScan / checkKeyScan (:89-128, the rule of lvx_data_association_poses): a key scan — all its points, NaN ones included — is moved with its pose
+ *     (pcl::transformPointCloud with a Matrix4d: double, summed left to right, rounded to float; non-finite points copied) and appended to the map cloud on the device;
+ *     the voxel grid is rebuilt over the WHOLE map at ndt_resolution (setInputTarget(map_cloud_), :98-102).
+ * The clouds, the map and the grid stay on the device; the host keeps what the reference keeps in scalars (Newton / More-Thuente bookkeeping, the key decision).
+ * After the call the context's voxel grid is that of the final map, as after lvx_voxel_build_d.
+ * DEVIATION: a scan whose source is empty (every point non-finite) keeps the guess as its pose, with n_src = 0, converged = 1, n_evaluations = 0 — PCL refuses an
+ * empty input cloud.  LVX_E_STATE: before lvx_set_scans, or a map whose grid has no leaf (as lvx_ndt_align).  LVX_E_ARG: NULL pose16 / steps, a non-positive
+ * resolution or leaf, an unknown search, or n_key * H * W beyond 2^31 - 1 points. */
+typedef struct lvx_odom_options {
+  float ndt_resolution, downsample_leaf;        /* 0.5, 0.5 (lidar_odometry.cpp:36,81) */
+  double key_dist, key_angle_deg;               /* 0.2 m, 5 deg (:121-122) */
+  lvx_ndt_options ndt;                          /* step 0.01, epsilon 1e-3, 50 iterations, DIRECT7 (:36-41); outlier ratio: the constructor's 0.55 */
+  int32_t min_points_per_voxel, reserved;       /* 6 (ndt_omp: VoxelGridCovariance default) */
+  double min_covar_eigvalue_mult;               /* 0.01 */
+} lvx_odom_options;
+typedef struct lvx_odom_step {
+  int32_t n_src, is_key, iterations, converged, n_evaluations, reserved;   /* filtered source points; 1 = joined the map; then as lvx_ndt_result */
+  double score, trans_probability, p6[6];
+} lvx_odom_step;
+int lvx_odom_default_options(lvx_odom_options* opt);
+/* predict16: [n_scans][16] row-major or NULL; pose16: out, [n_scans][16] row-major scan -> map; steps: out, [n_scans]; n_key (may be NULL): out, key scans */
+int lvx_lidar_odometry(lvx_ctx* ctx, const lvx_odom_options* opt, const double* predict16, double* pose16, lvx_odom_step* steps, int32_t* n_key);
+/* the key-scan map cloud of the last lvx_lidar_odometry (n_key * H * W points, NaN points included): at most max_points are written, *n_points (may be NULL) is the
+ * full count.  LVX_E_STATE before any odometry run. */
+int lvx_odometry_get_map(lvx_ctx* ctx, int64_t max_points, float* xyzi4, int64_t* n_points);
+
 /* surfel map extraction ------------------------------------------------------------------------------*/
 /* SurfelAssociation::setSurfelMap + checkPlaneType (src/lvi_exc/src/core/surfel_association.cpp:50-86, 246-266) over the leaves of the last
  * lvx_voxel_build of this context (the cloud passed to it must still be alive): leaves with >= min_leaf_points points and planarity >= p_lambda,

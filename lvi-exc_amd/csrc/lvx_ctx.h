@@ -184,6 +184,11 @@ struct lvx_ctx {
   // device-resident DataAssociation (lvx_set_scans / lvx_data_association): [0] raw scans, [1] state, [2] map time, [3] map pose, [4] scans in the map frame = map cloud,
   // [5] plane table, [6] flags, [7] SurfelPoint arrays
   lvx::DevBuf d_da_key, d_da_aux;   // lvx_data_association_poses (first map): the key-scan map cloud; per-scan [time | q | p | valid | present | pose16 | key list]
+  // pcl::VoxelGrid centroid filter (lvx_voxelgrid_downsample): [0] extents + VxInfo, [1] keys, [2] point ids (both double-buffered for the sort), [3] digit
+  // histograms and tile counts of the sort, [4] run heads per tile; ds_cells_cap bounds the key range the sort covers (grown on demand); ds_pinned: what the host reads back (overflow, output count)
+  lvx::DevBuf d_ds[5]; long long ds_cells_cap = 0; void* ds_pinned = nullptr;
+  // lvx_lidar_odometry: [0] the current scan as xyzi, [1] its filtered source cloud (also the work buffers of the host-array filter call), [2] the key-scan map cloud
+  lvx::DevBuf d_od[3]; long long od_map_n = -1;   // points in the map cloud; -1 = no odometry run yet
   lvx::DevBuf d_da[8]; int da_S = 0, da_H = 0, da_W = 0, da_points = 0; std::vector<lvx_surfel_plane> da_planes;
   // lvx_data_association without host stops (round 5): capacities learned from the previous call (leaves, planes, association-grid list entries; 0 = none yet, the call
   // runs the synchronous path), the pinned mirror the device writes its counts into, the planes still to fetch from d_da[5] when somebody asks for them

@@ -509,7 +509,7 @@ __global__ __launch_bounds__(256) void k_vx_keys(const float4* p, int n, const V
   const int nbins = 1 << db;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool ovf = info->overflow != 0;
-  if (!ovf) { const long long nc = info->cells; for (long long e = i; e < nc; e += (long long)gridDim.x * blockDim.x) cells[e] = -1; }
+  if (!ovf && cells) { const long long nc = info->cells; for (long long e = i; e < nc; e += (long long)gridDim.x * blockDim.x) cells[e] = -1; }   // (no table: the centroid filter sorts only)
   if (i < n_tiles) lb[i] = 0ull;
   if (tcnt) for (int e = i; e < n_tcnt; e += gridDim.x * blockDim.x) tcnt[e] = 0u;
   if (blockIdx.x * 1024 >= n) return;   // (workgroups that only clear)
@@ -1862,6 +1862,11 @@ __global__ void k_undistort(const double* state, int N, double t0, double dt, in
 // orientation at the scan's stamp, conjugated) — rounded to float, the VPoint of scan_data_ — and then moved with the scan's odometry pose as pcl::transformPointCloud does
 // with a Matrix4d (double arithmetic on the float coordinates, rounded to float; non-finite points stay as they are).  Scans without a pose or whose stamp lies outside
 // the spline are absent from scan_data_in_map_: their points become NaN here (no association, no map point).
+// pcl::transformPointCloud with a Matrix4d on one point: double arithmetic on the float coordinates, the sum taken left to right, rounded to float (T row-major 4 x 4)
+__device__ __forceinline__ float4 xf_pose16(const double* T, const float4 o) {
+  const double x = (double)o.x, y = (double)o.y, z = (double)o.z;
+  return make_float4((float)(T[0] * x + T[1] * y + T[2] * z + T[3]), (float)(T[4] * x + T[5] * y + T[6] * z + T[7]), (float)(T[8] * x + T[9] * y + T[10] * z + T[11]), o.w);
+}
 __global__ void k_deskew_pose(const double* state, int N, double t0, double dt, int HW, int n, const PointXYZIT* raw, const double* q_scan, const int* present, const double* pose16, float4* out, int* flags_init) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1876,14 +1881,87 @@ __global__ void k_deskew_pose(const double* state, int N, double t0, double dt, 
     const v3 po = qrot(qmul(qGt, q), mk((double)r.x, (double)r.y, (double)r.z));
     o = make_float4((float)po.x, (float)po.y, (float)po.z, r.intensity);
   }
-  const double* T = pose16 + 16 * (size_t)s;
-  const double x = (double)o.x, y = (double)o.y, z = (double)o.z;
-  out[i] = make_float4((float)(T[0] * x + T[1] * y + T[2] * z + T[3]), (float)(T[4] * x + T[5] * y + T[6] * z + T[7]), (float)(T[8] * x + T[9] * y + T[10] * z + T[11]), o.w);
+  out[i] = xf_pose16(pose16 + 16 * (size_t)s, o);
 }
 // the key-scan map (LiDAROdometry::updateKeyScan: *map_cloud_ += scan_in_target): scans key[0], key[1], ... of the scans in the map frame, concatenated
 __global__ void k_gather_scans(const float4* scans, const int* key, int HW, int n, float4* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = scans[(size_t)key[i / HW] * HW + i % HW];
+}
+
+
+// ---- pcl::VoxelGrid centroid filter of an unorganised cloud (downsampleCloud, include/utils/pcl_utils.h:46-53) and the kernels of the NDT odometry loop ----------------
+// The filter is k_vx_extent -> k_vx_keys -> the stable radix sort of the covariance grid -> the three kernels below.  As for the covariance leaves only the reference's
+// summation order reproduces its floats: a run (= voxel) is summed by ONE lane, in sorted = input order.  k_sr_voxelgrid stays the per-ring LDS kernel.
+struct DsHost { int overflow, n_out; long long cells; };   // pinned mirror: VxInfo::overflow, output points, cells of the extents
+// run heads (first sorted position of a voxel; the non-finite points' invalid key sorts last and starts no run) per tile of 256 sorted positions
+__global__ __launch_bounds__(256) void k_ds_heads(const unsigned* __restrict__ skeys, int n, unsigned invalid, int* tile_cnt) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  bool head = false;
+  if (i < n) { const unsigned k = skeys[i]; head = k != invalid && (i == 0 || skeys[i - 1] != k); }
+  const int cnt = __syncthreads_count(head);
+  if (threadIdx.x == 0) tile_cnt[blockIdx.x] = cnt;
+}
+// exclusive scan of the tiles' head counts in one workgroup (1 024 tiles = 262 144 points per round); the total is the number of output points
+__global__ __launch_bounds__(1024) void k_ds_scan(int* tile_cnt, int n_tiles, const VxInfo* info, DsHost* h_res) {
+  __shared__ int wsum[16];
+  __shared__ int carry_s;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (tid == 0) carry_s = 0;
+  __syncthreads();
+  for (int t0 = 0; t0 < n_tiles; t0 += 1024) {
+    const int t = t0 + tid;
+    const int v = t < n_tiles ? tile_cnt[t] : 0;
+    int incl = v;
+    for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(incl, o); if (lane >= o) incl += u; }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int base = carry_s;
+    for (int w = 0; w < wv; ++w) base += wsum[w];
+    if (t < n_tiles) tile_cnt[t] = base + incl - v;
+    __syncthreads();
+    if (tid == 1023) carry_s = base + incl;
+    __syncthreads();
+  }
+  if (tid == 0) {
+    DsHost r; r.overflow = info->overflow; r.n_out = carry_s; r.cells = info->cells;
+    *h_res = r;
+  }
+}
+// one lane per run: the float sum of all four fields over the run's points in sorted order, divided by the float count (pcl::VoxelGrid's centroid with all fields averaged)
+__global__ __launch_bounds__(256) void k_ds_centroid(const float4* __restrict__ p, const unsigned* __restrict__ skeys, const int* __restrict__ sids, int n, unsigned invalid,
+                                                     const int* __restrict__ tile_off, float4* out) {
+  __shared__ int wcnt[4];
+  const int i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  unsigned k = invalid;
+  bool head = false;
+  if (i < n) { k = skeys[i]; head = k != invalid && (i == 0 || skeys[i - 1] != k); }
+  const unsigned long long m = __ballot(head);
+  if (lane == 0) wcnt[wv] = __popcll(m);
+  __syncthreads();
+  if (!head) return;
+  int r = tile_off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+  for (int w = 0; w < wv; ++w) r += wcnt[w];
+  float cx = 0.f, cy = 0.f, cz = 0.f, cw = 0.f;
+  int e = i;
+  do { const float4 q = p[sids[e]]; cx += q.x; cy += q.y; cz += q.z; cw += q.w; ++e; } while (e < n && skeys[e] == k);
+  const float cnt = (float)(e - i);
+  out[r] = make_float4(cx / cnt, cy / cnt, cz / cnt, cw / cnt);
+}
+// PointXYZIT -> the xyzi cloud the filter, the registration and the map take (VPoint)
+__global__ void k_xyzit_to_xyzi(const PointXYZIT* __restrict__ raw, int n, float4* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PointXYZIT r = raw[i];
+  out[i] = make_float4(r.x, r.y, r.z, r.intensity);
+}
+// updateKeyScan (lidar_odometry.cpp:98-101): the whole scan under its pose, appended to the map cloud; points with a non-finite coordinate are copied as they are
+struct Pose16 { double m[16]; };
+__global__ void k_transform_append(const float4* __restrict__ scan, int n, Pose16 T, float4* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 q = scan[i];
+  out[i] = (isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) ? xf_pose16(T.m, q) : q;
 }
 
 }  // namespace lvx
@@ -2047,29 +2125,30 @@ int lvx_scan_register_batch(lvx_ctx* c, int n_sweeps, const int32_t* sweep_offse
 // clear + keys -> rocPRIM radix sort -> k_vx_leaf: run heads, leaf numbering, sums, eigen-solve), captured once per (cloud buffer, size, parameters) into a HIP graph and
 // replayed: a small cloud's build is bound by the NUMBER of launches (~4.6 us each in a replayed graph), not by HBM.  Leaf arrays are strided by the CAPACITY (the point count: a leaf holds at least one point), the dense cell table by its own capacity.
 static int vox_info(lvx_ctx* c);
-static int voxel_enqueue(lvx_ctx* c, const float4* d_pts, int n, float leaf, int min_pts, double eig_mult) {
+// Keys and their stable sort by voxel index, shared by the covariance grid and the centroid filter (lvx_voxelgrid_downsample): keys / vals hold 2 n entries each, the
+// sorted keys and point ids end in their second halves.  tmp: digit histograms (k_vx_extent clears them: ghist below goes to it too) + per-tile digit counts of the own
+// sort, or rocPRIM's work area.  cells (may be NULL) / lbs / n_tiles: what k_vx_keys resets for the covariance leaves.
+struct VxSort { unsigned* keys; int* vals; void* tmp; size_t rocprim_bytes; int sort_bits; };
+static int* vx_sort_ghist(const VxSort& S, int n) { return n <= VX_OWN_SORT_MAX ? (int*)S.tmp : nullptr; }
+static unsigned vx_sort_invalid(const VxSort& S) { return (unsigned)((1ull << S.sort_bits) - 1ull); }   // sort_bits <= 31 (cells_cap is clamped), the 64-bit shift keeps even 32 defined
+static size_t vx_sort_tmp_bytes(size_t rocprim_bytes) {   // digit histograms + per-tile digit counts of the own sort (up to 4 passes x 1 024 bins)
+  return std::max(rocprim_bytes + 16, (size_t)4 * 1024 * 4 + (size_t)4 * ((VX_OWN_SORT_MAX + 1023) / 1024) * 1024 * 4);
+}
+static int vx_keys_sort_enqueue(lvx_ctx* c, const float4* d_pts, int n, const VxInfo* d_info, const VxSort& S, int* cells, unsigned long long* lbs, int n_tiles) {
   hipStream_t st = c->stream;
-  lvx_ctx::Voxels& V = c->vox;
-  int* d_mm = (int*)V.misc.p;
-  VxInfo* d_info = (VxInfo*)((char*)V.misc.p + 64);
-  unsigned* k_in = (unsigned*)V.keys.p; unsigned* k_out = k_in + n;
-  int* v_in = (int*)V.vals.p; int* v_out = v_in + n;
-  unsigned* counts = (unsigned*)V.runs.p + n; unsigned* offs = counts + n;   // ([0, n) unused since the run-length encode left)
-  unsigned long long* lbs = (unsigned long long*)((unsigned*)V.runs.p + (((size_t)n * 3 + 1) & ~(size_t)1));   // look-back states of k_vx_leaf, one per tile
-  const size_t cap = (size_t)V.cap;
-  const int n_tiles = (n + 255) / 256;
+  unsigned* k_in = S.keys; unsigned* k_out = k_in + n;
+  int* v_in = S.vals; int* v_out = v_in + n;
   // own radix sort up to VX_OWN_SORT_MAX points (one launch per 8-bit digit), rocPRIM above; either way the sorted keys / ids end in the second halves of the buffers
   const bool own_sort = n <= VX_OWN_SORT_MAX;
   // digit width: the narrowest of 8 / 9 / 10 bits that covers the key range in the fewest passes (<= 16 bits: 2 x 8, <= 18: 2 x 9, <= 20: 2 x 10, <= 24: 3 x 8, ...)
-  int db = 8, passes = (V.sort_bits + 7) / 8;
-  for (int d = 9; d <= 10; ++d) if ((V.sort_bits + d - 1) / d < passes) { db = d; passes = (V.sort_bits + d - 1) / d; }
+  int db = 8, passes = (S.sort_bits + 7) / 8;
+  for (int d = 9; d <= 10; ++d) if ((S.sort_bits + d - 1) / d < passes) { db = d; passes = (S.sort_bits + d - 1) / d; }
   const int nbins = 1 << db, sort_tiles = (n + 1023) / 1024;
-  int* ghist = own_sort ? (int*)V.tmp.p : nullptr;
-  unsigned* tcnt = own_sort ? (unsigned*)V.tmp.p + 4 * 1024 : nullptr;
-  hipLaunchKernelGGL(k_vx_extent, dim3((unsigned)std::min(std::max(n / 4096, 64), 256)), dim3(256), 0, st, d_pts, n, d_mm, leaf, (long long)V.cells_cap, d_info, ghist);
-  const unsigned invalid = (unsigned)((1ull << V.sort_bits) - 1ull);   // sort_bits <= 31 (cells_cap is clamped), the 64-bit shift keeps even 32 defined
+  int* ghist = vx_sort_ghist(S, n);
+  unsigned* tcnt = own_sort ? (unsigned*)S.tmp + 4 * 1024 : nullptr;
+  const unsigned invalid = vx_sort_invalid(S);
   unsigned* k_first = (own_sort && passes % 2 == 0) ? k_out : k_in;   // an even number of passes starts in the second buffer
-  hipLaunchKernelGGL(k_vx_keys, dim3((unsigned)std::max((n + 1023) / 1024, 512)), dim3(256), 0, st, d_pts, n, (const VxInfo*)d_info, invalid, k_first, v_in, (int*)V.cells.p, lbs, n_tiles,
+  hipLaunchKernelGGL(k_vx_keys, dim3((unsigned)std::max((n + 1023) / 1024, 512)), dim3(256), 0, st, d_pts, n, d_info, invalid, k_first, v_in, cells, lbs, n_tiles,
                      ghist, tcnt, passes * sort_tiles * nbins, passes, db);
   if (own_sort) {
     unsigned* ka = k_first; unsigned* kb = k_first == k_in ? k_out : k_in;
@@ -2087,16 +2166,32 @@ static int voxel_enqueue(lvx_ctx* c, const float4* d_pts, int n, float leaf, int
       std::swap(ka, kb); std::swap(va, vb);
     }
   } else {
-    size_t t1 = V.tmp_bytes[0];
-    LVX_HIP(c, rocprim::radix_sort_pairs(V.tmp.p, t1, k_in, k_out, v_in, v_out, (size_t)n, 0, (unsigned)V.sort_bits, st));   // stable: input order kept inside a leaf
+    size_t t1 = S.rocprim_bytes;
+    LVX_HIP(c, rocprim::radix_sort_pairs(S.tmp, t1, k_in, k_out, v_in, v_out, (size_t)n, 0, (unsigned)S.sort_bits, st));   // stable: input order kept inside a leaf
   }
+  return LVX_OK;
+}
+static int voxel_enqueue(lvx_ctx* c, const float4* d_pts, int n, float leaf, int min_pts, double eig_mult) {
+  hipStream_t st = c->stream;
+  lvx_ctx::Voxels& V = c->vox;
+  int* d_mm = (int*)V.misc.p;
+  VxInfo* d_info = (VxInfo*)((char*)V.misc.p + 64);
+  const VxSort S{(unsigned*)V.keys.p, (int*)V.vals.p, V.tmp.p, V.tmp_bytes[0], V.sort_bits};
+  const unsigned* k_out = S.keys + n; const int* v_out = S.vals + n;
+  unsigned* counts = (unsigned*)V.runs.p + n; unsigned* offs = counts + n;   // ([0, n) unused since the run-length encode left)
+  unsigned long long* lbs = (unsigned long long*)((unsigned*)V.runs.p + (((size_t)n * 3 + 1) & ~(size_t)1));   // look-back states of k_vx_leaf, one per tile
+  const size_t cap = (size_t)V.cap;
+  const int n_tiles = (n + 255) / 256;
+  hipLaunchKernelGGL(k_vx_extent, dim3((unsigned)std::min(std::max(n / 4096, 64), 256)), dim3(256), 0, st, d_pts, n, d_mm, leaf, (long long)V.cells_cap, d_info, vx_sort_ghist(S, n));
+  const unsigned invalid = vx_sort_invalid(S);
+  { const int rc = vx_keys_sort_enqueue(c, d_pts, n, (const VxInfo*)d_info, S, (int*)V.cells.p, lbs, n_tiles); if (rc) return rc; }
   int* lk = (int*)V.leaf_i.p; int* ln = lk + cap;
   double* mean = (double*)V.leaf_d.p; double* cov = mean + 3 * cap; double* icov = cov + 9 * cap; double* evecs = icov + 9 * cap; double* evals = evecs + 9 * cap;
   // tile = 256 PT sorted positions per workgroup, PT chosen so that the launch is ONE round of resident workgroups (4 per CU at 37 KB of LDS = 1 024) as long as the
   // cloud allows: the workgroup is a latency chain (keys -> counts of all predecessors -> points -> sums -> eigen-solve) and a second round repeats it
   auto launch_leaf = [&](auto pt) {
     constexpr int PT = decltype(pt)::value;
-    hipLaunchKernelGGL(k_vx_leaf<PT>, dim3((unsigned)((n + 256 * PT - 1) / (256 * PT))), dim3(256), 0, st, d_pts, (const unsigned*)k_out, (const int*)v_out, n, invalid, lbs, min_pts, eig_mult, d_info, (int*)V.cells.p, lk, ln,
+    hipLaunchKernelGGL(k_vx_leaf<PT>, dim3((unsigned)((n + 256 * PT - 1) / (256 * PT))), dim3(256), 0, st, d_pts, k_out, v_out, n, invalid, lbs, min_pts, eig_mult, d_info, (int*)V.cells.p, lk, ln,
                        counts, offs, mean, cov, icov, evecs, evals, (float*)V.leaf_f.p, (VxInfo*)V.h_info);
   };
   if (n > 524288) launch_leaf(std::integral_constant<int, 4>{});
@@ -2135,8 +2230,7 @@ static int voxel_build_device(lvx_ctx* c, const float4* d_pts, int n, float leaf
     size_t t1 = 0;
     LVX_HIP(c, rocprim::radix_sort_pairs(nullptr, t1, k_in, k_in + n, v_in, v_in + n, (size_t)n, 0, (unsigned)V.sort_bits, st));
     V.tmp_bytes[0] = t1;
-    const size_t own = (size_t)4 * 1024 * 4 + (size_t)4 * ((VX_OWN_SORT_MAX + 1023) / 1024) * 1024 * 4;   // digit histograms + per-tile digit counts of the own sort (up to 4 passes x 1 024 bins)
-    if ((rc = dev_alloc(c, V.tmp, std::max(t1 + 16, own)))) return rc;
+    if ((rc = dev_alloc(c, V.tmp, vx_sort_tmp_bytes(t1)))) return rc;
   }
   // replay the captured chain when nothing it was captured with has changed
   uint64_t lb = 0, eb = 0; std::memcpy(&lb, &leaf, 4); std::memcpy(&eb, &eig_mult, 8);
@@ -2206,6 +2300,79 @@ int lvx_voxel_build_d(lvx_ctx* c, int n, const float* xyzi4_d, float leaf, int m
   LVX_HIP(c, hipSetDevice(c->device));
   ProfScope ps(c, LVX_KERNEL_UPSTREAM);
   return voxel_build_device(c, (const float4*)xyzi4_d, n, leaf, min_pts, eig_mult);   // asynchronous: nothing comes back to the host until a consumer asks (vox_info)
+}
+// pcl::VoxelGrid<VPoint>::applyFilter with all fields averaged (downsampleCloud, include/utils/pcl_utils.h:46-53): extents -> keys -> stable sort (the covariance grid's
+// kernels, without its cell table) -> run heads -> one lane per run.  One host stop: the output count (and whether the sorted key range covered the extents — if not the
+// range grows and the chain runs again, as vox_info does for the cell table).  d_out holds n points.
+static int downsample_device(lvx_ctx* c, const float4* d_pts, int n, float leaf, float4* d_out, int* n_out) {
+  hipStream_t st = c->stream;
+  *n_out = 0;
+  if (n == 0) return LVX_OK;
+  int rc;
+  if (!c->ds_pinned) LVX_HIP(c, hipHostMalloc(&c->ds_pinned, sizeof(DsHost), hipHostMallocDefault));
+  if (c->ds_cells_cap < (1 << 18) - 1) c->ds_cells_cap = (1 << 18) - 1;
+  if (!c->d_ds[0].p) {   // extents in their start state (k_vx_extent's last workgroup restores it)
+    if ((rc = dev_alloc(c, c->d_ds[0], 64 + sizeof(VxInfo)))) return rc;
+    const int mm0[7] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
+    LVX_HIP(c, hipMemcpyAsync(c->d_ds[0].p, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
+    LVX_HIP(c, hipStreamSynchronize(st));
+  }
+  const int n_tiles = (n + 255) / 256;
+  if ((rc = dev_alloc(c, c->d_ds[1], (size_t)n * 4 * 2))) return rc;
+  if ((rc = dev_alloc(c, c->d_ds[2], (size_t)n * 4 * 2))) return rc;
+  if ((rc = dev_alloc(c, c->d_ds[4], (size_t)n_tiles * 4))) return rc;
+  int* d_mm = (int*)c->d_ds[0].p;
+  VxInfo* d_info = (VxInfo*)((char*)c->d_ds[0].p + 64);
+  for (int round = 0;; ++round) {
+    int bits = 1; while ((1ll << bits) - 1 < c->ds_cells_cap && bits < 31) ++bits;   // keys < cells <= capacity <= 2^31 - 1 < the invalid key 2^bits - 1
+    VxSort S{(unsigned*)c->d_ds[1].p, (int*)c->d_ds[2].p, nullptr, 0, bits};
+    if (n > VX_OWN_SORT_MAX) LVX_HIP(c, rocprim::radix_sort_pairs(nullptr, S.rocprim_bytes, S.keys, S.keys + n, S.vals, S.vals + n, (size_t)n, 0, (unsigned)bits, st));
+    if ((rc = dev_alloc(c, c->d_ds[3], vx_sort_tmp_bytes(S.rocprim_bytes)))) return rc;
+    S.tmp = c->d_ds[3].p;
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      hipLaunchKernelGGL(k_vx_extent, dim3((unsigned)std::min(std::max(n / 4096, 64), 256)), dim3(256), 0, st, d_pts, n, d_mm, leaf, c->ds_cells_cap, d_info, vx_sort_ghist(S, n));
+      if ((rc = vx_keys_sort_enqueue(c, d_pts, n, (const VxInfo*)d_info, S, nullptr, nullptr, 0))) return rc;
+      const unsigned invalid = vx_sort_invalid(S);
+      hipLaunchKernelGGL(k_ds_heads, dim3((unsigned)n_tiles), dim3(256), 0, st, (const unsigned*)(S.keys + n), n, invalid, (int*)c->d_ds[4].p);
+      hipLaunchKernelGGL(k_ds_scan, dim3(1), dim3(1024), 0, st, (int*)c->d_ds[4].p, n_tiles, (const VxInfo*)d_info, (DsHost*)c->ds_pinned);
+      hipLaunchKernelGGL(k_ds_centroid, dim3((unsigned)n_tiles), dim3(256), 0, st, d_pts, (const unsigned*)(S.keys + n), (const int*)(S.vals + n), n, invalid, (const int*)c->d_ds[4].p, d_out); }
+    LVX_HIP(c, hipGetLastError());
+    LVX_HIP(c, hipStreamSynchronize(st));
+    DsHost r; std::memcpy(&r, c->ds_pinned, sizeof(r));
+    if (r.overflow == 2) return fail(c, LVX_E_ARG, "Leaf size is too small for the input dataset. Integer indices would overflow.");   // pcl/filters/impl/voxel_grid.hpp:241-246
+    if (r.overflow == 1) {
+      if (round > 0) return fail(c, LVX_E_ALLOC, "voxel key range could not be grown");
+      c->ds_cells_cap = std::min<long long>(r.cells + r.cells / 4, 2147483647LL);
+      continue;
+    }
+    *n_out = r.n_out;
+    return LVX_OK;
+  }
+}
+int lvx_voxelgrid_downsample_d(lvx_ctx* c, int n, const float* xyzi4_d, float leaf, float* out_xyzi4_d, int32_t* n_out) {
+  if (!c || n < 0 || !(leaf > 0) || !n_out || (n > 0 && (!xyzi4_d || !out_xyzi4_d))) return LVX_E_ARG;
+  LVX_HIP(c, hipSetDevice(c->device));
+  int m = 0;
+  const int rc = downsample_device(c, (const float4*)xyzi4_d, n, leaf, (float4*)out_xyzi4_d, &m);
+  *n_out = m;
+  return rc;
+}
+int lvx_voxelgrid_downsample(lvx_ctx* c, int n, const float* xyzi4, float leaf, int64_t max_out, float* out_xyzi4, int32_t* n_out) {
+  if (!c || n < 0 || !(leaf > 0) || !n_out || max_out < 0 || (n > 0 && !xyzi4) || (max_out > 0 && !out_xyzi4)) return LVX_E_ARG;
+  LVX_HIP(c, hipSetDevice(c->device));
+  *n_out = 0;
+  if (n == 0) return LVX_OK;
+  int rc, m = 0;
+  if ((rc = upload(c, c->d_od[0], xyzi4, (size_t)n * 16))) return rc;
+  if ((rc = dev_alloc(c, c->d_od[1], (size_t)n * 16))) return rc;
+  if ((rc = downsample_device(c, (const float4*)c->d_od[0].p, n, leaf, (float4*)c->d_od[1].p, &m))) return rc;   // (waits for the stream: the caller's buffer may go away)
+  *n_out = m;
+  const size_t take = (size_t)std::min<int64_t>(m, max_out);
+  if (take) {
+    LVX_HIP(c, hipMemcpyAsync(out_xyzi4, c->d_od[1].p, take * 16, hipMemcpyDeviceToHost, c->stream));
+    LVX_HIP(c, hipStreamSynchronize(c->stream));
+  }
+  return LVX_OK;
 }
 int lvx_voxel_get(lvx_ctx* c, int32_t* leaf_key, int32_t* leaf_n, double* mean, double* cov, double* icov, double* evecs, double* evals, float* centroid,
                   int32_t* offsets, int32_t* point_ids) {
@@ -2765,6 +2932,29 @@ static void r2ypr_deg(const double* T, double ypr[3]) {   // mathutils::R2ypr (i
   const double r = std::atan2(a0 * std::sin(y) - a1 * std::cos(y), -o0 * std::sin(y) + o1 * std::cos(y));
   ypr[0] = y / M_PI * 180.0; ypr[1] = p / M_PI * 180.0; ypr[2] = r / M_PI * 180.0;
 }
+// LiDAROdometry::checkKeyScan (lidar_odometry.cpp:107-128) over the scans fed so far: the first one, or one further than key_dist from the LAST KEY scan, or turned by
+// more than key_angle_deg in yaw, pitch or roll.  Shared by the first map from given poses and by lvx_lidar_odometry.
+struct KeyScanRule {
+  double key_dist, key_angle_deg, pos_last[3] = {0, 0, 0}, ypr_last[3] = {0, 0, 0};
+  bool any = false;
+  KeyScanRule(double dist, double angle_deg) : key_dist(dist), key_angle_deg(angle_deg) {}
+  bool check(const double* T) {   // T row-major 4 x 4 scan -> map
+    const double dx = T[3] - pos_last[0], dy = T[7] - pos_last[1], dz = T[11] - pos_last[2];
+    const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
+    double ypr[3]; r2ypr_deg(T, ypr);
+    bool turned = false;
+    for (int a = 0; a < 3; ++a) {
+      double d = ypr[a] - ypr_last[a];
+      if (d > 180) d -= 360;           // LiDAROdometry::normalize_angle (include/core/lidar_odometry.h:95-102)
+      if (d < -180) d += 360;
+      if (std::fabs(d) > key_angle_deg) turned = true;
+    }
+    if (any && !(dist > key_dist) && !turned) return false;
+    pos_last[0] = T[3]; pos_last[1] = T[7]; pos_last[2] = T[11]; ypr_last[0] = ypr[0]; ypr_last[1] = ypr[1]; ypr_last[2] = ypr[2];
+    any = true;
+    return true;
+  }
+};
 int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* scan_t, const double* pose16, const int32_t* has_pose, double key_dist, double key_angle_deg,
                                const lvx_assoc_options* opt_in, int32_t* n_planes, int32_t* n_points, int32_t* key_scan) {
   if (!c || !state || !scan_t || !pose16) return LVX_E_ARG;
@@ -2795,24 +2985,12 @@ int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* sc
   LVX_HIP(c, hipMemcpyAsync(present.data(), d_valid, (size_t)S * 4, hipMemcpyDeviceToHost, st));
   LVX_HIP(c, hipStreamSynchronize(st));
   // Mapping(): scans in order; feedScan needs the scan's pose (loam_poses_map_.find(stamp)); checkKeyScan against the LAST KEY scan
-  double pos_last[3] = {0, 0, 0}, ypr_last[3] = {0, 0, 0};
+  KeyScanRule rule(key_dist, key_angle_deg);
   for (int s = 0; s < S; ++s) {
     present[s] = (present[s] && (!has_pose || has_pose[s])) ? 1 : 0;
     if (key_scan) key_scan[s] = 0;
     if (!present[s]) continue;
-    const double* T = pose16 + 16 * (size_t)s;
-    const double dx = T[3] - pos_last[0], dy = T[7] - pos_last[1], dz = T[11] - pos_last[2];
-    const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
-    double ypr[3]; r2ypr_deg(T, ypr);
-    bool turned = false;
-    for (int a = 0; a < 3; ++a) {
-      double d = ypr[a] - ypr_last[a];
-      if (d > 180) d -= 360;           // LiDAROdometry::normalize_angle (include/core/lidar_odometry.h:95-102)
-      if (d < -180) d += 360;
-      if (std::fabs(d) > key_angle_deg) turned = true;
-    }
-    if (key.empty() || dist > key_dist || turned) {
-      pos_last[0] = T[3]; pos_last[1] = T[7]; pos_last[2] = T[11]; ypr_last[0] = ypr[0]; ypr_last[1] = ypr[1]; ypr_last[2] = ypr[2];
+    if (rule.check(pose16 + 16 * (size_t)s)) {
       key.push_back(s);
       if (key_scan) key_scan[s] = 1;
     }
@@ -3144,14 +3322,15 @@ int lvx_ndt_derivatives(lvx_ctx* c, int n, const float* input_xyzi4, const float
   return LVX_OK;
 }
 
-// pcl::Registration::align -> pclomp::NormalDistributionsTransform::computeTransformation (ndt_omp_impl.hpp:81-171) against the voxel grid of the last lvx_voxel_build
-int lvx_ndt_align(lvx_ctx* c, int n, const float* src_xyzi4, const float* guess16, const lvx_ndt_options* opt, lvx_ndt_result* res, float* aligned_xyzi4) {
-  if (!c || n < 0 || !res || (n > 0 && !src_xyzi4)) return LVX_E_ARG;
-  lvx_ndt_options o; lvx_ndt_default_options(&o); if (opt) o = *opt;
-  if (o.search != 1 && o.search != 7 && o.search != 26) return fail(c, LVX_E_ARG, "lvx_ndt_align: search must be 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
-  LVX_HIP(c, hipSetDevice(c->device));
-  { const int rc0 = vox_info(c); if (rc0) return rc0; }
+// pcl::Registration::align -> pclomp::NormalDistributionsTransform::computeTransformation (ndt_omp_impl.hpp:81-171) against the voxel grid of the last lvx_voxel_build.
+// The core takes a source cloud that is already on the device (lvx_ndt_align uploads its host cloud, lvx_lidar_odometry passes the filter's output).
+static int ndt_target_check(lvx_ctx* c) {
+  const int rc0 = vox_info(c);
+  if (rc0) return rc0;
   if (c->vox.n_leaves == 0 || !c->vox.cells.p) return fail(c, LVX_E_STATE, "lvx_ndt_align needs a target: call lvx_voxel_build first");
+  return LVX_OK;
+}
+static int ndt_align_device(lvx_ctx* c, int n, const float4* src_d, const float* guess16, const lvx_ndt_options& o, lvx_ndt_result* res) {
   std::memset(res, 0, sizeof(*res));
   if (n == 0) {   // no points: gradient and Hessian are zero, the Newton step has norm 0 and the loop leaves converged before its first iteration (:134-139)
     for (int i = 0; i < 4; ++i) res->final_transformation[5 * i] = 1.0f;
@@ -3162,8 +3341,6 @@ int lvx_ndt_align(lvx_ctx* c, int n, const float* src_xyzi4, const float* guess1
     return LVX_OK;
   }
   int rc;
-  if ((rc = upload(c, c->d_up[2], src_xyzi4, (size_t)n * 16))) return rc;
-  const float4* src_d = (const float4*)c->d_up[2].p;
   NdtDev W;
   if ((rc = ndt_workspace(c, n, &W))) return rc;
   NdtState st{};
@@ -3192,13 +3369,127 @@ int lvx_ndt_align(lvx_ctx* c, int n, const float* src_xyzi4, const float* guess1
   for (int i = 0; i < 6; ++i) res->p6[i] = p[i];
   res->iterations = nr_iterations; res->converged = converged ? 1 : 0; res->n_evaluations = st.n_eval;
   res->score = st.score; res->trans_probability = n > 0 ? st.score / (double)n : 0.0;                       // :170
+  return LVX_OK;
+}
+int lvx_ndt_align(lvx_ctx* c, int n, const float* src_xyzi4, const float* guess16, const lvx_ndt_options* opt, lvx_ndt_result* res, float* aligned_xyzi4) {
+  if (!c || n < 0 || !res || (n > 0 && !src_xyzi4)) return LVX_E_ARG;
+  lvx_ndt_options o; lvx_ndt_default_options(&o); if (opt) o = *opt;
+  if (o.search != 1 && o.search != 7 && o.search != 26) return fail(c, LVX_E_ARG, "lvx_ndt_align: search must be 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
+  LVX_HIP(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = ndt_target_check(c))) return rc;
+  if (n > 0 && (rc = upload(c, c->d_up[2], src_xyzi4, (size_t)n * 16))) return rc;
+  const float4* src_d = (const float4*)c->d_up[2].p;
+  if ((rc = ndt_align_device(c, n, src_d, guess16, o, res))) return rc;
   if (aligned_xyzi4 && n > 0) {   // the output cloud of align(): the source under the final transformation (:832, 877)
     if ((rc = dev_alloc(c, c->d_up[3], (size_t)n * 16))) return rc;
-    hipLaunchKernelGGL(k_ndt_transform, dim3((n + 255) / 256), dim3(256), 0, c->stream, src_d, n, ndt_mat12(st.final), (float4*)c->d_up[3].p);
+    hipLaunchKernelGGL(k_ndt_transform, dim3((n + 255) / 256), dim3(256), 0, c->stream, src_d, n, ndt_mat12(res->final_transformation), (float4*)c->d_up[3].p);
     LVX_HIP(c, hipGetLastError());
     LVX_HIP(c, hipMemcpyAsync(aligned_xyzi4, c->d_up[3].p, (size_t)n * 16, hipMemcpyDeviceToHost, c->stream));
     LVX_HIP(c, hipStreamSynchronize(c->stream));
   }
+  return LVX_OK;
+}
+
+// ---- LiDAROdometry::feedScan(using_loam = false) over the scans of lvx_set_scans (src/core/lidar_odometry.cpp:45-128; CalibrHelperLVI::Initialization feeds every scan with
+// an identity prediction and update_map = true, calib_helper_lvi.cpp:55-60) ----------------------------------------------------------------------------------------------
+int lvx_odom_default_options(lvx_odom_options* o) {
+  if (!o) return LVX_E_ARG;
+  std::memset(o, 0, sizeof(*o));
+  o->ndt_resolution = 0.5f; o->downsample_leaf = 0.5f; o->key_dist = 0.2; o->key_angle_deg = 5.0;   // :36, :81, :121-122
+  lvx_ndt_default_options(&o->ndt);
+  o->ndt.step_size = 0.01; o->ndt.transformation_epsilon = 1e-3; o->ndt.max_iterations = 50; o->ndt.search = 7;   // :38-41
+  o->min_points_per_voxel = 6; o->min_covar_eigvalue_mult = 0.01;
+  return LVX_OK;
+}
+// the map cloud grows by one scan per key scan: the buffer doubles and keeps its contents
+static int odom_map_reserve(lvx_ctx* c, size_t points) {
+  DevBuf& M = c->d_od[2];
+  if (M.p && M.bytes >= points * 16) return LVX_OK;
+  const size_t bytes = std::max(points * 16, M.bytes * 2);
+  void* q = nullptr;
+  if (hipMalloc(&q, bytes) != hipSuccess) return fail(c, LVX_E_ALLOC, "hipMalloc failed");
+  if (M.p && c->od_map_n > 0) {
+    const hipError_t e = hipMemcpyAsync(q, M.p, (size_t)c->od_map_n * 16, hipMemcpyDeviceToDevice, c->stream);
+    if (e != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { (void)hipFree(q); return fail(c, LVX_E_HIP, "copy of the odometry map failed"); }
+  }
+  if (M.p) { (void)hipStreamSynchronize(c->stream); (void)hipFree(M.p); }
+  M.p = q; M.bytes = bytes;
+  return LVX_OK;
+}
+int lvx_lidar_odometry(lvx_ctx* c, const lvx_odom_options* opt_in, const double* predict16, double* pose16, lvx_odom_step* steps, int32_t* n_key) {
+  if (!c || !pose16 || !steps) return LVX_E_ARG;
+  if (c->da_S <= 0 || (size_t)c->da_H * c->da_W == 0) return fail(c, LVX_E_STATE, "lvx_set_scans has not been called");
+  lvx_odom_options o; lvx_odom_default_options(&o); if (opt_in) o = *opt_in;
+  if (!(o.ndt_resolution > 0) || !(o.downsample_leaf > 0)) return fail(c, LVX_E_ARG, "lvx_lidar_odometry: ndt_resolution and downsample_leaf must be positive");
+  if (o.ndt.search != 1 && o.ndt.search != 7 && o.ndt.search != 26) return fail(c, LVX_E_ARG, "lvx_lidar_odometry: search must be 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
+  const int S = c->da_S;
+  const size_t HWs = (size_t)c->da_H * c->da_W;
+  if (HWs > 2147483647ull) return fail(c, LVX_E_ARG, "too many points in one scan");
+  const int HW = (int)HWs;
+  LVX_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  int rc;
+  if ((rc = dev_alloc(c, c->d_od[0], HWs * 16))) return rc;
+  if ((rc = dev_alloc(c, c->d_od[1], HWs * 16))) return rc;
+  float4* d_scan = (float4*)c->d_od[0].p; float4* d_src = (float4*)c->d_od[1].p;
+  const PointXYZIT* raw = (const PointXYZIT*)c->d_da[0].p;
+  c->od_map_n = 0;
+  if (n_key) *n_key = 0;
+  int keys = 0;
+  KeyScanRule rule(o.key_dist, o.key_angle_deg);
+  for (int k = 0; k < S; ++k) {
+    lvx_odom_step& R = steps[k];
+    std::memset(&R, 0, sizeof(R));
+    double* T = pose16 + 16 * (size_t)k;
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      hipLaunchKernelGGL(k_xyzit_to_xyzi, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, raw + (size_t)k * HW, HW, d_scan); }
+    if (c->od_map_n == 0) {   // :56-57: nothing to register against, the pose stays the identity
+      for (int e = 0; e < 16; ++e) T[e] = (e % 5 == 0) ? 1.0 : 0.0;
+      R.converged = 1;
+    } else {
+      if ((rc = ndt_target_check(c))) return rc;   // a map without a leaf is no target
+      const double* L = T - 16;
+      float guess[16];
+      for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) {   // :59 T_LtoM_predict = pose[k-1] * predict[k] in double, :84 cast to float
+        double v = L[4 * i + j];
+        if (predict16) { const double* P = predict16 + 16 * (size_t)k; v = L[4 * i] * P[j] + L[4 * i + 1] * P[4 + j] + L[4 * i + 2] * P[8 + j] + L[4 * i + 3] * P[12 + j]; }
+        guess[4 * i + j] = (float)v;
+      }
+      int n_src = 0;
+      if ((rc = downsample_device(c, d_scan, HW, o.downsample_leaf, d_src, &n_src))) return rc;   // :81
+      lvx_ndt_result res;
+      if ((rc = ndt_align_device(c, n_src, d_src, guess, o.ndt, &res))) return rc;                 // :83-84; an empty source leaves the guess (PCL refuses an empty input)
+      for (int e = 0; e < 16; ++e) T[e] = (double)res.final_transformation[e];                      // :86
+      R.n_src = n_src; R.iterations = res.iterations; R.converged = res.converged; R.n_evaluations = res.n_evaluations;
+      R.score = res.score; R.trans_probability = res.trans_probability;
+      for (int e = 0; e < 6; ++e) R.p6[e] = res.p6[e];
+    }
+    if (!rule.check(T)) continue;
+    // updateKeyScan (:89-105): the whole scan under its pose joins the map, the target is rebuilt over the whole map
+    if (((size_t)keys + 1) * HWs > 2147483647ull) return fail(c, LVX_E_ARG, "too many key-scan points for one map cloud");
+    if ((rc = odom_map_reserve(c, ((size_t)keys + 1) * HWs))) return rc;
+    Pose16 P; for (int e = 0; e < 16; ++e) P.m[e] = T[e];
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      hipLaunchKernelGGL(k_transform_append, dim3((unsigned)((HW + 255) / 256)), dim3(256), 0, st, (const float4*)d_scan, HW, P, (float4*)c->d_od[2].p + c->od_map_n); }
+    LVX_HIP(c, hipGetLastError());
+    c->od_map_n += HW; ++keys;
+    R.is_key = 1;
+    if (n_key) *n_key = keys;
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      if ((rc = voxel_build_device(c, (const float4*)c->d_od[2].p, (int)c->od_map_n, o.ndt_resolution, o.min_points_per_voxel, o.min_covar_eigvalue_mult))) return rc; }
+  }
+  return LVX_OK;
+}
+int lvx_odometry_get_map(lvx_ctx* c, int64_t max_points, float* xyzi4, int64_t* n_points) {
+  if (!c || max_points < 0 || (max_points > 0 && !xyzi4)) return LVX_E_ARG;
+  if (c->od_map_n < 0) return fail(c, LVX_E_STATE, "lvx_lidar_odometry has not been called");
+  if (n_points) *n_points = c->od_map_n;
+  const size_t take = (size_t)std::min<int64_t>(max_points, c->od_map_n);
+  if (!take) return LVX_OK;
+  LVX_HIP(c, hipSetDevice(c->device));
+  LVX_HIP(c, hipMemcpyAsync(xyzi4, c->d_od[2].p, take * 16, hipMemcpyDeviceToHost, c->stream));
+  LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
 }
 

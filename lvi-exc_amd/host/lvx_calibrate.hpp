@@ -14,8 +14,11 @@
 // map, surfel map, association), so a recorded dataset starts from the reference's initial state (identity rotations, zero positions) with nothing hand-fitted.
 // CalibrateOptions::init_lidar_rotation adds Initialization()'s EstimateRotation loop (calib_helper_lvi.cpp:55-89) after Solve #0: the LiDAR mounting rotation itself then
 // starts from the odometry (lvx_estimate_rotation), e.g. for a LiDAR turned 90 degrees against the IMU, which the surfel stage alone does not recover from identity.
-// Not mirrored: LiDAROdometry's own NDT scan-to-map registration (using_loam = false; lvx_ndt_align is its align()).
+// CalibrateOptions::lidar_odometry: without a pose file (CalibrateInput::loam empty) the odometry poses are LiDAROdometry's own NDT scan-to-map registration
+// (using_loam = false: lvx_lidar_odometry over the raw scans, as CalibrHelperLVI::Initialization feeds them, calib_helper_lvi.cpp:55-60); the first map and the rotation
+// initialisation then take their poses from it (RunLidarOdometry).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -44,7 +47,8 @@ struct CalibrateInput {
 };
 struct CalibrateOptions {
   bool solve0_so3_from_gyro = false;     // Initialization()
-  bool init_lidar_rotation = false;      // Initialization()'s EstimateRotation loop after Solve #0 (calib_helper_lvi.cpp:55-89), when LOAM poses are present: q_LtoI from the odometry (lvx_estimate_rotation)
+  bool init_lidar_rotation = false;      // Initialization()'s EstimateRotation loop after Solve #0 (calib_helper_lvi.cpp:55-89), when odometry poses are present: q_LtoI from the odometry (lvx_estimate_rotation)
+  bool lidar_odometry = false;           // no CalibrateInput::loam: the odometry poses come from lvx_lidar_odometry over the scans (feedScan with using_loam = false)
   int refine_iterations = 2;             // DataAssociation + trajInitFromSurfel rounds (the reference runs batch + 2 refinements)
   bool lvi_stage = true;                 // trajInitFromLVIdata
   bool camera_surfel_stage = false;      // the third stage with camera-landmark-to-surfel blocks
@@ -207,6 +211,25 @@ inline void QuaternionOfPose(const double T[16], double q[4]) {
   }
 }
 
+// ---- LiDAR odometry (lvx_lidar_odometry): LiDAROdometry::feedScan(using_loam = false) over the scans of lvx_set_scans, the poses in the form ReadPoseGT returns ----
+// `loam.all`: one pose per scan under its header stamp ((int64_t)(stamp * 1e9), what PoseOfScan looks up), q = Eigen's Quaternion(Matrix3d) of the pose; `loam.key`: the
+// key scans; pose16 [n][16] row-major scan -> map and the step records as the call wrote them
+struct LidarOdometry { LoamPoses loam; std::vector<double> pose16; std::vector<lvx_odom_step> steps; int32_t n_key = 0; };
+inline LidarOdometry RunLidarOdometry(lvx_ctx* ctx, const std::vector<double>& scan_stamps, const lvx_odom_options* opt = nullptr) {
+  LidarOdometry r;
+  const size_t n = scan_stamps.size();
+  if (n == 0) return r;
+  r.pose16.assign(16 * n, 0.0); r.steps.assign(n, lvx_odom_step{});
+  ThrowOnError(ctx, lvx_lidar_odometry(ctx, opt, nullptr, r.pose16.data(), r.steps.data(), &r.n_key));
+  for (size_t s = 0; s < n; ++s) {
+    const double* T = &r.pose16[16 * s];
+    double q[4]; QuaternionOfPose(T, q);
+    const PoseStamped ps{(int64_t)(scan_stamps[s] * 1e9), {T[3], T[7], T[11]}, {q[3], q[0], q[1], q[2]}};
+    r.loam.all.push_back(ps);
+    if (r.steps[s].is_key) r.loam.key.push_back(ps);
+  }
+  return r;
+}
 
 class Calibrator {
  public:
@@ -234,9 +257,11 @@ class Calibrator {
     if ((int)state->size() != lvx_state_size(ctx_)) throw std::invalid_argument("state size does not match the problem");
     std::vector<StageReport> rep;
     if (opt_.solve0_so3_from_gyro) rep.push_back(Solve0(state));
-    if (opt_.init_lidar_rotation && !in_.loam.all.empty()) rep.push_back(InitializeRotation(state));
+    if (opt_.lidar_odometry && in_.loam.all.empty() && !in_.scans.empty()) EnsureOdometry();
+    const bool have_poses = !in_.loam.all.empty() || !odom_.pose16.empty();
+    if (opt_.init_lidar_rotation && have_poses) rep.push_back(InitializeRotation(state));
     for (int it = 0; it < opt_.refine_iterations; ++it) {
-      if (it == 0 && !in_.loam.all.empty()) FirstDataAssociation(*state); else
+      if (it == 0 && have_poses) FirstDataAssociation(*state); else
       DataAssociation(*state);
       rep.push_back(SolveSurfel(state, it == 0 ? "BatchOptimization" : "Refinement"));
     }
@@ -371,6 +396,7 @@ class Calibrator {
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }
   const std::vector<int32_t>& key_scans() const { return key_scans_; }   // of the first-map association: 1 where the scan joined the key-scan map
+  const LidarOdometry& odometry() const { return odom_; }                // CalibrateOptions::lidar_odometry: what RunLidarOdometry returned (empty before Run)
   lvx_ctx* context() { return ctx_; }
 
  private:
@@ -387,7 +413,20 @@ class Calibrator {
     check(lvx_set_orientation_prior(ctx_, 0, in_.t0, q0, opt_.w_gyro));
     return r;
   }
-  bool pose_of_scan(int idx, double scan_t, double T[16]) const { return PoseOfScan(in_.loam, in_.simulation, idx, scan_t, T); }
+  // the scans' odometry poses from lvx_lidar_odometry, once (the scans do not change)
+  void EnsureOdometry() {
+    if (!odom_.pose16.empty()) return;
+    if (in_.scan_stamps.size() != in_.scans.size()) throw std::invalid_argument("scan_stamps: one header stamp per scan is needed for the LiDAR odometry");
+    lvx_odom_options oo; lvx_odom_default_options(&oo);
+    oo.ndt_resolution = opt_.ndt_resolution; oo.key_dist = opt_.key_scan_dist; oo.key_angle_deg = opt_.key_scan_angle_deg;
+    odom_ = RunLidarOdometry(ctx_, in_.scan_stamps, &oo);
+    if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] LiDAR odometry: %zu scans, %d key scans\n", in_.scans.size(), (int)odom_.n_key);
+  }
+  // a scan's odometry pose: the pose file's (PoseOfScan), or — without one — the 4 x 4 lvx_lidar_odometry wrote for it, as it is
+  bool pose_of_scan(int idx, double scan_t, double T[16]) const {
+    if (in_.loam.all.empty() && !odom_.pose16.empty()) { std::copy(odom_.pose16.begin() + 16 * (size_t)idx, odom_.pose16.begin() + 16 * (size_t)idx + 16, T); return true; }
+    return PoseOfScan(in_.loam, in_.simulation, idx, scan_t, T);
+  }
   // Initialization()'s loop (calib_helper_lvi.cpp:55-89) on the odometry poses of the scans (the poses PoseOfScan selects; a scan without one is left out): the first
   // prefix of the schedule that passes sets q_LtoI = conj(q_ItoS); none: the reference's "[Initialization] fails"
   StageReport InitializeRotation(std::vector<double>* state) {
@@ -551,6 +590,7 @@ class Calibrator {
   std::vector<double> hist_cost_, hist_radius_, stage_state_in_; std::vector<int32_t> hist_acc_;
   std::vector<lvx_surfel_plane> planes_;
   std::vector<int32_t> key_scans_;
+  LidarOdometry odom_;
   std::vector<double> sp_pt_, sp_map_, sp_t_; std::vector<int32_t> sp_plane_;
   int n_surfel_used_ = 0;
   lvx_error_stats stats_before_{}, stats_after_{};

@@ -838,6 +838,7 @@ def set_scans(ctx, raw, H, W):
     raw = np.ascontiguousarray(raw, dtype=POINT_XYZIT)
     assert raw.size % (H * W) == 0
     ctx._ck(ctx._l.lvx_set_scans(ctx._h, C.c_int(raw.size // (H * W)), C.c_int(H), C.c_int(W), _p(raw)))
+    ctx._n_scans = raw.size // (H * W)
 
 
 def data_association(ctx, state, map_time, options=None):
@@ -882,6 +883,56 @@ def get_scans_in_map(ctx, n_scans, H, W):
     out = np.zeros((n_scans, H, W, 4), np.float32)
     ctx._ck(ctx._l.lvx_get_scans_in_map(ctx._h, _p(out)))
     return out
+
+
+def voxelgrid_downsample(ctx, xyzi, leaf):
+    """pcl::VoxelGrid centroid filter of an unorganised cloud (lvx_voxelgrid_downsample): one xyzi point per occupied voxel, in voxel-index order; points with a
+    non-finite coordinate are left out."""
+    xyzi = np.ascontiguousarray(xyzi, dtype=np.float32).reshape(-1, 4)
+    out = np.zeros((max(len(xyzi), 1), 4), np.float32)
+    n = C.c_int32(0)
+    ctx._ck(ctx._l.lvx_voxelgrid_downsample(ctx._h, C.c_int(len(xyzi)), _p(xyzi), C.c_float(leaf), C.c_int64(len(xyzi)), _p(out), C.byref(n)))
+    return out[:n.value]
+
+
+class OdomOptions(C.Structure):
+    """lvx_odom_options (include/lvx.h): LiDAROdometry's parameters."""
+    _fields_ = [("ndt_resolution", C.c_float), ("downsample_leaf", C.c_float), ("key_dist", C.c_double), ("key_angle_deg", C.c_double), ("ndt", NdtOptions),
+                ("min_points_per_voxel", C.c_int32), ("reserved", C.c_int32), ("min_covar_eigvalue_mult", C.c_double)]
+
+
+ODOM_STEP_DTYPE = np.dtype([("n_src", "<i4"), ("is_key", "<i4"), ("iterations", "<i4"), ("converged", "<i4"), ("n_evaluations", "<i4"), ("reserved", "<i4"),
+                            ("score", "<f8"), ("trans_probability", "<f8"), ("p6", "<f8", 6)])
+assert ODOM_STEP_DTYPE.itemsize == 88
+
+
+def odom_default_options(ctx, **kw):
+    o = OdomOptions()
+    ctx._ck(ctx._l.lvx_odom_default_options(C.byref(o)))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+def lidar_odometry(ctx, predict16=None, options=None):
+    """LiDAROdometry::feedScan(using_loam = false) over the scans of set_scans (lvx_lidar_odometry): (poses [n_scans][4][4] scan -> map, step records
+    (ODOM_STEP_DTYPE), number of key scans).  The map cloud stays in the context (odometry_get_map), its voxel grid is the context's grid."""
+    n = getattr(ctx, "_n_scans", 0)   # (none set: the call reports it)
+    pr = None if predict16 is None else _d(np.asarray(predict16, dtype=np.float64).reshape(n, 16))
+    poses = np.zeros((max(n, 1), 16))
+    steps = np.zeros(max(n, 1), ODOM_STEP_DTYPE)
+    nk = C.c_int32(0)
+    ctx._ck(ctx._l.lvx_lidar_odometry(ctx._h, C.byref(options) if options is not None else None, _p(pr), _p(poses), _p(steps), C.byref(nk)))
+    return poses[:n].reshape(n, 4, 4), steps[:n], nk.value
+
+
+def odometry_get_map(ctx):
+    """The key-scan map cloud of the last lidar_odometry: xyzi [n_key * H * W][4], NaN points included."""
+    n = C.c_int64(0)
+    ctx._ck(ctx._l.lvx_odometry_get_map(ctx._h, C.c_int64(0), None, C.byref(n)))
+    out = np.zeros((max(n.value, 1), 4), np.float32)
+    ctx._ck(ctx._l.lvx_odometry_get_map(ctx._h, C.c_int64(n.value), _p(out), None))
+    return out[:n.value]
 
 
 def eval_lidar_pose(ctx, state, t):
