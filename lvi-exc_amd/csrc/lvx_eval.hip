@@ -473,8 +473,18 @@ struct GyroAcc {
 // TAU (free LiDAR time offset, the reference's opt_time_offset_ stages: trajectory_manager_lvi.cpp:159-165, sensors.h:70-85): one more global column, d r / d tau_L =
 // g_p (v_k - v_0) + g_xi0 w_0 + g_xik w_k — the pose gradients the row already has, contracted with the spline's velocity and body angular velocity at both poses —
 // and padded spans through the generic segment branch.  The locked instantiation is unchanged.
+// DEPG: the hub pseudo-position columns J[24 + b] = -g_p[b] are minus the sum of the four knot position columns J[6 j + b] = Bp_j g_p[b] (the position weights
+// sum to one), so everything they contribute to J^T J and J^T r is a fixed combination of sums the workgroup already holds: they are no panel columns
+// (k_family_mfma rebuilds their accumulator slots before the flush), and a window of THREE intervals fits three column tiles: 36 + 9 (+ 1) + 1 <= 48.
+// 64 sorted rows at ~40 per interval touch three intervals more often than two: with WS = 2 most wave batches were cut into two windows.
+// (An even panel stride of 50 with two columns per ds_write_b128 was measured on top of this: panel phase -10 %, pass -0.4 % — inside the noise — and more spill
+// scratch in the record / free-offset instantiations: not kept, docs/HISTORY.md.)
+#ifndef LVX_SURF_WS
+#define LVX_SURF_WS 3      // measurement switch (tools/build_variant.sh): 2 = two-interval windows with all 12 globals in the panel
+#endif
 template <bool TAU> struct SurfAccT {
-  enum { NK = 24, NG = 12 + (TAU ? 1 : 0), NR = 1, HUB = 0, KPK = 6, LVO = 0, WS = 2, GL = 16, SKIP_GG = 0, SECONDARY = 0, LB = 64, NCP = 36 + (TAU ? 1 : 0), USE_PRE = 1, OCC = 2, FAM = LVX_FAM_SURFEL };   // reverse-mode Jacobian: fits two wavefronts per SIMD with a few spills, and two workgroups per CU hide its latencies
+  enum { DEPG = LVX_SURF_WS >= 3 ? 3 : 0 };
+  enum { NK = 24, NG = 12 + (TAU ? 1 : 0), NR = 1, HUB = 0, KPK = 6, LVO = 0, WS = LVX_SURF_WS, GL = 16, SKIP_GG = 0, SECONDARY = 0, LB = 64, NCP = 36 + (TAU ? 1 : 0), USE_PRE = 1, OCC = 2, FAM = LVX_FAM_SURFEL };   // reverse-mode Jacobian: fits two wavefronts per SIMD with a few spills, and two workgroups per CU hide its latencies
   __device__ static constexpr int jm(int c) { return c; }
   int n; const double* t; const double* pt; const double* rowpl; const int* perm; double t_map, weight, huber;   // rowpl: the row's plane (gathered at layout time: no dependent load)
   // raw inputs of a row, loaded one batch ahead of their use: the HBM latency hides behind the previous batch's assembly
@@ -1052,9 +1062,15 @@ template <class F> struct RowOf<F, std::void_t<typename F::Row>> { using type = 
 template <class F, class = void> struct PanelMajor { static constexpr bool on = false; };
 template <class F> struct PanelMajor<F, std::enable_if_t<(F::PMAJ > 0)>> { static constexpr bool on = true; static_assert(F::WS == 1, "panel-major needs shift-free windows"); };
 
+// F::DEPG: the family's first DEPG globals equal  -sum_j (knot j, scalar LVO + b)  and are not panel columns
+template <class F, class = void> struct DepGlobals { static constexpr int n = 0; };
+template <class F> struct DepGlobals<F, std::enable_if_t<(F::DEPG > 0)>> { static constexpr int n = F::DEPG; };
+
 template <class F> struct MfmaGeom {
+  static constexpr int DEPG = DepGlobals<F>::n;
+  static constexpr int NGP = F::NG - DEPG;                   // globals that are panel columns
   static constexpr int NKL = (F::WS + 3) * F::KPK;           // knot columns of a window
-  static constexpr int NCL = NKL + F::NG + 1;                // + globals + residual
+  static constexpr int NCL = NKL + NGP + 1;                  // + globals + residual
   static constexpr int NT = (NCL + 15) / 16;                 // 16-column tiles
   static constexpr int LDP = (NT * 16) | 1;                  // odd row stride: conflict-free row writes and fragment reads
   static constexpr int PR = F::GL * F::NR;                   // panel rows
@@ -1073,7 +1089,7 @@ template <class F, int OCC, bool EXP = false>
 __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, const int* __restrict__ chunk_off, long long row0, int CR, int var_nch, const int* __restrict__ det_list) {
   using G = MfmaGeom<F>;
   constexpr int NK = F::NK, NG = F::NG, NC = F::NCP, NR = F::NR, KPK = F::KPK, WS = F::WS, GL = F::GL, LB = F::LB;
-  constexpr int NKL = G::NKL, NT = G::NT, LDP = G::LDP, PR = G::PR;
+  constexpr int NKL = G::NKL, NT = G::NT, LDP = G::LDP, PR = G::PR, DEPG = G::DEPG, NGP = G::NGP;
   const int ACC_LV = (CR + 5) * 6;
   extern __shared__ double sm[];
   double* acc_band = sm;                              // [ACC_LV][ACC_BW]
@@ -1127,7 +1143,7 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
   double* P = panels + wv * (PR * LDP);
   const int rep = ch % cm.nrep;
   // class of a window-local column: >= 0 knot scalar (offset inside the window, in units of tangent scalars), -1-g global g, -100 residual, -200 padding
-  auto cls = [](int lc) { return lc < NKL ? 6 * (lc / KPK) + F::LVO + lc % KPK : (lc < NKL + NG ? -1 - (lc - NKL) : (lc == NKL + NG ? -100 : -200)); };
+  auto cls = [](int lc) { return lc < NKL ? 6 * (lc / KPK) + F::LVO + lc % KPK : (lc < NKL + NGP ? -1 - (DEPG + lc - NKL) : (lc == NKL + NGP ? -100 : -200)); };
   const int frag_off = (lane >> 4) * LDP + (lane & 15);
   double mycost = 0.0;
   // panel-major families: where accumulator register (tile pair t, v) of THIS lane goes at the end of a window — LDS index (doubles, relative
@@ -1224,8 +1240,8 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
 #pragma unroll
             for (int c = 0; c < NK; ++c) prow[c] = valid ? J[a][F::jm(c)] : 0.0;
 #pragma unroll
-            for (int g = 0; g < NG; ++g) prow[NKL + g] = valid ? J[a][F::jm(NK + g)] : 0.0;
-            prow[NKL + NG] = valid ? r[a] : 0.0;
+            for (int g = 0; g < NGP; ++g) prow[NKL + g] = valid ? J[a][F::jm(NK + DEPG + g)] : 0.0;
+            prow[NKL + NGP] = valid ? r[a] : 0.0;
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1320,8 +1336,8 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
 #pragma unroll
             for (int z = 0; z < (WS - 1) * KPK; ++z) prow[z < sh ? z : z + NK] = 0.0;
 #pragma unroll
-            for (int g = 0; g < NG; ++g) prow[NKL + g] = mrow ? J[a][F::jm(NK + g)] : 0.0;
-            prow[NKL + NG] = mrow ? r[a] : 0.0;
+            for (int g = 0; g < NGP; ++g) prow[NKL + g] = mrow ? J[a][F::jm(NK + DEPG + g)] : 0.0;
+            prow[NKL + NGP] = mrow ? r[a] : 0.0;
           }
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1397,7 +1413,7 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
     if (pa == LVX_DEAD || pb == LVX_DEAD) continue;
     add_H(cm, pa, pb, v, rep);
   }
-  for (int g = 0; g < NG; ++g)
+  for (int g = DEPG; g < NG; ++g)
     for (int e = tid; e < LVU; e += 256) {
       const double v = acc_bd[g * ACC_LV + e];
       if (v == 0.0) continue;
@@ -1407,13 +1423,64 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
     }
   for (int e = tid; e < NG * NG; e += 256) {
     const int ga = e / NG, gb2 = e % NG;
-    if (gb2 < ga) continue;
+    if (gb2 < ga || ga < DEPG) continue;
     const double v = acc_gg[e];
     if (v == 0.0 || gpos[ga] == LVX_DEAD || gpos[gb2] == LVX_DEAD) continue;
     add_H(cm, gpos[ga], gpos[gb2], v, rep);
   }
   for (int e = tid; e < LVU; e += 256) { const double v = acc_gk[e]; if (v != 0.0 && kpos[e] != LVX_DEAD) add_g(cm, kpos[e], v, rep); }
-  if (tid < NG) { const double v = acc_gG[tid]; if (v != 0.0 && gpos[tid] != LVX_DEAD) add_g(cm, gpos[tid], v, rep); }
+  if (tid >= DEPG && tid < NG) { const double v = acc_gG[tid]; if (v != 0.0 && gpos[tid] != LVX_DEAD) add_g(cm, gpos[tid], v, rep); }
+  if constexpr (DEPG > 0) {
+    // the dependent globals' slots were never accumulated: each is minus a sum over the chunk's knots kappa of entries the workgroup holds (b, b' < DEPG),
+    //   gG[b] = -sum gk[6 kappa + b],  bd[b][la] = -sum Hsym[6 kappa + b][la] (the band read symmetrically; zero beyond its width),
+    //   gg[b][g] = -sum bd[g][6 kappa + b] for a panel global g — and, behind a barrier, gg[b][b'] = -sum bd[b][6 kappa + b'] from the rebuilt rows.
+    // The thread that owns an output sums it in ascending kappa and adds it to HBM itself: no LDS atomics, the same bits on every run.  (Huber scales whole
+    // rows, fallback rows reach neither side.)  The loads of a sum are issued together — one load -> add chain per knot is 21 LDS latencies in a row — and the
+    // sums stand BEHIND the flush above, whose atomics are in flight meanwhile (measured: sums first, barrier, then the whole flush gives half the gain).
+    const int nkn = LVU / 6;
+    auto ksum = [nkn](const double* src) {   // -sum over kappa of src[6 kappa]
+      double s = 0.0;
+      for (int k0 = 0; k0 < nkn; k0 += 8) {
+        double v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = src[6 * min(k0 + j, nkn - 1)];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s += k0 + j < nkn ? v[j] : 0.0;
+      }
+      return -s;
+    };
+    for (int e = tid; e < DEPG * LVU; e += 256) {
+      const int b = e / LVU, la = e % LVU;
+      double v[9];   // the knots whose scalar b lies within the band of la
+#pragma unroll
+      for (int j = 0; j < 9; ++j) {
+        const int kk = la / 6 - 4 + j, c = 6 * kk + F::LVO + b, lo = min(c, la), d = max(c, la) - lo;
+        const bool ok = kk >= 0 && kk < nkn && d < ACC_BW;
+        v[j] = ok ? acc_band[ok ? lo * ACC_BW + d : 0] : 0.0;
+      }
+      double s = 0.0;
+#pragma unroll
+      for (int j = 0; j < 9; ++j) s += v[j];
+      acc_bd[b * ACC_LV + la] = -s;   // kept: gg[b][b'] sums these
+      if (s != 0.0 && gpos[b] != LVX_DEAD && kpos[la] != LVX_DEAD) add_H(cm, gpos[b], kpos[la], -s, rep);
+    }
+    const int q = 255 - tid;          // the long sums go to the threads with the fewest entries above
+    if (q < DEPG * NGP) {
+      const int b = q / NGP, g = DEPG + q % NGP;
+      const double v = ksum(acc_bd + g * ACC_LV + F::LVO + b);
+      if (v != 0.0 && gpos[b] != LVX_DEAD && gpos[g] != LVX_DEAD) add_H(cm, gpos[b], gpos[g], v, rep);
+    } else if (q < DEPG * NGP + DEPG) {
+      const int b = q - DEPG * NGP;
+      const double v = ksum(acc_gk + F::LVO + b);
+      if (v != 0.0 && gpos[b] != LVX_DEAD) add_g(cm, gpos[b], v, rep);
+    }
+    __syncthreads();
+    if (tid < DEPG * DEPG && tid % DEPG >= tid / DEPG) {
+      const int b = tid / DEPG, b2 = tid % DEPG;
+      const double v = ksum(acc_bd + b * ACC_LV + F::LVO + b2);
+      if (v != 0.0 && gpos[b] != LVX_DEAD && gpos[b2] != LVX_DEAD) add_H(cm, gpos[b], gpos[b2], v, rep);
+    }
+  }
 #ifdef LVX_KTIME
   KT(7)
 #ifndef LVX_KTIME_FAM

@@ -8,7 +8,8 @@ python build.py > /dev/null
 CONTRACT=fast; [ "$FILE" = "lvx_upstream" ] && CONTRACT=off
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-gpu-rdc -Wno-unused-result -ffp-contract=$CONTRACT $DEFS -c csrc/$FILE.hip -o /tmp/${FILE}_var_$TAG.o
 OBJS=""
-for f in lvx_api lvx_bcr lvx_eval lvx_solver lvx_upstream; do
+for s in csrc/*.hip; do
+  f=$(basename "$s" .hip)
   if [ "$f" = "$FILE" ]; then OBJS="$OBJS /tmp/${FILE}_var_$TAG.o"; else OBJS="$OBJS csrc/$f.o"; fi
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o liblvx_var_$TAG.so $OBJS -ldl -Wl,-rpath,/opt/rocm/lib
