@@ -104,6 +104,13 @@ typedef struct lvx_layout {
   int32_t solver_separators; /* the last solver plan: separators of the leaves + separators elimination of the band (a band that is narrow except for isolated wide runs:
                               * csrc/lvx_nd.h); 0: the uniform block chain (block cyclic reduction with b = bandwidth) runs */
   int32_t solver_leaves;     /* ... and its leaves (narrow stretches and wide runs) */
+  int32_t rep_groups;        /* (reference window, observation window) groups of the reprojection cross-term kernel in the current layout (at most 32 blocks each) */
+  int32_t lm_groups;         /* groups of the landmark elimination (at most 32 landmarks whose first band positions lie within 24 scalars) */
+  int32_t lm_group_spread;   /* ... the largest distance between the first band positions of two landmarks of one group */
+  int32_t lm_row_width;      /* band scalars a landmark row covers (the widest landmark's reach; 1 when no landmark touches the band) */
+  int32_t lm_elim_kernel;    /* the landmark elimination of the last lvx_solve_step / LM iteration: 0 none, 1 by groups (k_lm_schur_grp), 2 one workgroup per landmark
+                              * (k_lm_schur: the group panel does not fit the LDS, or the test switch TEST_LM_SCHUR_ONE) */
+  int32_t rep_colours;       /* DETERMINISTIC only: launches the cross-term groups are spread over so that no two groups of a launch add to the same entry (0 otherwise) */
 } lvx_layout;
 
 /* lifetime ------------------------------------------------------------------------------------------------*/

@@ -20,6 +20,7 @@ const SwitchName* switch_table(int* count) {
     {"DA_SYNC", &Switches::da_sync, false},   // lvx_data_association: always the synchronous chain (four host stops), never the speculative one
     {"TEST_BAD_PIVOT", &Switches::test_bad_pivot, false},   // lvx_solve_step: declare a pivot failure where there was none (the tests' way into the sequential redo)
     {"TEST_COMPACT_ONE", &Switches::test_compact_one, false},   // surfel_compact_launch: k_surfel_compact (one workgroup) whatever the co-residency bound says
+    {"TEST_LM_SCHUR_ONE", &Switches::test_lm_schur_one, false},   // solve_local: k_lm_schur (one workgroup per landmark) whatever the LDS size of the group panel says
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;
@@ -217,6 +218,8 @@ int lvx_get_layout(lvx_ctx* c, lvx_layout* o) {
   o->n_hub_knots = c->n_hub; o->hub_knot0 = c->hub0; o->n_blocks = c->n_blocks; o->n_residuals = c->n_residuals;
   o->exact_fallback = c->force_legacy ? 1 : 0; o->solver_fallbacks = c->solver_fallbacks; o->fallback_rows = c->fallback_rows;
   nd_counts(c, &o->solver_separators, &o->solver_leaves);
+  o->rep_groups = c->rep_groups; o->lm_groups = c->lm_ngrp; o->lm_group_spread = c->lm_gspread; o->lm_row_width = c->lm_wl; o->lm_elim_kernel = c->lm_elim_kernel;
+  o->rep_colours = c->det_cross_col.empty() ? 0 : (int)c->det_cross_col.size() - 1;
   return LVX_OK;
 }
 

@@ -786,7 +786,9 @@ static int leave_together(lvx_ctx* c, double votes, int lerr) {
 static int solver_alloc(lvx_ctx* c, SolveWork& w, bool will_inplace = false) {
   int rc;
   const size_t nb = (size_t)std::max(c->nb, 1), nbd = c->nbd, nt = (size_t)lvx_tangent_size(c);
-  const bool use_bcr = !c->sw.solver_seq;
+  // the block chain's batched triangular solves stop at blocks of 256 (trsv_batched): a wider band — a free landmark tracked over more than ~42 knots writes fill across
+  // its whole reach — goes to the sequential band Cholesky, whose panel holds half-bandwidths up to ~1 100.  (Until the landmark-track tests such a problem ended in LVX_E_ARG.)
+  const bool use_bcr = !c->sw.solver_seq && ((c->bw + 3) / 4) * 4 <= 256;
   size_t ldz = nb;
   if (use_bcr && c->nb > 0) {
     if ((rc = nd_plan(c, (int)nbd + 1))) return rc;      // leaves + separators elimination when the band's column profile allows it (lvx_nd.h), the uniform chain otherwise
@@ -802,6 +804,7 @@ static int solver_alloc(lvx_ctx* c, SolveWork& w, bool will_inplace = false) {
   const size_t nall = nb + nbd + (size_t)std::max(c->L, 0);
   if ((rc = dev_alloc(c, c->d_diag, 3 * nall * 8))) return rc;
   w.lm = c->L > 0 && c->rep.n > 0 && !(c->locks & LVX_LOCK_LANDMARKS);
+  if (!w.lm) c->lm_elim_kernel = 0;
   w.Hs = (const double*)c->d_Hb.p; w.Bs = (const double*)c->d_Bd.p; w.Cs = (const double*)c->d_C.p; w.gbs = (const double*)c->d_gb.p; w.gcs = (const double*)c->d_gc.p;
   if (w.lm) {
     const size_t ldc = c->nbd_ext;
@@ -866,11 +869,13 @@ static int solve_local(lvx_ctx* c, SolveWork& w, double radius, bool force_seq, 
     sums_cleared = true;
     const int ne_max = c->lm_wl + c->lm_gspread + c->nbd_ext;
     const size_t lds_g = (size_t)32 * (ne_max + 1) * 8 + 32 * 8 + (size_t)2 * ne_max * 4 + 16;
-    if (c->lm_ngrp > 0 && lds_g <= 160 * 1024) {
+    if (c->lm_ngrp > 0 && lds_g <= 160 * 1024 && !c->sw.test_lm_schur_one) {   // (switch TEST_LM_SCHUR_ONE: the tests' way into the per-landmark kernel on small problems)
+      c->lm_elim_kernel = 1;
       LVX_HIP(c, hipFuncSetAttribute((const void*)k_lm_schur_grp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g));
       hipLaunchKernelGGL(k_lm_schur_grp, dim3((unsigned)c->lm_ngrp), dim3(256), lds_g, st, (const double*)c->d_lmH.p, (const int*)c->d_lm_p0.p, (const int*)c->d_lm_grp.p, c->lm_ngrp, c->lm_wl, c->nbd_ext, c->lm_ls,
                          w.scale + (nb + nbd), w.lmd + (nb + nbd), ir, ne_max, (double*)w.Hs, bw, (double*)w.Bs, nb, (double*)w.Cs, c->nbd_ext, (double*)w.gbs, (double*)w.gcs, w.tk ? w.tk + 5 : nullptr);
     } else {
+    c->lm_elim_kernel = 2;
     const size_t lds = (size_t)(c->lm_wl + c->nbd_ext + 2) * 8 + (size_t)(c->lm_wl + c->nbd_ext) * 4 + 16;
     LVX_HIP(c, hipFuncSetAttribute((const void*)k_lm_schur, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_lm_schur, dim3((unsigned)c->L), dim3(256), lds, st, (const double*)c->d_lmH.p, (const int*)c->d_lm_p0.p, c->lm_wl, c->nbd_ext, c->lm_ls, w.scale + (nb + nbd), w.lmd + (nb + nbd), ir,

@@ -71,7 +71,8 @@ FAMILY_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf"]
 class Layout(C.Structure):
     _fields_ = [("n_knots", C.c_int32), ("n_landmarks", C.c_int32), ("n_tangent", C.c_int32), ("n_band", C.c_int32),
                 ("bandwidth", C.c_int32), ("n_border", C.c_int32), ("border_ld", C.c_int32), ("n_hub_knots", C.c_int32), ("hub_knot0", C.c_int32),
-                ("n_blocks", C.c_int64), ("n_residuals", C.c_int64), ("exact_fallback", C.c_int32), ("solver_fallbacks", C.c_int32), ("fallback_rows", C.c_int32), ("solver_separators", C.c_int32), ("solver_leaves", C.c_int32)]
+                ("n_blocks", C.c_int64), ("n_residuals", C.c_int64), ("exact_fallback", C.c_int32), ("solver_fallbacks", C.c_int32), ("fallback_rows", C.c_int32), ("solver_separators", C.c_int32), ("solver_leaves", C.c_int32),
+                ("rep_groups", C.c_int32), ("lm_groups", C.c_int32), ("lm_group_spread", C.c_int32), ("lm_row_width", C.c_int32), ("lm_elim_kernel", C.c_int32), ("rep_colours", C.c_int32)]
 
 
 class LmOptions(C.Structure):

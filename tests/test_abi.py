@@ -31,6 +31,33 @@ def test_every_declared_symbol_is_exported(liblvx):
     assert not missing, missing
 
 
+LAYOUT_FIELDS = [("n_knots", 4), ("n_landmarks", 4), ("n_tangent", 4), ("n_band", 4), ("bandwidth", 4), ("n_border", 4), ("border_ld", 4), ("n_hub_knots", 4), ("hub_knot0", 4),
+                 ("n_blocks", 8), ("n_residuals", 8), ("exact_fallback", 4), ("solver_fallbacks", 4), ("fallback_rows", 4), ("solver_separators", 4), ("solver_leaves", 4),
+                 # appended for the landmark-track tests: which plan the last layout / the last solve took.  Fields are only ever added at the end.
+                 ("rep_groups", 4), ("lm_groups", 4), ("lm_group_spread", 4), ("lm_row_width", 4), ("lm_elim_kernel", 4), ("rep_colours", 4)]
+
+
+def test_layout_struct_matches_the_header():
+    """lvx_layout of include/lvx.h, field by field, against the ctypes mirror lvx.Layout and the table above: names, order, widths, offsets (no earlier field moves when the struct
+    grows) and the total size."""
+    import lvx
+    src = open(os.path.join(ROOT, "include", "lvx.h")).read()
+    body = re.search(r"typedef struct lvx_layout \{(.*?)\} lvx_layout;", src, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    decl = []
+    for typ, names in re.findall(r"\b(int32_t|int64_t)\s+([^;]+);", body):
+        decl += [(n.strip(), 4 if typ == "int32_t" else 8) for n in names.split(",")]
+    assert decl == LAYOUT_FIELDS
+    assert [(n, C.sizeof(t)) for n, t in lvx.Layout._fields_] == LAYOUT_FIELDS
+    off = 0
+    for name, width in LAYOUT_FIELDS:
+        off = (off + width - 1) // width * width
+        assert getattr(lvx.Layout, name).offset == off, name
+        off += width
+    assert lvx.Layout.n_blocks.offset == 40 and lvx.Layout.solver_leaves.offset == 72 and lvx.Layout.rep_groups.offset == 76
+    assert C.sizeof(lvx.Layout) == 104      # 100 bytes of fields, padded to the alignment of the int64 members
+
+
 def test_no_device_means_error_not_fallback(liblvx):
     import torch
     if torch.cuda.is_available():
