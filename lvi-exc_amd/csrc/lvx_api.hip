@@ -17,6 +17,7 @@ const SwitchName* switch_table(int* count) {
     {"FORCE_LEGACY", &Switches::force_legacy, false}, {"SERIAL", &Switches::serial, false}, {"NO_GRAPH", &Switches::no_graph, false}, {"DETERMINISTIC", &Switches::deterministic, true},
     {"CLEAR_ALL", &Switches::clear_all, false}, {"SOLVER_SEQ", &Switches::solver_seq, false}, {"SOLVER_TIMING", &Switches::solver_timing, false},
     {"CHUNK_R", &Switches::chunk_r, true}, {"CHUNK_R_IMU", &Switches::chunk_r_imu, true}, {"CHUNK_R_REP", &Switches::chunk_r_rep, true}, {"CHUNK_ROWS", &Switches::chunk_rows, true}, {"REP_ROWS", &Switches::rep_rows, true}, {"REP_FUSED", &Switches::rep_fused, true}, {"SOLVER_ND", &Switches::solver_nd, false},
+    {"IMU_FIXED_SLICES", &Switches::imu_fixed_slices, true},   // k_imu_own: wavefront w takes samples [64 w, 64 w + 64) of a batch (the schedule before the window-balanced slices)
     {"DA_SYNC", &Switches::da_sync, false},   // lvx_data_association: always the synchronous chain (four host stops), never the speculative one
     {"TEST_BAD_PIVOT", &Switches::test_bad_pivot, false},   // lvx_solve_step: declare a pivot failure where there was none (the tests' way into the sequential redo)
     {"TEST_COMPACT_ONE", &Switches::test_compact_one, false},   // surfel_compact_launch: k_surfel_compact (one workgroup) whatever the co-residency bound says

@@ -67,7 +67,7 @@ struct DevBuf {
 // Experiment / debug switches: read ONCE from the environment (LVX_<NAME>) when the context is created and changed afterwards only
 // through lvx_set_switch — the evaluation and solve paths never call getenv.
 struct Switches {
-  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0, test_bad_pivot = 0, test_compact_one = 0, test_lm_schur_one = 0;   // test_lm_schur_one: the tests' way into k_lm_schur (one workgroup per landmark) on problems whose group panel fits the LDS; test_compact_one: the tests' way into k_surfel_compact (the single-workgroup plane compaction) on a device whose co-residency bound no test map exceeds; test_bad_pivot: the tests' way into the solver's failed-pivot branch (a failure is declared where there was none); rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
+  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0, test_bad_pivot = 0, test_compact_one = 0, test_lm_schur_one = 0, imu_fixed_slices = 0;   // imu_fixed_slices: the wavefronts of k_imu_own take fixed 64-sample slices of a batch instead of the window-balanced ones (measurement); test_lm_schur_one: the tests' way into k_lm_schur (one workgroup per landmark) on problems whose group panel fits the LDS; test_compact_one: the tests' way into k_surfel_compact (the single-workgroup plane compaction) on a device whose co-residency bound no test map exceeds; test_bad_pivot: the tests' way into the solver's failed-pivot branch (a failure is declared where there was none); rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
 };
 struct SwitchName { const char* name; int Switches::*field; bool relayout; };
 const SwitchName* switch_table(int* count);
@@ -135,7 +135,7 @@ struct lvx_ctx {
   int nrep = LVX_NREP;
   std::vector<int> h_chunk_k0[LVX_NUM_FAM], h_chunk_rows[LVX_NUM_FAM], det_col[LVX_NUM_FAM], det_cross_col;
   lvx::DevBuf d_det_list[LVX_NUM_FAM], d_det_cross, d_chk, d_imu_rtab;
-  // owner-computes IMU kernel (k_imu_own): batches [offsets | first interval], first batch of every workgroup, owner of every band column (-1: cleared + atomics)
+  // owner-computes IMU kernel (k_imu_own): batches [offsets | first interval | end | wavefront slices], [first batch | first primary sample] of every workgroup, owner of every band column (-1: cleared + atomics)
   lvx::DevBuf d_imu_chunk, d_imu_wg, d_imu_own; int imu_wg = 0, imu_nch = 0, imu_span = 0, imu_owned_cols = 0; size_t imu_own_k_off = 0; std::vector<int> imu_h_k0, imu_h_wg_c0;
   int chunk_var[LVX_NUM_FAM] = {0};   // != 0: chunks of equal ROW count (first interval of chunk c at d_chunk[n_chunk + 1 + c]) instead of equal interval count
   int n_chunk[LVX_NUM_FAM] = {0}, chunk_r[LVX_NUM_FAM] = {0};   // workgroups and knot intervals per workgroup of the MFMA assembly kernels (pick_chunk)

@@ -1534,7 +1534,9 @@ template <class PG> __device__ __forceinline__ void imu_build_rtab(int* rtab, in
       }
 }
 // rows of this wavefront's 64 lanes -> panel by panel -> windows (runs of equal knot interval) -> MFMA -> LDS accumulators
-template <class PG> __device__ __forceinline__ void imu_assemble(double* sm, double* P, const int* rtab, bool valid, int key, int k_lo, int acc_lv, const double* r, const double (*J)[PG::NCJ], int lane, int dummy) {
+// nhalo: lanes below it hold HALO samples (of the three intervals in front of the workgroup's primary range, see the schedule below); windows never mix the two kinds.
+// HALO = false: a trip without halo lanes (all but the first one or two of a workgroup) — the scatter without the halo predicate
+template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(double* sm, double* P, const int* rtab, bool valid, int key, int k_lo, int acc_lv, const double* r, const double (*J)[PG::NCJ], int lane, int dummy, int nhalo) {
   constexpr int NR = PG::NR, NT = PG::NT, LDP = PG::LDP, PR = PG::PR, GL = PG::GL;
   const unsigned long long vm = __ballot(valid);
   for (int g0 = 0; g0 < 64; g0 += GL) {
@@ -1593,16 +1595,17 @@ template <class PG> __device__ __forceinline__ void imu_assemble(double* sm, dou
       for (; ks + 6 <= nks; ks += 6) trip(ks, std::integral_constant<int, 6>{});
       for (; ks < nks; ks += 2) trip(ks, std::integral_constant<int, 2>{});
       const int wbB = wb * ACC_BW;
+      const int mlo = l0 < nhalo ? 1 : 0;   // a halo window adds to the knot-indexed accumulators (band, bd, gk: modes 2 and 1) only; gg / gG (mode 0) belong to the sample's primary workgroup
       // BRANCH-FREE scatter: every lane issues every LDS add — to its accumulator entry, or +0.0 to a dummy slot of its own when the tile position has no entry (lower
-      // triangle, padding) or lies beyond the window.  With a `continue` per slot every slot was a basic block of its own: exec-mask juggling, a branch and the 76-cycle
+      // triangle, padding), lies beyond the window or is not a halo window's to add.  With a `continue` per slot every slot was a basic block of its own: exec-mask juggling, a branch and the 76-cycle
       // wait for the MFMA result, one slot after the other (180 cycles per slot on the one wavefront per SIMD this kernel runs at).
 #pragma unroll
       for (int t = 0; t < PG::NTP; ++t)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
           const int te = rtab[t * 4 + v];
-          const bool ok = te >= 0 && wb + (te >> 18) < acc_lv;
           const int m = (te >> 16) & 3;
+          const bool ok = te >= 0 && (!HALO || m >= mlo) && wb + (te >> 18) < acc_lv;
           const int idx = ok ? (te & 0xffff) + (m == 2 ? wbB : (m == 1 ? wb : 0)) : dummy + lane;
           atomicAdd(&sm[idx], ok ? D[t][v] : 0.0);
         }
@@ -1619,13 +1622,22 @@ struct ImuFused { int n; const double* t; const double* gyro; const double* acc;
 //   * it walks its range batch by batch with the SAME LDS accumulators: the window [k_lo, k_lo + IMU_CR + 5) of knots slides with the data, the columns of the knots the
 //     next batch can no longer touch are flushed and the rest carried over — so every band column, gradient entry and IMU-calibration border entry inside the range has
 //     ONE writer, which STORES it (coalesced 16-byte stores, zeros included: these entries need no clear, k_clear reads the same ownership table);
-//   * only the 5 knots either side of a range boundary, knots next to the hub gap and knots no window covers keep the cleared-and-added-atomically protocol;
+//   * HALO samples give the knots at a range boundary one writer too.  A sample of interval i touches the knots i .. i + 3 (the evaluated interval IS the sort key:
+//     knot_lookup places the four-knot segment by t and admits t + tau_imu inside it only), so the range [P0, P1) of workgroup g and its left neighbour share P0 .. P0 + 2.
+//     Workgroup g therefore also walks the samples of the intervals [P0 - 3, P0) — its halo, the first rows of its first batch(es), primary samples of the workgroups
+//     before it — and with them sees every sample that touches a knot in [P0, P1): it owns those knots.  A halo window adds to the knot-indexed accumulators (band, bd, gk)
+//     only; cost, residuals, records, the fallback list and the sums over the IMU calibration alone (gg, gG) are done once, by the sample's primary workgroup.  What a
+//     workgroup sums into columns of another owner (halo windows into the knots below P0, its last three intervals into the knots from P1 on) is partial and dropped: the
+//     batch-end stores test the owner.  The first workgroup has no halo.  A pass without ownership or without normal equations skips the halo samples;
+//   * only knots next to the hub gap or the spline's ends, knots with landmarks ordered between them and knots no window covers keep the cleared-and-added-atomically
+//     protocol, where every workgroup adds its PRIMARY samples' sums — so a boundary whose halo windows would touch such a knot gets no halo, and its three shared knots
+//     keep that protocol as well (ensure_layout);
 //   * everything the batches look up — band positions, owners, the control-point-pair table — is loaded ONCE per workgroup for its whole knot range: between the flush
 //     stores of one batch and the row loads of the next there is no vector-memory load (a load's s_waitcnt vmcnt(0) waits for every store issued before it).
 // The kernel runs FIRST on the band (behind k_clear, before the LiDAR kernels), so the stores cannot overwrite another family's sums; every later family adds.
 #define IMU_CR 32                        // knot intervals a batch may span
 #define IMU_LV ((IMU_CR + 5) * 6)        // tangent scalars of the accumulator window (37 knots)
-struct ImuOwn { const int* wg_c0; const int* own_k; int nch, span; };   // batches of workgroup g: [wg_c0[g], wg_c0[g + 1]); own_k[knot] = the workgroup that stores the knot's six band columns (-1: nobody); span: knots of the widest workgroup range
+struct ImuOwn { const int* wg_c0; const int* own_k; int nch, span; };   // batches of workgroup g: [wg_c0[g], wg_c0[g + 1]), its first primary sample wg_c0[G + 1 + g] (the samples of its batches below that one are its halo); own_k[knot] = the workgroup that stores the knot's six band columns (-1: nobody); span: knots of the widest workgroup range
 // workgroup barrier that orders LDS traffic only: __syncthreads() also waits for the wave's outstanding global stores (vmcnt(0))
 #define LVX_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 static size_t imu_fused_lds_bytes(int span) {
@@ -1665,6 +1677,9 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
   if (c0 >= c1) return;
   const int nwv = det ? 1 : 4;
   const bool want_ne = (cm.what & LVX_EVAL_NORMAL_EQ) != 0;
+  // samples below prim0 are the workgroup's halo: walked only for the band columns it owns (a pass without ownership or without normal equations skips them)
+  const int prim0 = ow.wg_c0[gridDim.x + 1 + wg];
+  const bool use_halo = ow.own_k != nullptr && want_ne;
   constexpr int NACC = ACC_LV * ACC_BW + IMU_NGA * ACC_LV + IMU_NGA * IMU_NGA + ACC_LV + IMU_NGA;
   for (int e = tid; e < NACC; e += 256) sm[e] = 0.0;   // (the panels need no clearing: every row a k-step reads is rewritten, the padding columns with it)
   int* urng = gpos + IMU_NGA;                        // [2]: first / last accumulator row of a batch end whose columns this workgroup does not store
@@ -1697,16 +1712,21 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
 #define IKT(i)
 #endif
   for (int c = c0; c < c1; ++c) {
-    const int m0 = chunk_off[c], m1 = chunk_off[c + 1];
+    const int m0 = chunk_off[c], m1 = chunk_off[2 * ow.nch + 1 + c];   // (the next workgroup's first batch starts in front of this one's end: its halo)
     const int k_lo = chunk_off[ow.nch + 1 + c] - 1;   // window base knot of this batch
     const int woff = k_lo - k_base;
     const So3Pre* pre_tab = pre_all + woff;
     const int* kpos = kpos_all + 6 * woff;
     if (c == c0) __syncthreads(); else LVX_LDS_BARRIER();   // the tables (global loads: full barrier) / the previous batch's carry-over are in place
     IKT(0)
-    for (int base = wv < nwv ? m0 + wv * 64 : m1; base < m1; base += nwv * 64) {
+    // wavefront slices of the batch, laid out by the host with equal numbers of windows (the assembly costs per window, not per sample); DETERMINISTIC: one wavefront walks it all
+    const int* so = chunk_off + 3 * ow.nch + 1 + 5 * c;
+    const int wvu = __builtin_amdgcn_readfirstlane(wv);
+    const int b1 = nwv == 1 ? m1 : so[wvu + 1];
+    for (int base = nwv == 1 ? (wvu == 0 ? m0 : m1) : so[wvu]; base < b1; base += 64) {
       const int si = base + lane;
-      const bool in = si < m1;
+      const bool hal = si < prim0;   // halo sample: cost, residuals, records, error word and fallback list are its primary workgroup's
+      const bool in = si < b1 && (use_halo || !hal);
       int key = -1;
       bool valid = false;
       So3Eval e;
@@ -1725,10 +1745,13 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
           }
         }
         valid = status == RES_OK;
-        if (valid && (key < k_lo || key - k_lo > CR + 1)) { valid = false; fallback_row(cm, LVX_FAM_GYRO, si); }
-        else if (!valid && status == RES_OUTSIDE) fallback_row(cm, LVX_FAM_GYRO, si);   // (the sample: its gyroscope AND accelerometer block go to the exact kernels)
-        else if (!valid) atomicOr(cm.err, status);
+        if (valid && (key < k_lo || key - k_lo > CR + 1)) { valid = false; status = RES_OUTSIDE; }
+        if (!valid && !hal) {
+          if (status == RES_OUTSIDE) fallback_row(cm, LVX_FAM_GYRO, si);   // (the sample: its gyroscope AND accelerometer block go to the exact kernels)
+          else atomicOr(cm.err, status);
+        }
       }
+      const bool mine = valid && !hal;
       IKT(1)
       {   // gyroscope block (gyro_residual, lvx_resid.h)
         double r[3], J[3][GYRO_NC];
@@ -1747,12 +1770,14 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
           for (int a = 0; a < 3; ++a)
 #pragma unroll
             for (int b = 0; b < 3; ++b) J[a][12 + b] = (a == b) ? -w : 0.0;
-          mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-          if (cm.residuals) { const long long orow = row0_g + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
-          if constexpr (EXP) put_record<3, GYRO_NC>(cm, LVX_FAM_GYRO, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
+          if (mine) {
+            mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            if (cm.residuals) { const long long orow = row0_g + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
+            if constexpr (EXP) put_record<3, GYRO_NC>(cm, LVX_FAM_GYRO, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
+          }
         }
-        if constexpr (EXP) { if (in && !valid) { put_skipped(cm, LVX_FAM_GYRO, fam.perm[si]); put_skipped(cm, LVX_FAM_ACCEL, fam.perm[si]); } }
-        if (want_ne) imu_assemble<ImuG>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC);
+        if constexpr (EXP) { if (in && !valid && !hal) { put_skipped(cm, LVX_FAM_GYRO, fam.perm[si]); put_skipped(cm, LVX_FAM_ACCEL, fam.perm[si]); } }
+        if (want_ne) { if (base < prim0) imu_assemble<ImuG, true>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuG, false>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC, 0); }
         IKT(2)
       }
       {   // accelerometer block (accel_residual, lvx_resid.h)
@@ -1789,11 +1814,13 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
 #pragma unroll
             for (int bb = 0; bb < 3; ++bb) J[a][26 + bb] = (a == bb) ? -w : 0.0;
           }
-          mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-          if (cm.residuals) { const long long orow = row0_a + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
-          if constexpr (EXP) put_record<3, ACC_NC>(cm, LVX_FAM_ACCEL, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
+          if (mine) {
+            mycost += 0.5 * (r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
+            if (cm.residuals) { const long long orow = row0_a + (long long)fam.perm[si] * 3; cm.residuals[orow] = r[0]; cm.residuals[orow + 1] = r[1]; cm.residuals[orow + 2] = r[2]; }
+            if constexpr (EXP) put_record<3, ACC_NC>(cm, LVX_FAM_ACCEL, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
+          }
         }
-        if (want_ne) imu_assemble<ImuA>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC);
+        if (want_ne) { if (base < prim0) imu_assemble<ImuA, true>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuA, false>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC, 0); }
         IKT(3)
       }
     }
@@ -1803,41 +1830,40 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
     const bool more = c + 1 < c1;
     const int nfl = more ? min(ACC_LV, max(0, 6 * (chunk_off[ow.nch + 1 + c + 1] - 1 - k_lo))) : ACC_LV;
     const int* kown = kown_all + woff;   // per knot
-    const bool un_ = bt < nfl && kpos[bt] != LVX_DEAD && kown[bt / 6] != wg;
+    const bool un_ = bt < nfl && kpos[bt] != LVX_DEAD && kown[bt / 6] < 0;   // (a column ANOTHER workgroup stores holds a partial sum here — halo or range end: dropped by the stores below)
     { const unsigned long long ub = __ballot(un_);
       if (ub && lane == 0) { atomicMin(&urng[0], wv * 64 + __ffsll((long long)ub) - 1); atomicMax(&urng[1], wv * 64 + 63 - __clzll((long long)ub)); } }
     const int any_unowned = __syncthreads_or(un_);   // (the barrier: every wavefront's sums are in the LDS accumulators)
     IKT(4)
     if (any_unowned) {
-      // a range's first / last batch, the hub gap, hub knots = border rows: columns this workgroup does not store keep the cleared-and-added protocol.  Only the rows
-      // [r0, r1) between the first and the last such column are walked (a handful of knots at a range boundary; walking all 222 rows cost 17 k cycles per such batch)
+      // the hub gap, hub knots = border rows, knots with landmarks ordered between them, a range boundary without halo: columns NOBODY stores keep the cleared-and-added
+      // protocol (no halo window touches one: ensure_layout).  Only the rows [r0, r1) between the first and the last such column are walked (walking all 222 rows cost
+      // 17 k cycles per such batch); a column another workgroup stores is skipped: what this one summed into it is partial
       const int r0 = urng[0], r1 = urng[1] + 1;
       for (int e = r0 * ACC_BW + bt; e < r1 * ACC_BW; e += 256) {
         const int la = e / ACC_BW, lb = la + e % ACC_BW;
         const int pa = kpos[la], o = kown[la / 6];
-        if (o == wg || pa == LVX_DEAD || lb >= ACC_LV) continue;
+        if (o >= 0 || pa == LVX_DEAD || lb >= ACC_LV) continue;
         const double v = A.band[e];
         if (v == 0.0) continue;
-        if (o >= 0) { atomicOr(cm.err, LVX_ERR_FALLBACK); continue; }   // another workgroup STORES this column: cannot happen while |tau_imu| < dt
         const int pb = kpos[lb];
         if (pb != LVX_DEAD) add_H(cm, pa, pb, v, rep);
       }
       for (int gi = 0; gi < IMU_NGA; ++gi)
         for (int la = r0 + bt; la < r1; la += 256) {
           const int pg = gpos[gi], pa = kpos[la], o = kown[la / 6];
-          if (pg == LVX_DEAD || pa == LVX_DEAD || (o == wg && pg < 0)) continue;
+          if (pg == LVX_DEAD || pa == LVX_DEAD || (o >= 0 && (o != wg || pg < 0))) continue;
           const double v = A.bd[gi * ACC_LV + la];
-          if (v == 0.0) continue;
-          if (o >= 0) atomicOr(cm.err, LVX_ERR_FALLBACK); else add_H(cm, pg, pa, v, rep);
+          if (v != 0.0) add_H(cm, pg, pa, v, rep);
         }
-      if (bt < nfl && kpos[bt] != LVX_DEAD && kown[bt / 6] != wg) {
+      if (bt < nfl && kpos[bt] != LVX_DEAD && kown[bt / 6] < 0) {
         const double v = A.gk[bt];
-        if (v != 0.0) { if (kown[bt / 6] >= 0) atomicOr(cm.err, LVX_ERR_FALLBACK); else add_g(cm, kpos[bt], v, rep); }
+        if (v != 0.0) add_g(cm, kpos[bt], v, rep);
       }
       LVX_LDS_BARRIER();   // the register pass below zeroes what it reads
       if (tid == 0) { urng[0] = 1 << 30; urng[1] = -1; }
+      IKT(6)
     }
-    IKT(6)
     {
       // Every thread takes its share of the accumulators into registers (band: pairs of entries, 16 bytes) together with what it needs to route them, and leaves
       // ZERO behind; ONE barrier; then each value goes where it belongs: a finished column to HBM (stored by its owner), a live one down by nfl rows in LDS.  The
@@ -2249,6 +2275,7 @@ int ensure_layout(lvx_ctx* ctx) {
     }
   }
   const SplineRef sp{ctx->t0, ctx->dt, N, nullptr, nullptr};
+  std::vector<int> imu_sk;   // knot interval of every IMU sample, sorted
   // ---- sort every family by knot interval and upload ----
   {
     Family& f = ctx->imu;
@@ -2257,39 +2284,7 @@ int ensure_layout(lvx_ctx* ctx) {
     stable_perm_by_key(key, perm);
     { std::vector<int> sk(f.n); for (int i = 0; i < f.n; ++i) sk[i] = key[perm[i]];
       if ((rc = upload_chunks(ctx, LVX_FAM_GYRO, sk, pick_chunk_batches(16, 64, ctx->sw.chunk_r_imu, (double)f.n / std::max(1, N - 3), 4 * (int)GyroAcc::LB)))) return rc;   // the gyroscope-only kernel of Solve #0
-      // owner-computes schedule (k_imu_own): one workgroup per CU, equal row counts, boundaries on knot intervals; inside a workgroup batches of <= 256 rows spanning <= IMU_CR
-      // intervals.  The workgroup keeps the tables of its whole knot range in LDS: more (smaller) ranges when the widest one does not fit (sparse sample streams).
-      const int ncu = ctx->n_cu;
-      const int cr = IMU_CR;
-      std::vector<int> off, k0, wg_c0;
-      int G = std::max(1, std::min(ncu, (f.n + 255) / 256)), span = 0;
-      for (;; G *= 2) {
-        off.clear(); k0.clear(); wg_c0.clear(); span = cr + 5;
-        int r = 0;
-        for (int g = 0; g < G; ++g) {
-          wg_c0.push_back((int)k0.size());
-          int r1 = g + 1 == G ? f.n : (int)((long long)f.n * (g + 1) / G);
-          while (r1 < f.n && r1 > 0 && sk[r1] == sk[r1 - 1]) ++r1;   // next interval start
-          r1 = std::max(r1, r);
-          const size_t first = k0.size();
-          for (int i = r; i < r1;) {
-            const int kf = std::max(0, sk[i]);
-            int e = std::min(r1, i + 256);
-            while (e > i + 1 && sk[e - 1] >= kf + cr) --e;
-            off.push_back(i); k0.push_back(kf);
-            i = e;
-          }
-          if (k0.size() > first) span = std::max(span, k0.back() - k0[first] + cr + 5);
-          r = r1;
-        }
-        wg_c0.push_back((int)k0.size());
-        if (imu_fused_lds_bytes(span) <= 160 * 1024 || G >= std::max(1, f.n)) break;
-      }
-      ctx->imu_wg = G; ctx->imu_nch = (int)k0.size(); ctx->imu_span = span; ctx->imu_h_k0 = k0; ctx->imu_h_wg_c0 = wg_c0;
-      off.push_back(f.n);
-      off.insert(off.end(), k0.begin(), k0.end());
-      if ((rc = upload_tmp(ctx, ctx->d_imu_chunk, off.data(), off.size() * 4))) return rc;
-      if ((rc = upload_tmp(ctx, ctx->d_imu_wg, wg_c0.data(), wg_c0.size() * 4))) return rc;
+      imu_sk.swap(sk);   // the owner-computes schedule of k_imu_own is laid out with its ownership table, once the band order is known (below)
     }
     auto ts = gather(f.t, perm, 1); auto g = gather(f.a3, perm, 3); auto a = gather(f.b3, perm, 3);
     if ((rc = upload_tmp(ctx, f.d_t, ts.data(), ts.size() * 8))) return rc;
@@ -2570,33 +2565,120 @@ int ensure_layout(lvx_ctx* ctx) {
     ctx->bw_near = std::min(bw_near, ctx->bw);
     ++ctx->layout_epoch;
   }
-  {   // band columns k_imu_own STORES (ImuOwn::own): knots whose every contribution comes from ONE workgroup's samples and whose 24-entry column maps onto
-      // position-contiguous neighbours.  A sample sorted into interval i evaluates in i - 1 .. i + 1 (|tau_imu| < dt) and touches 4 knots, so a range whose first
-      // interval is B shares the knots [B - 1, B + 3] with its left neighbour: those, knots next to the hub gap or the spline's end and knots no batch window covers stay
-      // -1 = cleared by k_clear and added atomically.
+  {   // owner-computes schedule of k_imu_own and the band columns it STORES (ImuOwn::own_k).
+      // Schedule: one workgroup per CU, equal row counts, boundaries on knot intervals — the PRIMARY range [P0, P1) of workgroup g; inside a workgroup batches of <= 256 rows
+      // spanning <= IMU_CR intervals.  The workgroup keeps the tables of its whole knot range in LDS: more (smaller) ranges when the widest one does not fit (sparse streams).
+      // Halo: a sample's evaluated interval is its sort key (knot_lookup: the segment is placed by t, t + tau_imu must stay inside it — the reference rejects the sample
+      // otherwise — and host and device take the same floor, quot_dt), so a sample of interval i touches exactly the knots i .. i + 3 and neighbouring ranges share P0 .. P0 + 2.
+      // Workgroup g also walks the samples of [P0 - 3, P0) in front of its primary ones (they may reach back through several ranges shorter than three intervals): it then
+      // sees every sample that touches a knot in [P0, P1) and owns those knots.
+      // Owned (own_k[k] = g): knots of [P0, P1) inside a batch window of g whose 30 positions are band positions and contiguous.  -1 = cleared by k_clear and added
+      // atomically by every workgroup from its PRIMARY samples: knots next to the hub gap or the spline's end, knots with landmarks ordered between them, knots no batch
+      // window covers.  A halo window must not touch such a knot (its samples would be added twice), so a boundary with one of them in [P0 - 3, P0 + 2] gets no halo and its
+      // shared knots P0 .. P0 + 2 stay -1 too — which may take the halo from a boundary next to it, hence the loop.
     std::vector<int> own((size_t)std::max(ctx->nb, 1), -1), own_k((size_t)std::max(N, 1), -1);   // by band position (k_clear) and by knot (k_imu_own)
-    const int G = ctx->imu_wg, cr = IMU_CR;
-    const std::vector<int>& k0 = ctx->imu_h_k0; const std::vector<int>& wc = ctx->imu_h_wg_c0;
+    const Family& f = ctx->imu;
+    const std::vector<int>& sk = imu_sk;
+    const int cr = IMU_CR;
+    const bool can_own = ctx->nb > 0 && !(locks & LVX_LOCK_R3) && f.n > 0 && ctx->dt > ctx->imu_mto;
+    std::vector<char> free_k((size_t)std::max(N, 1), 0);   // knots that can have an owner
+    if (can_own)
+      for (int k = 0; k + 4 < N; ++k) {
+        const int p0 = ctx->ord[6 * k];
+        if (p0 < 0 || p0 >= LVX_LM_BASE) continue;
+        bool contig = true;
+        for (int e = 0; e < 30 && contig; ++e) contig = ctx->ord[6 * k + e] == p0 + e;
+        free_k[k] = contig;
+      }
+    std::vector<int> off, k0, end, sl, wc, rb, halo, ws;
+    // the four wavefront slices of a batch [i, e) (five offsets): borders on interval starts, at most 64 samples each, window (interval) counts that differ by at most
+    // one — a short last batch is spread over all four wavefronts.  Where no such cut exists (more than 64 samples in one interval) the slices are [64 w, 64 w + 64).
+    auto slices = [&](int i, int e) {
+      const size_t s0 = sl.size();
+      for (int w = 0; w <= 4; ++w) sl.push_back(std::min(e, i + 64 * w));
+      if (ctx->sw.imu_fixed_slices) return;
+      ws.clear();
+      for (int s = i; s < e; ++s) if (s == i || sk[s] != sk[s - 1]) ws.push_back(s);
+      ws.push_back(e);
+      const int nw = (int)ws.size() - 1, q = nw / 4, x = nw % 4;
+      for (int mask = 0; mask < 16; ++mask) {   // which slices take one of the x extra windows
+        if (__builtin_popcount(mask) != x) continue;
+        int cut[5] = {i, 0, 0, 0, 0}, p = 0;
+        bool ok = true;
+        for (int w = 0; w < 4; ++w) { p += q + ((mask >> w) & 1); cut[w + 1] = ws[p]; ok = ok && cut[w + 1] - cut[w] <= 64; }
+        if (!ok) continue;
+        std::copy(cut, cut + 5, sl.begin() + s0);
+        return;
+      }
+    };
+    std::vector<char> shared;
+    int G = std::max(1, std::min(ctx->n_cu, (f.n + 255) / 256)), span = 0;
+    for (;; G *= 2) {
+      rb.assign(1, 0);   // primary ranges: samples [rb[g], rb[g + 1])
+      for (int g = 0; g < G; ++g) {
+        int r1 = g + 1 == G ? f.n : (int)((long long)f.n * (g + 1) / G);
+        while (r1 < f.n && r1 > 0 && sk[r1] == sk[r1 - 1]) ++r1;   // next interval start
+        rb.push_back(std::max(r1, rb.back()));
+      }
+      halo.assign(G, 0); shared.assign((size_t)std::max(N, 1), 0);
+      for (int g = 1; g < G; ++g) halo[g] = can_own && rb[g] > 0 && rb[g] < rb[g + 1] && sk[rb[g]] >= 0;   // (the first non-empty range starts at sample 0)
+      for (bool changed = can_own; changed;) {
+        changed = false;
+        for (int g = 1; g < G; ++g) {
+          if (!halo[g]) continue;
+          const int P0 = sk[rb[g]];
+          bool ok = true;
+          for (int k = std::max(0, P0 - 3); k <= std::min(N - 1, P0 + 2) && ok; ++k) ok = free_k[k] && !shared[k];
+          if (ok) continue;
+          halo[g] = 0; changed = true;
+          for (int k = P0; k <= std::min(N - 1, P0 + 2); ++k) shared[k] = 1;
+        }
+      }
+      off.clear(); k0.clear(); end.clear(); sl.clear(); wc.clear(); span = cr + 5;
+      for (int g = 0; g < G; ++g) {
+        wc.push_back((int)k0.size());
+        const int r0 = halo[g] ? (int)(std::lower_bound(sk.begin(), sk.begin() + rb[g], std::max(0, sk[rb[g]] - 3)) - sk.begin()) : rb[g], r1 = rb[g + 1];
+        const size_t first = k0.size();
+        for (int i = r0; i < r1;) {
+          const int kf = std::max(0, sk[i]);
+          int e = std::min(r1, i + 256);
+          while (e > i + 1 && sk[e - 1] >= kf + cr) --e;
+          off.push_back(i); k0.push_back(kf); end.push_back(e);
+          slices(i, e);
+          i = e;
+        }
+        if (k0.size() > first) span = std::max(span, k0.back() - k0[first] + cr + 5);
+      }
+      wc.push_back((int)k0.size());
+      if (imu_fused_lds_bytes(span) <= 160 * 1024 || G >= std::max(1, f.n)) break;
+    }
+    ctx->imu_wg = G; ctx->imu_nch = (int)k0.size(); ctx->imu_span = span; ctx->imu_h_k0 = k0; ctx->imu_h_wg_c0 = wc;
     ctx->imu_owned_cols = 0;
-    if (ctx->nb > 0 && !(locks & LVX_LOCK_R3) && ctx->imu.n > 0 && ctx->dt > ctx->imu_mto) {
+    if (can_own) {
       int prev = -1;
       for (int g = 0; g < G; ++g) {
-        if (wc[g] >= wc[g + 1]) continue;
-        int nxt = -1; for (int h = g + 1; h < G && nxt < 0; ++h) if (wc[h] < wc[h + 1]) nxt = h;
-        const int lo = prev < 0 ? 0 : k0[wc[g]] + 4, hi = nxt < 0 ? N - 1 : k0[wc[nxt]] - 2;
+        if (rb[g] >= rb[g + 1]) continue;
+        int nxt = -1; for (int h = g + 1; h < G && nxt < 0; ++h) if (rb[h] < rb[h + 1]) nxt = h;
+        const int lo = prev < 0 ? 0 : sk[rb[g]], hi = nxt < 0 ? N - 1 : sk[rb[nxt]] - 1;   // the primary range in knots (a boundary without halo: less its shared knots)
         for (int c = wc[g]; c < wc[g + 1]; ++c)
           for (int k = std::max(lo, k0[c] - 1); k <= std::min(hi, k0[c] - 1 + cr + 4); ++k) {
-            if (k < 0 || k + 4 >= N) continue;
+            if (k < 0 || k >= N || !free_k[k] || shared[k]) continue;
             const int p0 = ctx->ord[6 * k];
-            if (p0 < 0 || p0 >= LVX_LM_BASE) continue;
-            bool contig = true;
-            for (int e = 0; e < 30 && contig; ++e) contig = ctx->ord[6 * k + e] == p0 + e;
-            if (!contig) continue;
             for (int d = 0; d < 6; ++d) { if (own[p0 + d] < 0) ctx->imu_owned_cols++; own[p0 + d] = g; }
             own_k[k] = g;
           }
         prev = g;
       }
+    }
+    {
+      std::vector<int> wgtab(wc);   // [batches of every workgroup (G + 1) | its first primary sample (G)]
+      wgtab.insert(wgtab.end(), rb.begin(), rb.begin() + G);
+      off.push_back(f.n);   // batches: [first sample (nch + 1) | first interval (nch) | end (nch) | wavefront slices (5 nch)]
+      off.insert(off.end(), k0.begin(), k0.end());
+      off.insert(off.end(), end.begin(), end.end());
+      off.insert(off.end(), sl.begin(), sl.end());
+      if ((rc = upload_tmp(ctx, ctx->d_imu_chunk, off.data(), off.size() * 4))) return rc;
+      if ((rc = upload_tmp(ctx, ctx->d_imu_wg, wgtab.data(), wgtab.size() * 4))) return rc;
     }
     ctx->imu_own_k_off = own.size();
     own.insert(own.end(), own_k.begin(), own_k.end());
