@@ -388,6 +388,19 @@ int lvx_voxel_lookup1_d(lvx_ctx* ctx, int nq, const float* xyzi4_d, int32_t* lea
  * leaf_ids[q][r] = leaf at displacement rel3[r] = (di, dj, dk) from the query's cell, or -1 (outside the grid, empty, fewer than min_points_per_voxel points).
  * The reference returns the hits in this order without the misses.  DIRECT26 = pcl::getAllNeighborCellIndices() as rel3. */
 int lvx_voxel_lookup_rel(lvx_ctx* ctx, int nq, const float* xyzi4, int n_rel, const int32_t* rel3, int32_t* leaf_ids);
+/* VoxelGridCovariance::radiusSearch(point, radius, k_leaves, k_sqr_distances) (voxel_grid_covariance_omp.h:473-502) against the grid of the last lvx_voxel_build: the
+ * leaves whose float centroid lies within `radius` of the query, nearest first.  Per query LVX_VOXEL_RADIUS_MAX slots: count[q] leaf indices in leaf_ids27[q][] and
+ * their squared distances in sqr_dist27[q][], then -1 / +infinity.  Defined in lvi-exc_amd/csrc/lvx_vxradius.h: no tree — the 27 cells around the query's cell hold
+ * every centroid within a radius <= leaf size; float distance d2 = (dx dx + dy dy) + dz dz to the stored float centroid, a hit is d2 < (float)(radius * radius)
+ * (FLANN's L2_Simple and RadiusResultSet); ascending d2, equal d2 by ascending leaf index (FLANN leaves ties unspecified).  Deviation: the build's cell arithmetic is
+ * float, so a centroid within an ulp of a cell face and about `radius` away can lie two cells from the query — the reference's tree finds it, the 27 cells do not.
+ * MEMBERS are the leaves that had at least min_points_per_voxel points when the grid was built, as in the reference's tree (voxel_grid_covariance_omp_impl.hpp:301-330):
+ * a leaf the build rejected afterwards (nr_points -1) IS returned here — and never by lvx_voxel_lookup1 / 7 / _rel.  A non-finite query has count 0.
+ * LVX_E_ARG: radius <= 0, not finite or above the grid's leaf size (the 27 cells would no longer cover it), NULL xyzi4.  LVX_E_STATE: no grid.  nq = 0 is fine.
+ * Host arrays; any output may be NULL.  The _d form takes device addresses and is ASYNCHRONOUS on the context's stream. */
+#define LVX_VOXEL_RADIUS_MAX 27
+int lvx_voxel_radius_search(lvx_ctx* ctx, int nq, const float* xyzi4, double radius, int32_t* leaf_ids27, float* sqr_dist27, int32_t* count);
+int lvx_voxel_radius_search_d(lvx_ctx* ctx, int nq, const float* xyzi4_d, double radius, int32_t* leaf_ids27_d, float* sqr_dist27_d, int32_t* count_d);
 /* SurfelAssociation::getAssociation flag pass (src/lvi_exc/src/core/surfel_association.cpp:111-138): plane_of_point[H*W] = surfel id or -1.
  * Conflicts resolve as the reference's SERIAL plane loop (highest plane id wins); W <= 4096 */
 int lvx_surfel_assoc(lvx_ctx* ctx, int H, int W, const float* scan_map_xyzi4, int n_planes, const double* plane_p4, const double* box_min3, const double* box_max3,
@@ -451,6 +464,13 @@ int64_t lvx_collective_count(lvx_ctx* ctx, int reset);
  * The NDT calls (lvx_ndt_derivatives, lvx_ndt_align, lvx_ndt_fitness) require a finite source cloud: their kernels do not carry the lookups' non-finite guard. */
 int lvx_ndt_derivatives(lvx_ctx* ctx, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian,
                         double* score, double* gradient6, double* hessian36);
+/* The same evaluation with the neighbour search of the caller's choice (ndt_omp.h:59-64): search = LVX_NDT_SEARCH_KDTREE (0), 1 (DIRECT1), 7 (DIRECT7: what
+ * lvx_ndt_derivatives does) or 26 (DIRECT26).  KDTREE = radiusSearch(x_trans_pt, resolution_, ...) (ndt_omp_impl.hpp:233-236): lvx_voxel_radius_search at the grid's leaf
+ * size, neighbours visited nearest first.  A rejected leaf among them is evaluated with what the grid stores for it, as the reference does: a zero inverse covariance
+ * (eigenvalue test) adds -gauss_d1 to the score and nothing else; one with infinities is dropped by updateDerivatives' own guard. */
+#define LVX_NDT_SEARCH_KDTREE 0
+int lvx_ndt_derivatives_search(lvx_ctx* ctx, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian,
+                               int search, double* score, double* gradient6, double* hessian36);
 
 /* NDT registration (the loop around the derivatives) ---------------------------------------------------------------------------*/
 /* pcl::Registration::align -> pclomp::NormalDistributionsTransform::computeTransformation (src/ndt_omp/include/pclomp/ndt_omp_impl.hpp:81-171): Newton steps
@@ -458,7 +478,8 @@ int lvx_ndt_derivatives(lvx_ctx* ctx, int n, const float* input_xyzi4, const flo
  * :689-768), derivatives by computeDerivatives (:180-285) and, after a line search that moved, computeHessian (:540-645), all against the voxel grid of the last
  * lvx_voxel_build of this context (= setInputTarget at that resolution, ndt_omp.h:117-122,275-282).  The Newton / line-search bookkeeping (a handful of scalars per
  * iteration) runs on the host as in the reference; every evaluation over the cloud is one kernel.  Defaults = the reference's constructor (:46-76).
- * search: 1 = DIRECT1, 7 = DIRECT7, 26 = DIRECT26 (ndt_omp.h:59-64; KDTREE is not offered: the calibration uses DIRECT7, lidar_odometry.cpp:32-43). */
+ * search: 0 = KDTREE (LVX_NDT_SEARCH_KDTREE: the radius search over the leaf centroids, see lvx_ndt_derivatives_search), 1 = DIRECT1, 7 = DIRECT7, 26 = DIRECT26
+ * (ndt_omp.h:59-64; the calibration uses DIRECT7, lidar_odometry.cpp:32-43). */
 typedef struct lvx_ndt_options { double step_size, outlier_ratio, transformation_epsilon; int32_t max_iterations, search; } lvx_ndt_options;
 typedef struct lvx_ndt_result {
   float final_transformation[16];   /* row-major 4 x 4: getFinalTransformation() */

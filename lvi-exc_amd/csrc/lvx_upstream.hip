@@ -3,6 +3,7 @@
 //                       6-sector sort + greedy edge/plane pick     (reference: src/aloam/src/scanRegistration.cpp:101-131,199-447)
 //   lvx_voxel_build     ndt_omp VoxelGridCovariance::applyFilter    (src/ndt_omp/include/pclomp/voxel_grid_covariance_omp_impl.hpp:49-374)
 //   lvx_voxel_lookup7   getNeighborhoodAtPoint7                     (same file :378-438)
+//   lvx_voxel_radius_search  VoxelGridCovariance::radiusSearch      (voxel_grid_covariance_omp.h:473-502; lvx_vxradius.h)
 //   lvx_surfel_assoc    SurfelAssociation::getAssociation           (src/lvi_exc/src/core/surfel_association.cpp:111-138,296-331)
 // These are HBM/latency-bound integer + float kernels (no MFMA).  Float expressions keep the reference's evaluation order and the
 // library is built with -ffp-contract=off, so scan registration is bit-exact against the serial code.
@@ -19,6 +20,7 @@
 #include "lvx_ctx.h"
 #include "lvx_pose.h"
 #include "lvx_stdsort.h"
+#include "lvx_vxradius.h"
 
 namespace lvx {
 
@@ -984,7 +986,7 @@ __device__ __forceinline__ float ndt_expf(float x) {
 }
 template <int NB, bool XF>
 __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, const float4* trn, NdtMat M, int n, float leaf, int min_pts, VxGrid g, const int* grid, const int* leaf_n,
-                                                         const double* mean, const double* icov, NdtConst K, int compute_hessian, double* part, int* ticket, double* out43) {
+                                                         const double* mean, const double* icov, const float* centroid, NdtConst K, int compute_hessian, double* part, int* ticket, double* out43) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   double acc[43];
 #pragma unroll
@@ -1012,7 +1014,7 @@ __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, cons
     const int ijk[3] = {(int)floorf(xt.x / leaf), (int)floorf(xt.y / leaf), (int)floorf(xt.z / leaf)};
     // the NB cell probes in flight, then the NB leaf counts (as in k_vx_lookup: probe by probe the loads queue up one behind the other); cells are still visited
     // in the reference's order
-    int lis[NB]; bool use[NB];
+    int lis[NB ? NB : 1]; bool use[NB ? NB : 1];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bool in = true;
@@ -1024,10 +1026,25 @@ __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, cons
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { const int cn = leaf_n[lis[nb] >= 0 ? lis[nb] : 0]; use[nb] = lis[nb] >= 0 && cn >= min_pts; }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      if (!use[nb]) continue;
-      const int li = lis[nb];
+    // NB = 0, KDTREE: the leaves whose centroid lies within one leaf size of the point, nearest first (lvx_vxradius.h: 27 candidate keys in fixed slots, the next
+    // larger key per trip; the loop is not unrolled).  A leaf the build rejected is among them and carries the zero inverse covariance the reference leaves it with:
+    // -gauss_d1 to the score, nothing to the gradient and the Hessian.
+    unsigned long long rkey[NB ? 1 : LVX_VXR_CELLS], rlo = 0;
+    if constexpr (NB == 0) {
+      const VxrGrid vg = {{g.min_b[0], g.min_b[1], g.min_b[2]}, {g.max_b[0], g.max_b[1], g.max_b[2]}, {g.mul[0], g.mul[1], g.mul[2]}};
+      vxr_candidates(xt.x, xt.y, xt.z, leaf, vxr_r2((double)leaf), min_pts, vg, grid, leaf_n, centroid, rkey);
+    }
+#pragma unroll(NB ? NB : 1)
+    for (int nb = 0; nb < (NB ? NB : LVX_VXR_CELLS); ++nb) {
+      int li;
+      if constexpr (NB == 0) {
+        const unsigned long long b = vxr_next(rkey, rlo);
+        if (b == VXR_NONE) break;
+        rlo = b + 1; li = vxr_key_leaf(b);
+      } else {
+        if (!use[nb]) continue;
+        li = lis[nb];
+      }
       const double* mu = mean + 3 * (size_t)li; const double* ic = icov + 9 * (size_t)li;
       const float x4[3] = {(float)((double)xt.x - mu[0]), (float)((double)xt.y - mu[1]), (float)((double)xt.z - mu[2])};
       float ci[3][3];
@@ -1068,7 +1085,7 @@ __global__ __launch_bounds__(256) void k_ndt_derivatives(const float4* src, cons
 struct NdtConstD { double j_ang[8][3]; double h_ang[15][3]; double gd1, gd2; };
 template <int NB>
 __global__ __launch_bounds__(256) void k_ndt_hessian(const float4* src, NdtMat M, int n, float leaf, int min_pts, VxGrid g, const int* grid, const int* leaf_n, const double* mean,
-                                                     const double* icov, NdtConstD K, double* part, int* ticket, double* out36) {
+                                                     const double* icov, const float* centroid, NdtConstD K, double* part, int* ticket, double* out36) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   double acc[36];
 #pragma unroll
@@ -1089,7 +1106,7 @@ __global__ __launch_bounds__(256) void k_ndt_hessian(const float4* src, NdtMat M
     for (int r = 0; r < 3; ++r) { hv[3][r] = dot3(x, K.h_ang[6 + r]); hv[4][r] = dot3(x, K.h_ang[9 + r]); hv[5][r] = dot3(x, K.h_ang[12 + r]); }
     const int hsel[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
     const int ijk[3] = {(int)floorf(xt.x / leaf), (int)floorf(xt.y / leaf), (int)floorf(xt.z / leaf)};
-    int lis[NB]; bool use[NB];
+    int lis[NB ? NB : 1]; bool use[NB ? NB : 1];
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
       bool in = true;
@@ -1101,10 +1118,23 @@ __global__ __launch_bounds__(256) void k_ndt_hessian(const float4* src, NdtMat M
     }
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) { const int cn = leaf_n[lis[nb] >= 0 ? lis[nb] : 0]; use[nb] = lis[nb] >= 0 && cn >= min_pts; }
-#pragma unroll
-    for (int nb = 0; nb < NB; ++nb) {
-      if (!use[nb]) continue;
-      const int li = lis[nb];
+    // NB = 0, KDTREE: as in k_ndt_derivatives (a rejected leaf's zero inverse covariance adds nothing here)
+    unsigned long long rkey[NB ? 1 : LVX_VXR_CELLS], rlo = 0;
+    if constexpr (NB == 0) {
+      const VxrGrid vg = {{g.min_b[0], g.min_b[1], g.min_b[2]}, {g.max_b[0], g.max_b[1], g.max_b[2]}, {g.mul[0], g.mul[1], g.mul[2]}};
+      vxr_candidates(xt.x, xt.y, xt.z, leaf, vxr_r2((double)leaf), min_pts, vg, grid, leaf_n, centroid, rkey);
+    }
+#pragma unroll(NB ? NB : 1)
+    for (int nb = 0; nb < (NB ? NB : LVX_VXR_CELLS); ++nb) {
+      int li;
+      if constexpr (NB == 0) {
+        const unsigned long long b = vxr_next(rkey, rlo);
+        if (b == VXR_NONE) break;
+        rlo = b + 1; li = vxr_key_leaf(b);
+      } else {
+        if (!use[nb]) continue;
+        li = lis[nb];
+      }
       const double* mu = mean + 3 * (size_t)li; const double* ci = icov + 9 * (size_t)li;
       const double xd[3] = {(double)xt.x - mu[0], (double)xt.y - mu[1], (double)xt.z - mu[2]};
       double cxv[3];
@@ -1180,6 +1210,18 @@ __global__ __launch_bounds__(256) void k_vx_lookup_rel(const float4* q, int nq, 
     if (li >= 0 && leaf_n[li] >= min_pts) id = li;                                                                                                       // :399
   }
   ids[e] = id;
+}
+// VoxelGridCovariance::radiusSearch(point, radius, k_leaves, k_sqr_distances) (voxel_grid_covariance_omp.h:473-502) without a tree (lvx_vxradius.h): one thread per
+// query, 27 results per query (count of them, then -1 / +infinity); any output may be NULL
+__global__ __launch_bounds__(256) void k_vx_radius(const float4* q, int nq, float leaf, double radius, int min_pts, VxGrid g, const int* grid, const int* leaf_n, const float* centroid,
+                                                   int* ids27, float* d2_27, int* count) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nq) return;
+  const float4 p = q[i];
+  const VxrGrid vg = {{g.min_b[0], g.min_b[1], g.min_b[2]}, {g.max_b[0], g.max_b[1], g.max_b[2]}, {g.mul[0], g.mul[1], g.mul[2]}};
+  const int n = vxr_search(p.x, p.y, p.z, leaf, radius, min_pts, vg, grid, leaf_n, centroid, ids27 ? ids27 + (size_t)i * LVX_VXR_CELLS : nullptr,
+                           d2_27 ? d2_27 + (size_t)i * LVX_VXR_CELLS : nullptr);
+  if (count) count[i] = n;
 }
 // surfel map extraction: one WAVEFRONT per leaf (tens to hundreds of points each).  Round 3 had one thread per leaf walking its points three times with a dependent
 // id -> point gather per point (1.5 ms for the 410 k-point map cloud, more than half of lvx_data_association); now the 64 lanes stride over the leaf's points, the inlier
@@ -3161,12 +3203,12 @@ int ndt_workspace(lvx_ctx* c, int n, NdtDev* W) {
   LVX_HIP(c, hipMemsetAsync(W->out, 0, 64 * 8, c->stream));
   return LVX_OK;
 }
-struct NdtGridArgs { VxGrid g; const int* cells; const int* leaf_n; const double* mean; const double* icov; float leaf; int min_pts; };
+struct NdtGridArgs { VxGrid g; const int* cells; const int* leaf_n; const double* mean; const double* icov; const float* centroid; float leaf; int min_pts; };
 NdtGridArgs ndt_grid(const lvx_ctx* c) {
   const lvx_ctx::Voxels& V = c->vox;
   NdtGridArgs G; std::memcpy(&G.g, &V.grid, sizeof(G.g));
   const size_t nl = (size_t)V.cap;   // leaf arrays are strided by the capacity
-  G.cells = (const int*)V.cells.p; G.leaf_n = (const int*)V.leaf_i.p + nl; G.mean = (const double*)V.leaf_d.p; G.icov = G.mean + 12 * nl; G.leaf = V.leaf; G.min_pts = V.min_pts;
+  G.cells = (const int*)V.cells.p; G.leaf_n = (const int*)V.leaf_i.p + nl; G.mean = (const double*)V.leaf_d.p; G.icov = G.mean + 12 * nl; G.centroid = (const float*)V.leaf_f.p; G.leaf = V.leaf; G.min_pts = V.min_pts;
   return G;
 }
 // one computeDerivatives on the device: score, gradient, Hessian at p6 (transform M16 applied in the kernel, or the caller's transformed cloud trn_d)
@@ -3176,9 +3218,9 @@ int ndt_eval(lvx_ctx* c, const NdtDev& W, int n, const float4* src_d, const floa
   const NdtMat M = ndt_mat12(M16);
   const dim3 grid((unsigned)W.blocks), blk(256);
   { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
-#define LVX_NDT_LAUNCH(NB, XF) hipLaunchKernelGGL((k_ndt_derivatives<NB, XF>), grid, blk, 0, c->stream, src_d, trn_d, M, n, G.leaf, G.min_pts, G.g, G.cells, G.leaf_n, G.mean, G.icov, T.f, compute_hessian, W.part, W.ticket, W.out)
-    if (trn_d) { if (search == 1) LVX_NDT_LAUNCH(1, false); else if (search == 26) LVX_NDT_LAUNCH(26, false); else LVX_NDT_LAUNCH(7, false); }
-    else { if (search == 1) LVX_NDT_LAUNCH(1, true); else if (search == 26) LVX_NDT_LAUNCH(26, true); else LVX_NDT_LAUNCH(7, true); }
+#define LVX_NDT_LAUNCH(NB, XF) hipLaunchKernelGGL((k_ndt_derivatives<NB, XF>), grid, blk, 0, c->stream, src_d, trn_d, M, n, G.leaf, G.min_pts, G.g, G.cells, G.leaf_n, G.mean, G.icov, G.centroid, T.f, compute_hessian, W.part, W.ticket, W.out)
+    if (trn_d) { if (search == 0) LVX_NDT_LAUNCH(0, false); else if (search == 1) LVX_NDT_LAUNCH(1, false); else if (search == 26) LVX_NDT_LAUNCH(26, false); else LVX_NDT_LAUNCH(7, false); }
+    else { if (search == 0) LVX_NDT_LAUNCH(0, true); else if (search == 1) LVX_NDT_LAUNCH(1, true); else if (search == 26) LVX_NDT_LAUNCH(26, true); else LVX_NDT_LAUNCH(7, true); }
 #undef LVX_NDT_LAUNCH
   }
   LVX_HIP(c, hipGetLastError());
@@ -3192,8 +3234,8 @@ int ndt_hessian(lvx_ctx* c, const NdtDev& W, int n, const float4* src_d, const f
   const NdtMat M = ndt_mat12(M16);
   const dim3 grid((unsigned)W.blocks), blk(256);
   { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
-#define LVX_NDT_LAUNCH(NB) hipLaunchKernelGGL((k_ndt_hessian<NB>), grid, blk, 0, c->stream, src_d, M, n, G.leaf, G.min_pts, G.g, G.cells, G.leaf_n, G.mean, G.icov, T.d, W.part, W.ticket, W.out)
-    if (search == 1) LVX_NDT_LAUNCH(1); else if (search == 26) LVX_NDT_LAUNCH(26); else LVX_NDT_LAUNCH(7);
+#define LVX_NDT_LAUNCH(NB) hipLaunchKernelGGL((k_ndt_hessian<NB>), grid, blk, 0, c->stream, src_d, M, n, G.leaf, G.min_pts, G.g, G.cells, G.leaf_n, G.mean, G.icov, G.centroid, T.d, W.part, W.ticket, W.out)
+    if (search == 0) LVX_NDT_LAUNCH(0); else if (search == 1) LVX_NDT_LAUNCH(1); else if (search == 26) LVX_NDT_LAUNCH(26); else LVX_NDT_LAUNCH(7);
 #undef LVX_NDT_LAUNCH
   }
   LVX_HIP(c, hipGetLastError());
@@ -3298,9 +3340,12 @@ int lvx_ndt_default_options(lvx_ndt_options* o) {
   return LVX_OK;
 }
 
-int lvx_ndt_derivatives(lvx_ctx* c, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian,
-                        double* score, double* gradient6, double* hessian36) {
+static bool ndt_search_ok(int search) { return search == LVX_NDT_SEARCH_KDTREE || search == 1 || search == 7 || search == 26; }
+
+int lvx_ndt_derivatives_search(lvx_ctx* c, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian, int search,
+                               double* score, double* gradient6, double* hessian36) {
   if (!c || n < 0 || !p6 || !score || !gradient6 || (compute_hessian && !hessian36) || (n > 0 && (!input_xyzi4 || !trans_xyzi4))) return LVX_E_ARG;
+  if (!ndt_search_ok(search)) return fail(c, LVX_E_ARG, "lvx_ndt_derivatives_search: search must be 0 (KDTREE), 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
   LVX_HIP(c, hipSetDevice(c->device));
   { const int rc0 = vox_info(c); if (rc0) return rc0; }
   const lvx_ctx::Voxels& V = c->vox;
@@ -3315,11 +3360,15 @@ int lvx_ndt_derivatives(lvx_ctx* c, int n, const float* input_xyzi4, const float
   if ((rc = ndt_workspace(c, n, &W))) return rc;
   const float I16[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   double h[43];
-  if ((rc = ndt_eval(c, W, n, (const float4*)c->d_up[2].p, (const float4*)c->d_up[3].p, I16, p6, outlier_ratio, 7, compute_hessian, h))) return rc;
+  if ((rc = ndt_eval(c, W, n, (const float4*)c->d_up[2].p, (const float4*)c->d_up[3].p, I16, p6, outlier_ratio, search, compute_hessian, h))) return rc;
   *score = h[0];
   for (int j = 0; j < 6; ++j) gradient6[j] = h[1 + j];
   if (hessian36) for (int e = 0; e < 36; ++e) hessian36[e] = h[7 + e];
   return LVX_OK;
+}
+int lvx_ndt_derivatives(lvx_ctx* c, int n, const float* input_xyzi4, const float* trans_xyzi4, const double* p6, double outlier_ratio, int compute_hessian,
+                        double* score, double* gradient6, double* hessian36) {
+  return lvx_ndt_derivatives_search(c, n, input_xyzi4, trans_xyzi4, p6, outlier_ratio, compute_hessian, 7, score, gradient6, hessian36);
 }
 
 // pcl::Registration::align -> pclomp::NormalDistributionsTransform::computeTransformation (ndt_omp_impl.hpp:81-171) against the voxel grid of the last lvx_voxel_build.
@@ -3374,7 +3423,7 @@ static int ndt_align_device(lvx_ctx* c, int n, const float4* src_d, const float*
 int lvx_ndt_align(lvx_ctx* c, int n, const float* src_xyzi4, const float* guess16, const lvx_ndt_options* opt, lvx_ndt_result* res, float* aligned_xyzi4) {
   if (!c || n < 0 || !res || (n > 0 && !src_xyzi4)) return LVX_E_ARG;
   lvx_ndt_options o; lvx_ndt_default_options(&o); if (opt) o = *opt;
-  if (o.search != 1 && o.search != 7 && o.search != 26) return fail(c, LVX_E_ARG, "lvx_ndt_align: search must be 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
+  if (!ndt_search_ok(o.search)) return fail(c, LVX_E_ARG, "lvx_ndt_align: search must be 0 (KDTREE), 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
   LVX_HIP(c, hipSetDevice(c->device));
   int rc;
   if ((rc = ndt_target_check(c))) return rc;
@@ -3422,7 +3471,7 @@ int lvx_lidar_odometry(lvx_ctx* c, const lvx_odom_options* opt_in, const double*
   if (c->da_S <= 0 || (size_t)c->da_H * c->da_W == 0) return fail(c, LVX_E_STATE, "lvx_set_scans has not been called");
   lvx_odom_options o; lvx_odom_default_options(&o); if (opt_in) o = *opt_in;
   if (!(o.ndt_resolution > 0) || !(o.downsample_leaf > 0)) return fail(c, LVX_E_ARG, "lvx_lidar_odometry: ndt_resolution and downsample_leaf must be positive");
-  if (o.ndt.search != 1 && o.ndt.search != 7 && o.ndt.search != 26) return fail(c, LVX_E_ARG, "lvx_lidar_odometry: search must be 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
+  if (!ndt_search_ok(o.ndt.search)) return fail(c, LVX_E_ARG, "lvx_lidar_odometry: search must be 0 (KDTREE), 1 (DIRECT1), 7 (DIRECT7) or 26 (DIRECT26)");
   const int S = c->da_S;
   const size_t HWs = (size_t)c->da_H * c->da_W;
   if (HWs > 2147483647ull) return fail(c, LVX_E_ARG, "too many points in one scan");
@@ -3542,6 +3591,53 @@ int lvx_voxel_lookup_rel(lvx_ctx* c, int nq, const float* xyzi4, int n_rel, cons
   LVX_HIP(c, hipMemcpyAsync(leaf_ids, c->d_up[3].p, ne * 4, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
+}
+
+// VoxelGridCovariance::radiusSearch (voxel_grid_covariance_omp.h:473-502) against the grid of the last lvx_voxel_build
+static int radius_check(lvx_ctx* c, int nq, const float* xyzi4, double radius, const char* who) {
+  if (!c || nq < 0) return LVX_E_ARG;
+  if (!xyzi4) return fail(c, LVX_E_ARG, std::string(who) + ": xyzi4 is NULL");
+  if (!(radius > 0) || !std::isfinite(radius)) return fail(c, LVX_E_ARG, std::string(who) + ": the radius must be positive and finite");
+  LVX_HIP(c, hipSetDevice(c->device));
+  { const int rc0 = vox_info(c); if (rc0) return rc0; }
+  if (!c->vox.cells.p || !(c->vox.leaf > 0)) return fail(c, LVX_E_STATE, std::string(who) + " needs a grid: call lvx_voxel_build first");
+  if (radius > (double)c->vox.leaf) return fail(c, LVX_E_ARG, std::string(who) + ": the radius must not exceed the grid's leaf size (the 27 cells around a query would not cover it)");
+  return LVX_OK;
+}
+static int radius_device(lvx_ctx* c, int nq, const float4* q_d, double radius, int* ids_d, float* d2_d, int* count_d) {
+  const lvx_ctx::Voxels& V = c->vox;
+  if (V.n_leaves == 0) {   // a grid without a leaf (an empty or all-non-finite cloud): nobody is within the radius
+    if (ids_d) LVX_HIP(c, hipMemsetAsync(ids_d, 0xff, (size_t)nq * LVX_VOXEL_RADIUS_MAX * 4, c->stream));
+    if (d2_d) LVX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)d2_d, 0x7f800000, (size_t)nq * LVX_VOXEL_RADIUS_MAX, c->stream));
+    if (count_d) LVX_HIP(c, hipMemsetAsync(count_d, 0, (size_t)nq * 4, c->stream));
+    return LVX_OK;
+  }
+  const NdtGridArgs G = ndt_grid(c);
+  { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+    hipLaunchKernelGGL(k_vx_radius, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, q_d, nq, G.leaf, radius, G.min_pts, G.g, G.cells, G.leaf_n, G.centroid, ids_d, d2_d, count_d); }
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+int lvx_voxel_radius_search(lvx_ctx* c, int nq, const float* xyzi4, double radius, int32_t* leaf_ids27, float* sqr_dist27, int32_t* count) {
+  int rc;
+  if ((rc = radius_check(c, nq, xyzi4, radius, "lvx_voxel_radius_search"))) return rc;
+  if (nq == 0) return LVX_OK;
+  const size_t ne = (size_t)nq * LVX_VOXEL_RADIUS_MAX;
+  if ((rc = upload(c, c->d_up[2], xyzi4, (size_t)nq * 16))) return rc;
+  if ((rc = dev_alloc(c, c->d_up[3], (2 * ne + (size_t)nq) * 4))) return rc;
+  int* ids_d = (int*)c->d_up[3].p; float* d2_d = (float*)(ids_d + ne); int* cnt_d = ids_d + 2 * ne;
+  if ((rc = radius_device(c, nq, (const float4*)c->d_up[2].p, radius, ids_d, d2_d, cnt_d))) return rc;
+  if (leaf_ids27) LVX_HIP(c, hipMemcpyAsync(leaf_ids27, ids_d, ne * 4, hipMemcpyDeviceToHost, c->stream));
+  if (sqr_dist27) LVX_HIP(c, hipMemcpyAsync(sqr_dist27, d2_d, ne * 4, hipMemcpyDeviceToHost, c->stream));
+  if (count) LVX_HIP(c, hipMemcpyAsync(count, cnt_d, (size_t)nq * 4, hipMemcpyDeviceToHost, c->stream));
+  LVX_HIP(c, hipStreamSynchronize(c->stream));
+  return LVX_OK;
+}
+int lvx_voxel_radius_search_d(lvx_ctx* c, int nq, const float* xyzi4_d, double radius, int32_t* leaf_ids27_d, float* sqr_dist27_d, int32_t* count_d) {
+  int rc;
+  if ((rc = radius_check(c, nq, xyzi4_d, radius, "lvx_voxel_radius_search_d"))) return rc;
+  if (nq == 0) return LVX_OK;
+  return radius_device(c, nq, (const float4*)xyzi4_d, radius, leaf_ids27_d, sqr_dist27_d, count_d);
 }
 
 int lvx_scan_less_flat_downsample_sweep(lvx_ctx* c, int sweep, float leaf, int max_out, float* out_xyzi4, int32_t* ring_counts, int32_t* n_out) {

@@ -417,7 +417,7 @@ class Calibrator {
   void EnsureOdometry() {
     if (!odom_.pose16.empty()) return;
     if (in_.scan_stamps.size() != in_.scans.size()) throw std::invalid_argument("scan_stamps: one header stamp per scan is needed for the LiDAR odometry");
-    lvx_odom_options oo; lvx_odom_default_options(&oo);
+    lvx_odom_options oo; lvx_odom_default_options(&oo);   // (oo.ndt.search: DIRECT7 as ndtInit sets it; 0 / 1 / 26 select KDTREE / DIRECT1 / DIRECT26)
     oo.ndt_resolution = opt_.ndt_resolution; oo.key_dist = opt_.key_scan_dist; oo.key_angle_deg = opt_.key_scan_angle_deg;
     odom_ = RunLidarOdometry(ctx_, in_.scan_stamps, &oo);
     if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] LiDAR odometry: %zu scans, %d key scans\n", in_.scans.size(), (int)odom_.n_key);

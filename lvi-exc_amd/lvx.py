@@ -740,14 +740,34 @@ def scan_less_flat_downsample(ctx, n_rings, max_out, leaf=0.2, sweep=0):
     return out[:min(n.value, max_out)], rc, n.value
 
 
-def ndt_derivatives(ctx, src, trans, p6, outlier_ratio=0.55, compute_hessian=True):
-    """Score, gradient, Hessian of the NDT objective against the context's last voxel_build (computeDerivatives, DIRECT7)."""
+NDT_SEARCH_KDTREE = 0
+VOXEL_RADIUS_MAX = 27
+
+
+def ndt_derivatives(ctx, src, trans, p6, outlier_ratio=0.55, compute_hessian=True, search=7):
+    """Score, gradient, Hessian of the NDT objective against the context's last voxel_build (computeDerivatives); search = 0 (KDTREE), 1, 7 (DIRECT7) or 26."""
     src = np.ascontiguousarray(src, dtype=np.float32).reshape(-1, 4)
     trans = np.ascontiguousarray(trans, dtype=np.float32).reshape(-1, 4)
     score = C.c_double(0)
     g, H = np.zeros(6), np.zeros((6, 6))
-    ctx._ck(ctx._l.lvx_ndt_derivatives(ctx._h, C.c_int(len(src)), _p(src), _p(trans), _p(_d(p6)), C.c_double(outlier_ratio), C.c_int(1 if compute_hessian else 0), C.byref(score), _p(g), _p(H)))
+    ctx._ck(ctx._l.lvx_ndt_derivatives_search(ctx._h, C.c_int(len(src)), _p(src), _p(trans), _p(_d(p6)), C.c_double(outlier_ratio), C.c_int(1 if compute_hessian else 0), C.c_int(search),
+                                              C.byref(score), _p(g), _p(H)))
     return score.value, g, H
+
+
+def voxel_radius_search(ctx, queries, radius):
+    """VoxelGridCovariance::radiusSearch against the context's last voxel_build: (ids [nq][27], d2 [nq][27], count [nq]) — per query the leaves whose centroid lies within
+    `radius` (at most the grid's leaf size), nearest first, then -1 / +inf.  Leaves the build rejected (nr_points -1) are returned, unlike by the cell lookups."""
+    q = np.ascontiguousarray(queries, dtype=np.float32).reshape(-1, 4)
+    ids, d2, cnt = np.full((len(q), VOXEL_RADIUS_MAX), -1, np.int32), np.full((len(q), VOXEL_RADIUS_MAX), np.inf, np.float32), np.zeros(len(q), np.int32)
+    ctx._ck(ctx._l.lvx_voxel_radius_search(ctx._h, C.c_int(len(q)), _p(q), C.c_double(radius), _p(ids), _p(d2), _p(cnt)))
+    return ids, d2, cnt
+
+
+def voxel_radius_search_d(ctx, nq, queries_ptr, radius, ids_ptr, d2_ptr, count_ptr):
+    """lvx_voxel_radius_search_d on device addresses (0 / None = that output is not wanted): queued on the context's stream, not waited for."""
+    vp = lambda a: C.c_void_p(a) if a else None
+    ctx._ck(ctx._l.lvx_voxel_radius_search_d(ctx._h, C.c_int(nq), vp(queries_ptr), C.c_double(radius), vp(ids_ptr), vp(d2_ptr), vp(count_ptr)))
 
 
 class NdtOptions(C.Structure):
