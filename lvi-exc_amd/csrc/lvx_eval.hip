@@ -13,6 +13,7 @@
 
 #include <thread>
 #include "lvx_ctx.h"
+#include "lvx_fold.h"
 
 namespace lvx {
 
@@ -424,17 +425,31 @@ __global__ __launch_bounds__(64 * PW) void k_family(F fam, DevCommon cm, const u
 __device__ void hub_eval_thread(const DevCommon& cm, double t_map, int want_surf, int want_cs, HubShared* hubs, int s) {
   if (s > 1) return;
   if ((s == 0 && !want_surf) || (s == 1 && !want_cs)) { hubs[s].ok = 0; return; }
+#ifdef LVX_KTIME_FOLD   // tools/build_kt.sh FOLD: s_memtime ticks of the hub chain's phases (debug print), and when it ends (k_clear prints its last block's end)
+  long long kt_[5] = {0, 0, 0, 0, 0}; long long kt0_ = __builtin_amdgcn_s_memtime(); const long long kts_ = kt0_;
+#define HKT(i) { const long long n_ = __builtin_amdgcn_s_memtime(); kt_[i] += n_ - kt0_; kt0_ = n_; }
+#else
+#define HKT(i)
+#endif
   const SplineRef sp{cm.t0, cm.dt, cm.N, cm.state, cm.state + 3 * (size_t)cm.N};
   const Cal cal = load_cal(cm);
   const bool tl = s == 0 ? (cm.locks & LVX_LOCK_LIDAR_TAU) != 0 : (cm.locks & LVX_LOCK_CAM_TAU) != 0;
   const double tau = s == 0 ? cal.lidar.tau : cal.cam.tau;
   double s1[1][2]; hub_spans(t_map, tl, cm.sensor_mto, s1);
+  HKT(0)
   Segs sg; KnotRef kh; hubs[s].ok = 0;
   if (!build_segments(sp, s1, 1, &sg)) return;
   if (!seg_lookup(sp, sg, t_map + tau, &kh)) return;
+  HKT(1)
   if (!(tl ? pose_eval<true>(sp, kh, &hubs[s].A) : pose_eval<true, true>(sp, kh, &hubs[s].A))) { hubs[s].ok = -RES_NONUNIT; return; }   // a free offset differentiates through the hub's velocity / angular velocity
+  HKT(2)
   hub_matrix(hubs[s].A, hubs[s].M);   // once here instead of by one thread of each of the fold's ~600 workgroups
   hubs[s].ok = 1;
+  HKT(3)
+#ifdef LVX_KTIME_FOLD
+  printf("HKT hub set %d: cal+spans %lld segments+lookup %lld pose_eval %lld hub_matrix+stores %lld | total %lld, ends at %lld (ticks of s_memtime)\n", s, kt_[0], kt_[1], kt_[2], kt_[3],
+         (long long)__builtin_amdgcn_s_memtime() - kts_, (long long)__builtin_amdgcn_s_memtime());
+#endif
 }
 // everything that depends on the state only: blocks [0, nblk_tab) fill the control-point-pair table, the next block evaluates the shared
 // t_map poses; run by the first blocks of the pass's clear kernel (k_clear)
@@ -1980,6 +1995,12 @@ __device__ __forceinline__ void fold_border_dense_block(const DevCommon& cm) {
   extern __shared__ double Cf[];   // full symmetric [n][n] then g[n]
   const int n = cm.nbd;
   double* g = Cf + n * n;
+#ifdef LVX_KTIME_FOLD
+  long long kt_[4] = {0, 0, 0, 0}; long long kt0_ = __builtin_amdgcn_s_memtime(); const long long kts_ = kt0_;
+#define DKT(i) { const long long n_ = __builtin_amdgcn_s_memtime(); kt_[i] += n_ - kt0_; kt0_ = n_; }
+#else
+#define DKT(i)
+#endif
   // one workgroup, latency bound: issue a batch of 8 independent loads per thread before the first LDS store
   for (int e0 = threadIdx.x; e0 < n * n; e0 += 8 * 256) {
     double v[8];
@@ -1990,6 +2011,7 @@ __device__ __forceinline__ void fold_border_dense_block(const DevCommon& cm) {
   }
   for (int e = threadIdx.x; e < n; e += 256) g[e] = cm.gc[e];
   __syncthreads();
+  DKT(0)
   for (int set = 0; set < 2; ++set) {
     const HubShared* hub = ((const HubShared*)cm.hubs) + set;
     if (hub->ok != 1) continue;   // uniform
@@ -2009,6 +2031,7 @@ __device__ __forceinline__ void fold_border_dense_block(const DevCommon& cm) {
     }
     if (threadIdx.x < 24 && hrow[threadIdx.x] >= 0) { double s = 0.0; for (int p = 0; p < 6; ++p) s += M[p][threadIdx.x] * g[p0 + p]; g[hrow[threadIdx.x]] += s; }
     __syncthreads();
+    DKT(1)
     // columns: C[:][hub_c] += sum_p C[:][p0+p] M[p][c]
     for (int e = threadIdx.x; e < 24 * n; e += 256) {
       const int c = e / n, row = e % n;
@@ -2018,9 +2041,14 @@ __device__ __forceinline__ void fold_border_dense_block(const DevCommon& cm) {
       Cf[row * n + hrow[c]] += s;
     }
     __syncthreads();
+    DKT(2)
   }
   for (int e = threadIdx.x; e < n * n; e += 256) { const int a = e / n, b = e % n; if (a >= b) cm.C[(size_t)a * n + b] = Cf[e]; }
   for (int e = threadIdx.x; e < n; e += 256) cm.gc[e] = g[e];
+  DKT(3)
+#ifdef LVX_KTIME_FOLD
+  if (threadIdx.x == 0) printf("FKT dense block (one workgroup, n %d): load %lld rows %lld columns %lld store %lld | total %lld\n", n, kt_[0], kt_[1], kt_[2], kt_[3], (long long)__builtin_amdgcn_s_memtime() - kts_);
+#endif
 }
 
 __global__ __launch_bounds__(256) void k_fold_border_dense(DevCommon cm) { fold_border_dense_block(cm); }
@@ -2049,26 +2077,116 @@ __device__ __forceinline__ void fold_replicas_block(const DevCommon& cm, int blk
   if (i == 0) cm.cost[0] = strided_sum(cm.cost, 1, cm.nrep);
 }
 __global__ void k_fold_replicas(DevCommon cm) { fold_replicas_block(cm, (int)blockIdx.x); }
-// The whole fold in ONE launch (round 5b): blocks [0, n_rep) sum the replicas of the dense border accumulators, and the LAST of them to finish (a ticket) folds the dense
-// block; blocks behind them fold the border rows of set `set0` (then of `set1` if >= 0).  Three launches on two streams before — replicas 10 us -> dense 17 us on the chain,
-// border rows 17 us beside them, plus the fork / join packets around the side stream.
-__global__ __launch_bounds__(256) void k_fold_all(DevCommon cm, int n_rep, int n_rows, int set0, int store0, int set1, int store1, int* ticket) {
-  __shared__ int s_last;
-  const int b = blockIdx.x;
-  if (b < n_rep) {
-    fold_replicas_block(cm, b);
-    __threadfence();
-    __syncthreads();
-    if (threadIdx.x == 0) { const int t = atomicAdd(ticket, 1); s_last = t == n_rep - 1; if (s_last) *ticket = 0; }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    fold_border_dense_block(cm);
-    return;
+// the same sum with 64 loads in flight: a replica block of k_fold_all sums three or four entries per thread, one round trip to memory each
+__device__ __forceinline__ double strided_sum64(const double* p, size_t stride, int n) {
+  double s = 0.0;
+  for (int r0 = 0; r0 < n; r0 += 64) {
+    double v[64];
+#pragma unroll
+    for (int q = 0; q < 64; ++q) v[q] = r0 + q < n ? p[(size_t)(r0 + q) * stride] : 0.0;
+#pragma unroll
+    for (int q = 0; q < 64; ++q) s += v[q];
   }
-  const int r = b - n_rep;
+  return s;
+}
+#define LVX_FOLD_OWN 128   // entries of the dense block per replica block of k_fold_all
+// U of fold_dense_entry (zeroed by the caller): M of the wanted sets with ok == 1 at their live hub rows
+__device__ __forceinline__ void fold_load_U(const DevCommon& cm, unsigned want, double* U, int n) {
+  for (int s = 0; s < 2; ++s) {
+    const HubShared* hub = ((const HubShared*)cm.hubs) + s;
+    if (!((want >> s) & 1u) || hub->ok != 1) continue;   // uniform
+    if (threadIdx.x < 144) {
+      const int p = threadIdx.x / 24, c = threadIdx.x % 24;
+      const int o = cm.ord[6 * (hub->A.k.i0 + c / 6) + c % 6];   // hub control points are border variables; distinct (p, c) -> distinct entry of U
+      if (o != LVX_DEAD && o < 0) U[(6 * s + p) * n + (-1 - o)] = hub->M[p][c];
+    }
+  }
+}
+// A replica block of k_fold_all: LVX_FOLD_OWN entries of the dense block, folded, without waiting for any other block.  It forms the replica sums of the wanted
+// sets' pseudo rows itself (LDS: R, U), sums its own entries and applies fold_dense_entry.  The upper half of the threads own an entry each and the pseudo rows'
+// entries are dealt to all of them: two replica sums of 64 loads per thread with one set, two or three with both.  The fold works IN PLACE on replica 0, and the
+// lower entries of the wanted pseudo rows are what every block reads and what the fold changes: nobody stores them until every block has read them — the block
+// that takes the last ticket (taken right behind a block's own reads, so no block ever waits) stores them from its LDS copy.  An unwanted set's pseudo rows are
+// structurally zero in this pass (nothing evaluates its family) and are not read.
+__device__ __forceinline__ void fold_dense_closed_block(const DevCommon& cm, int blk, int n_rep, int set0, int set1, int* ticket) {
+  extern __shared__ double Lf[];   // R[12][n], U[12][n], gp[12]
+  __shared__ int s_last;
+  const int n = cm.nbd, pp = cm.nbd_solve, n2 = n * n, tid = threadIdx.x;
+  double* R = Lf; double* U = Lf + 12 * n;
+#ifdef LVX_KTIME_FOLD
+  long long kt_[6] = {0, 0, 0, 0, 0, 0}; long long kt0_ = __builtin_amdgcn_s_memtime(); const long long kts_ = kt0_;
+#define FKT(i) { const long long n_ = __builtin_amdgcn_s_memtime(); kt_[i] += n_ - kt0_; kt0_ = n_; }
+#else
+#define FKT(i)
+#endif
+  const unsigned want = (1u << set0) | (set1 >= 0 ? 1u << set1 : 0u);
+  for (int e = tid; e < 24 * n + 12; e += 256) Lf[e] = 0.0;
+  __syncthreads();
+  fold_load_U(cm, want, U, n);
+  // own entry, then the pseudo rows of the wanted sets: row pp + k up to its diagonal, the corner's upper part by symmetry
+  const int i = tid >= 256 - LVX_FOLD_OWN ? blk * LVX_FOLD_OWN + tid - (256 - LVX_FOLD_OWN) : n2, a = i / n, b = i % n;
+  const bool own = i < n2 && !(a >= b && a >= pp && ((want >> ((a - pp) / 6)) & 1u));   // lower entries of the wanted pseudo rows belong to the last ticket
+  const double S = own ? strided_sum64(cm.C + i, (size_t)n2, cm.nrep) : 0.0;
+  const int k_first = set1 >= 0 ? 0 : 6 * set0, n_items = (set1 >= 0 ? 12 : 6) * n;
+  for (int e = tid; e < n_items; e += 256) {
+    const int k = k_first + e / n, x = e % n;
+    if (x > pp + k) continue;
+    const double v = strided_sum64(cm.C + (size_t)(pp + k) * n + x, (size_t)n2, cm.nrep);
+    R[k * n + x] = v;
+    if (x >= pp && x != pp + k) R[(x - pp) * n + pp + k] = v;   // (that row's own loads stop at its diagonal: one writer)
+  }
+  FKT(0)
+  __threadfence();
+  __syncthreads();   // R, U complete; every read of the pseudo rows by this block has returned
+  if (tid == 0) { const int t = atomicAdd(ticket, 1); s_last = t == n_rep - 1; if (s_last) *ticket = 0; }
+  FKT(1)
+  if (own) cm.C[i] = a >= b ? fold_dense_entry(a, b, S, R, U, n, pp) : S;   // (the upper triangle holds plain sums, as the replica kernel leaves them)
+  FKT(2)
+  __syncthreads();
+  if (s_last) {
+    for (int e = tid; e < n_items; e += 256) {
+      const int k = k_first + e / n, x = e % n;
+      if (x <= pp + k) cm.C[(size_t)(pp + k) * n + x] = fold_dense_entry(pp + k, x, R[k * n + x], R, U, n, pp);
+    }
+  }
+  FKT(3)
+#ifdef LVX_KTIME_FOLD
+  if (tid == 0 && (blk == 0 || blk == n_rep - 1 || s_last))
+    printf("FKT fold replica blk %d last %d: sums+rows %lld ticket %lld own %lld pseudo %lld | total %lld (ticks of s_memtime)\n", blk, s_last, kt_[0], kt_[1], kt_[2], kt_[3], (long long)__builtin_amdgcn_s_memtime() - kts_);
+#endif
+}
+// The gradient block of k_fold_all: g' = g + U^T g_pseudo, one entry per thread (nobody else reads the gradient's replicas), and the cost.
+__device__ __forceinline__ void fold_grad_block(const DevCommon& cm, int set0, int set1) {
+  extern __shared__ double Lf[];
+  const int n = cm.nbd, pp = cm.nbd_solve, j = threadIdx.x;
+  double* U = Lf + 12 * n; double* gp = Lf + 24 * n;
+  for (int e = j; e < 12 * n + 12; e += 256) U[e] = 0.0;
+  __syncthreads();
+  fold_load_U(cm, (1u << set0) | (set1 >= 0 ? 1u << set1 : 0u), U, n);
+  double Sg = 0.0;
+  if (j <= n) Sg = j < n ? strided_sum64(cm.gc + j, (size_t)n, cm.nrep) : strided_sum64(cm.cost, 1, cm.nrep);
+  if (j >= pp && j < n) gp[j - pp] = Sg;
+  __syncthreads();
+  if (j < n) cm.gc[j] = fold_dense_grad(j, Sg, gp, U, n);
+  else if (j == n) cm.cost[0] = Sg;
+}
+// The whole fold in ONE launch: blocks [0, n_rep) fold the dense border block in closed form, LVX_FOLD_OWN entries each and none waiting for another
+// (fold_dense_closed_block), block n_rep folds the gradient and sums the cost; blocks behind them fold the border rows of set `set0` (then of `set1` if >= 0).
+// Before: replica sums 10 us -> ticket -> ONE workgroup folding the dense block in LDS, 17 us, beside 17 us of border rows; SERIAL and a cost-only pass still run
+// those three kernels.
+__global__ __launch_bounds__(256) void k_fold_all(DevCommon cm, int n_rep, int n_rows, int set0, int store0, int set1, int store1, int* ticket) {
+  const int b = blockIdx.x;
+  if (b < n_rep) { fold_dense_closed_block(cm, b, n_rep, set0, set1, ticket); return; }
+  if (b == n_rep) { fold_grad_block(cm, set0, set1); return; }
+  const int r = b - n_rep - 1;
+#ifdef LVX_KTIME_FOLD
+  const long long kts_ = __builtin_amdgcn_s_memtime();
+#endif
   fold_border_rows_block(cm, set0, r, store0 != 0);
   if (set1 >= 0) fold_border_rows_block(cm, set1, r, store1 != 0);   // the two sets may share hub rows: the same thread folds them one after the other
+#ifdef LVX_KTIME_FOLD
+  if (threadIdx.x == 0 && (r == 0 || r == n_rows / 2 || r == n_rows - 1)) printf("FKT fold border-row blk %d of %d: total %lld\n", r, n_rows, (long long)__builtin_amdgcn_s_memtime() - kts_);
+#endif
 }
 // ---------------------------------------------------------------------------------------------------------
 // host side
@@ -2746,7 +2864,7 @@ int ensure_layout(lvx_ctx* ctx) {
   if ((rc = upload_pairs(ctx, ctx->d_pairs[5], CS_NC + tC, cat(range(0, 24), range(48, 60 + tC))))) return rc;
   if (ctx->lp.n > 0 && (rc = upload_pairs(ctx, ctx->d_pairs_lp, LPOS_NC + tL, cat(range(0, 24), range(48, 54 + tL))))) return rc;
   ctx->force_legacy = false; ctx->fb_on = false; ctx->fb_mask = 0; ctx->fallback_rows = 0;
-  { static const int zero[2] = {0, 0}; if ((rc = upload_tmp(ctx, ctx->d_zero, zero, 8))) return rc; }   // [0]: identity permutation of the single prior block, [1]: ticket of k_fold_all (returns to zero by itself)
+  { static const int zero[2] = {0, 0}; if ((rc = upload_tmp(ctx, ctx->d_zero, zero, 8))) return rc; }   // [0]: identity permutation of the single prior block, [1]: ticket of k_fold_all's pseudo rows (returns to zero by itself)
   if ((rc = dev_alloc(ctx, ctx->d_imu_rtab, (size_t)64 * (ImuG::NTP * 4 + ImuA::NTP * 4) * 4))) return rc;
   hipLaunchKernelGGL(k_imu_rtab, dim3(1), dim3(64), 0, ctx->stream, (int*)ctx->d_imu_rtab.p);
   ctx->cfg_version++;   // captured evaluation graphs of the previous layout are stale
@@ -2845,6 +2963,9 @@ __global__ __launch_bounds__(256) void k_clear(ClearList cl, BandClear bc, int n
     }
     for (; i < nw; i += stride) cl.p[b][i] = make_uint4(0u, 0u, 0u, 0u);
   }
+#ifdef LVX_KTIME_FOLD
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) printf("HKT k_clear: last clear block (%u) ends at %lld\n", blockIdx.x, (long long)__builtin_amdgcn_s_memtime());
+#endif
 }
 
 // k_family with or without the per-block records (EXP)
@@ -2972,8 +3093,25 @@ template <class FT> static int launch_mfma(Pass& p, const FT& fam, int chunk_slo
   if constexpr ((int)FT::OCC == 1) return p.xb ? launch_mfma_occ<FT, 1, true>(p, fam, chunk_slot, stream, row0) : launch_mfma_occ<FT, 1, false>(p, fam, chunk_slot, stream, row0);
   else return p.xb ? launch_mfma_occ<FT, 2, true>(p, fam, chunk_slot, stream, row0) : launch_mfma_occ<FT, 2, false>(p, fam, chunk_slot, stream, row0);
 }
+// DETERMINISTIC: a fallback list in ascending row order.  The fused kernels append to it in the order their atomics arrive, and the exact kernel forms its segments and
+// adds their sums in list order: two passes with the same rows in another order differ in the last bits of the entries that several segments share (the hub columns).
+// One workgroup, rank sort in LDS (the rows of a list are distinct).  Lists of more than 64 rows still take several workgroups of the exact kernel, which add to the band
+// in no fixed order: those stay outside deterministic mode.
+__global__ __launch_bounds__(256) void k_fb_sort(int* rows, const int* nrows, int cap) {
+  __shared__ int a[LVX_FB_CAP];
+  const int n = min(*nrows, min(cap, LVX_FB_CAP));
+  for (int i = threadIdx.x; i < n; i += 256) a[i] = rows[i];
+  __syncthreads();
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const int v = a[i];
+    int r = 0;
+    for (int j = 0; j < n; ++j) r += (a[j] < v || (a[j] == v && j < i)) ? 1 : 0;
+    rows[r] = v;
+  }
+}
 // the exact per-segment kernel over family f's fallback list, on stream s (row-level fallback: enabled after the first pass that needed it)
 template <class F, int PW> static void launch_family_list(Pass& p, int f, int list, hipStream_t s, const F& fam) {
+  if (p.det) hipLaunchKernelGGL(k_fb_sort, dim3(1), dim3(256), 0, s, const_cast<int*>(p.fb_rows(list)), p.fb_cnt(list), LVX_FB_CAP);
   launch_family<F, PW>(p.xb, dim3((unsigned)(LVX_FB_CAP / 64)) /* the list's capacity: the kernel reads the count */, dim3(64 * PW), s, fam, p.cm, (const uint16_t*)p.ctx->d_pairs[f].p, (long long)p.ctx->fam_row0[f], p.fb_rows(list), p.fb_cnt(list));
 }
 // the per-segment kernel over the whole of family f, on the chain
@@ -3081,7 +3219,8 @@ template <class Acc, class Fam> static int step_lidar(Pass& p, int f, bool fused
     if ((rc = launch_mfma(p, acc, f, p.st, ctx->fam_row0[f]))) return rc;
     if (listed) { if ((rc = p.fb_fork())) return rc;
       ProfScope psf(ctx, LVX_KERNEL_FIXUP, p.s_fb);
-      launch_family_list<Fam, LVX_PW>(p, f, f, p.s_fb, fam);
+      if (p.det) launch_family_list<Fam, 1>(p, f, f, p.s_fb, fam);   // one wavefront: two local columns on one tangent index (merged hub segment) add to the same entry in program order
+      else launch_family_list<Fam, LVX_PW>(p, f, f, p.s_fb, fam);
     }
   } else launch_family_all<Fam, 1>(p, f, fam);
   return p.xb_copy(f, listed ? p.s_fb : p.st);
@@ -3168,18 +3307,18 @@ template <bool T> static int step_reproj_tau(Pass& p) {
   return p.xb_copy(LVX_FAM_REPROJ, p.st);
 }
 static int step_reproj(Pass& p) { return p.ctx->rep.n <= 0 ? LVX_OK : with_tau(p.tauC, [&](auto T) { return step_reproj_tau<decltype(T)::value>(p); }); }
-// replica sums -> dense block (the last replica block to finish) and the border-row fold (Bd, streaming; disjoint buffers) in one launch
+// the dense block folded in closed form by the blocks that sum its replicas, and the border-row fold (Bd, streaming; disjoint buffers), in one launch
 static int step_fold(Pass& p) {
   lvx_ctx* ctx = p.ctx; hipStream_t st = p.st; const DevCommon& cm = p.cm; const bool fast_surf = p.fast_surf, fast_cs = p.fast_cs;
   ProfScope ps(ctx, LVX_KERNEL_FOLD);
   const bool fold_fast = (p.what & LVX_EVAL_NORMAL_EQ) && (fast_surf || fast_cs);
   const unsigned n_rep_blk = (unsigned)((ctx->nbd_ext * ctx->nbd_ext + 255) / 256);
-  if (fold_fast && ctx->nb > 0 && !ctx->sw.serial) {
+  if (fold_fast && ctx->nb > 0 && !ctx->sw.serial && ctx->nbd_ext <= 255) {   // (the gradient block folds the gradient and the cost one entry per thread; 24 n + 12 doubles of LDS)
     const unsigned n_rows_blk = (unsigned)((ctx->nb + 255) / 256);
     const int set0 = fast_surf ? 0 : 1, set1 = (fast_surf && fast_cs) ? 1 : -1;
-    const size_t lds = ((size_t)ctx->nbd_ext * ctx->nbd_ext + ctx->nbd_ext) * 8;
-    LVX_HIP(ctx, hipFuncSetAttribute((const void*)k_fold_all, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_fold_all, dim3(n_rep_blk + n_rows_blk), dim3(256), lds, st, cm, (int)n_rep_blk, (int)n_rows_blk, set0, 1, set1, 0, (int*)ctx->d_zero.p + 1);
+    const size_t lds = ((size_t)2 * LVX_FOLD_NP * ctx->nbd_ext + LVX_FOLD_NP) * 8;
+    const unsigned n_dense_blk = (unsigned)((ctx->nbd_ext * ctx->nbd_ext + LVX_FOLD_OWN - 1) / LVX_FOLD_OWN);
+    hipLaunchKernelGGL(k_fold_all, dim3(n_dense_blk + 1 + n_rows_blk), dim3(256), lds, st, cm, (int)n_dense_blk, (int)n_rows_blk, set0, 1, set1, 0, (int*)ctx->d_zero.p + 1);
     return LVX_OK;
   }
   hipStream_t s_fold = (fold_fast && p.side_on) ? ctx->fam_stream[0] : st;
