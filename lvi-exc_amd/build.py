@@ -13,12 +13,24 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # residual / Jacobian / solver kernels are compared at 1e-12 relative and use FMAs.  The map rendering's projection rounds as the g++ build of its header does
 # (tests/native/render_host_check.cpp): records are compared byte for byte.  The trajectory queries share lvx_pose.h with both: a sensor pose is the same bits in all three.
 # The rotation initialisation's sums and 4 x 4 eigen-solver are held against the g++ build of lvx_rotinit.h (tests/native/rotinit_host_check.cpp).
-CONTRACT = {"lvx_upstream.hip": "off", "lvx_render.hip": "off", "lvx_traj.hip": "off", "lvx_rotinit.hip": "off"}
+# Every csrc/*.hip is named here: "off", or DEFAULT (fast unless LVX_CONTRACT overrides it).  A source that is not listed is an error, never a silent default.
+DEFAULT = None
+CONTRACT = {"lvx_upstream.hip": "off", "lvx_render.hip": "off", "lvx_traj.hip": "off", "lvx_rotinit.hip": "off",
+            "lvx_api.hip": DEFAULT, "lvx_bcr.hip": DEFAULT, "lvx_eval.hip": DEFAULT, "lvx_solver.hip": DEFAULT, "lvx_stats.hip": DEFAULT}
 DEFAULT_CONTRACT = os.environ.get("LVX_CONTRACT", "fast")
 
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+
+
+def contract(src):
+    """-ffp-contract mode of one source (path or file name, with or without .hip)."""
+    name = os.path.basename(src)
+    name = name if name.endswith(".hip") else name + ".hip"
+    if name not in CONTRACT:
+        raise RuntimeError("%s has no entry in build.py's CONTRACT table: say 'off' or DEFAULT" % name)
+    return CONTRACT[name] or DEFAULT_CONTRACT
 
 
 def stale():
@@ -34,9 +46,10 @@ def build(force=False, verbose=False):
         return OUT
     objs = []
     procs = []
-    for src in sources():
+    modes = [(src, contract(src)) for src in sources()]   # (raises before anything is compiled)
+    for src, mode in modes:
         obj = os.path.join(CSRC, os.path.basename(src)[:-4] + ".o")
-        cmd = [HIPCC] + FLAGS + ["-ffp-contract=" + CONTRACT.get(os.path.basename(src), DEFAULT_CONTRACT), "-c", src, "-o", obj]
+        cmd = [HIPCC] + FLAGS + ["-ffp-contract=" + mode, "-c", src, "-o", obj]
         if verbose:
             cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
             print(" ".join(cmd), flush=True)
@@ -51,4 +64,7 @@ def build(force=False, verbose=False):
 
 
 if __name__ == "__main__":
+    if "--contract" in sys.argv:   # python build.py --contract FILE: the mode FILE is built with (tools/build_variant.sh)
+        print(contract(sys.argv[sys.argv.index("--contract") + 1]))
+        sys.exit(0)
     print(build(force="--force" in sys.argv, verbose="--verbose" in sys.argv))

@@ -2010,6 +2010,66 @@ __global__ void k_transform_append(const float4* __restrict__ scan, int n, Pose1
 
 using namespace lvx;
 
+// ---- one view per device buffer layout: every host function below takes its pointers from these ----------------------------------------------------------------------
+// Every pointer carved from lvx_ctx::Voxels.  A build over n points allocates for n leaves (a leaf holds at least one point), so the leaf arrays are strided by
+// that CAPACITY (cap = n), never by the leaf count:
+//   keys, vals  [2 n] each: the sort's input in the first halves, the sorted keys / point ids in the second
+//   runs        [n unused | counts n | offs n | look-back states of k_vx_leaf: one 64-bit word per tile of 256 sorted positions, 8-byte aligned]
+//   leaf_i      [key | n] x cap        leaf_d  [mean 3 | cov 9 | icov 9 | evecs 9 | evals 3] x cap        leaf_f  [centroid 3] x cap
+//   misc        [extents 3 x min, 3 x max, ticket | VxInfo at byte 64]
+// g is the host's copy of the grid geometry: valid after vox_info.
+struct VoxelView {
+  VxGrid g; float leaf; int min_pts, cap;
+  unsigned* keys; unsigned* sorted_keys; int* ids; int* sorted_ids; unsigned* counts; unsigned* offs; unsigned long long* lookback;
+  int* leaf_key; int* leaf_n; double* mean; double* cov; double* icov; double* evecs; double* evals; float* centroid; int* cells;
+  int* extents; VxInfo* info;
+};
+static VoxelView vox_view(const lvx_ctx* c) {
+  const lvx_ctx::Voxels& V = c->vox;
+  const size_t n = (size_t)V.n_points, cap = (size_t)V.cap;
+  VoxelView v;
+  std::memcpy(&v.g, V.grid, sizeof(v.g)); v.leaf = V.leaf; v.min_pts = V.min_pts; v.cap = V.cap;
+  v.keys = (unsigned*)V.keys.p; v.sorted_keys = v.keys + n; v.ids = (int*)V.vals.p; v.sorted_ids = v.ids + n;
+  v.counts = (unsigned*)V.runs.p + n; v.offs = v.counts + n; v.lookback = (unsigned long long*)((unsigned*)V.runs.p + ((n * 3 + 1) & ~(size_t)1));
+  v.leaf_key = (int*)V.leaf_i.p; v.leaf_n = v.leaf_key + cap;
+  v.mean = (double*)V.leaf_d.p; v.cov = v.mean + 3 * cap; v.icov = v.cov + 9 * cap; v.evecs = v.icov + 9 * cap; v.evals = v.evecs + 9 * cap;
+  v.centroid = (float*)V.leaf_f.p; v.cells = (int*)V.cells.p;
+  v.extents = (int*)V.misc.p; v.info = (VxInfo*)((char*)V.misc.p + 64);
+  return v;
+}
+// The association grid of a plane table: d_assoc[0] = [AssocGrid | cell counts | cell offsets (+ total) | cursors | plane AoS, 80 bytes per plane], the cells' lists in
+// d_assoc[1].  planes > 0 (re)allocates d_assoc[0] for that many planes first; 0 views the buffer as it is.
+struct AssocGridView { AssocGrid* geom; int* cell_cnt; int* cell_off; int* cursor; double* aos; int* list; };
+static int assoc_grid_view(lvx_ctx* c, int planes, AssocGridView* A) {
+  const size_t grid_bytes = (sizeof(AssocGrid) + (size_t)(3 * SA_CELLS + 8) * 4 + 15) & ~(size_t)15;
+  if (planes > 0) { const int rc = dev_alloc(c, c->d_assoc[0], grid_bytes + (size_t)planes * 80); if (rc) return rc; }
+  A->geom = (AssocGrid*)c->d_assoc[0].p; A->cell_cnt = (int*)(A->geom + 1); A->cell_off = A->cell_cnt + SA_CELLS; A->cursor = A->cell_off + SA_CELLS + 1;
+  A->aos = (double*)((char*)c->d_assoc[0].p + grid_bytes); A->list = (int*)c->d_assoc[1].p;
+  return LVX_OK;
+}
+// The hit masks of `rings` (scan, plane, ring) triples of W points (d_assoc[3]): one bit per point, one occupancy word per ring.  Nothing else writes the buffer and
+// k_assoc_select leaves it zero, so it is cleared only when it is (re)allocated or re-shaped.
+struct HitMask { unsigned* bits; unsigned long long* occ; int wpr, oshift; };
+static int assoc_hit_mask(lvx_ctx* c, size_t rings, int W, HitMask* M) {
+  const int wpr = (W + 31) / 32;
+  const size_t bits_bytes = (rings * wpr * 4 + 7) & ~(size_t)7, bytes = bits_bytes + rings * 8;
+  if (!c->d_assoc[3].p || c->d_assoc[3].bytes < bytes || c->assoc_rings != rings || c->assoc_wpr != wpr) {
+    const int rc = dev_alloc(c, c->d_assoc[3], bytes); if (rc) return rc;
+    LVX_HIP(c, hipMemsetAsync(c->d_assoc[3].p, 0, c->d_assoc[3].bytes, c->stream));
+    c->assoc_rings = rings; c->assoc_wpr = wpr;
+  }
+  M->bits = (unsigned*)c->d_assoc[3].p; M->occ = (unsigned long long*)((char*)c->d_assoc[3].p + bits_bytes);
+  M->wpr = wpr; M->oshift = wpr > 64 ? 1 : 0;   // (W <= SA_WMAX = 4096: at most 128 mask words per ring, two per occupancy bit)
+  return LVX_OK;
+}
+// The SurfelPoint arrays of lvx_data_association (d_da[7]), strided by the CAPACITY cap = every scan point: [pt 3 | pt_map 3 | t] doubles, then the plane ids.
+// alloc: (re)allocate for cap points first.
+static int surfel_point_arrays(lvx_ctx* c, size_t cap, bool alloc, SurfelOut* o) {
+  if (alloc) { const int rc = dev_alloc(c, c->d_da[7], cap * (24 + 24 + 8 + 4) + 64); if (rc) return rc; }
+  o->pt = (double*)c->d_da[7].p; o->pt_map = o->pt + 3 * cap; o->t = o->pt_map + 3 * cap; o->plane = (int*)(o->t + cap);
+  return LVX_OK;
+}
+
 extern "C" {
 
 // Scan registration of a batch of sweeps: six launches (count, bucket, gather, curvature, classify, compact; grid.y = sweep).  No host round trip in between: the
@@ -2216,30 +2276,37 @@ static int vx_keys_sort_enqueue(lvx_ctx* c, const float4* d_pts, int n, const Vx
 static int voxel_enqueue(lvx_ctx* c, const float4* d_pts, int n, float leaf, int min_pts, double eig_mult) {
   hipStream_t st = c->stream;
   lvx_ctx::Voxels& V = c->vox;
-  int* d_mm = (int*)V.misc.p;
-  VxInfo* d_info = (VxInfo*)((char*)V.misc.p + 64);
-  const VxSort S{(unsigned*)V.keys.p, (int*)V.vals.p, V.tmp.p, V.tmp_bytes[0], V.sort_bits};
-  const unsigned* k_out = S.keys + n; const int* v_out = S.vals + n;
-  unsigned* counts = (unsigned*)V.runs.p + n; unsigned* offs = counts + n;   // ([0, n) unused since the run-length encode left)
-  unsigned long long* lbs = (unsigned long long*)((unsigned*)V.runs.p + (((size_t)n * 3 + 1) & ~(size_t)1));   // look-back states of k_vx_leaf, one per tile
-  const size_t cap = (size_t)V.cap;
+  const VoxelView X = vox_view(c);   // (voxel_build_device: n = V.n_points = V.cap)
+  const VxSort S{X.keys, X.ids, V.tmp.p, V.tmp_bytes[0], V.sort_bits};
   const int n_tiles = (n + 255) / 256;
-  hipLaunchKernelGGL(k_vx_extent, dim3((unsigned)std::min(std::max(n / 4096, 64), 256)), dim3(256), 0, st, d_pts, n, d_mm, leaf, (long long)V.cells_cap, d_info, vx_sort_ghist(S, n));
+  hipLaunchKernelGGL(k_vx_extent, dim3((unsigned)std::min(std::max(n / 4096, 64), 256)), dim3(256), 0, st, d_pts, n, X.extents, leaf, (long long)V.cells_cap, X.info, vx_sort_ghist(S, n));
   const unsigned invalid = vx_sort_invalid(S);
-  { const int rc = vx_keys_sort_enqueue(c, d_pts, n, (const VxInfo*)d_info, S, (int*)V.cells.p, lbs, n_tiles); if (rc) return rc; }
-  int* lk = (int*)V.leaf_i.p; int* ln = lk + cap;
-  double* mean = (double*)V.leaf_d.p; double* cov = mean + 3 * cap; double* icov = cov + 9 * cap; double* evecs = icov + 9 * cap; double* evals = evecs + 9 * cap;
+  { const int rc = vx_keys_sort_enqueue(c, d_pts, n, (const VxInfo*)X.info, S, X.cells, X.lookback, n_tiles); if (rc) return rc; }
   // tile = 256 PT sorted positions per workgroup, PT chosen so that the launch is ONE round of resident workgroups (4 per CU at 37 KB of LDS = 1 024) as long as the
   // cloud allows: the workgroup is a latency chain (keys -> counts of all predecessors -> points -> sums -> eigen-solve) and a second round repeats it
   auto launch_leaf = [&](auto pt) {
     constexpr int PT = decltype(pt)::value;
-    hipLaunchKernelGGL(k_vx_leaf<PT>, dim3((unsigned)((n + 256 * PT - 1) / (256 * PT))), dim3(256), 0, st, d_pts, k_out, v_out, n, invalid, lbs, min_pts, eig_mult, d_info, (int*)V.cells.p, lk, ln,
-                       counts, offs, mean, cov, icov, evecs, evals, (float*)V.leaf_f.p, (VxInfo*)V.h_info);
+    hipLaunchKernelGGL(k_vx_leaf<PT>, dim3((unsigned)((n + 256 * PT - 1) / (256 * PT))), dim3(256), 0, st, d_pts, (const unsigned*)X.sorted_keys, (const int*)X.sorted_ids, n, invalid, X.lookback, min_pts, eig_mult, X.info,
+                       X.cells, X.leaf_key, X.leaf_n, X.counts, X.offs, X.mean, X.cov, X.icov, X.evecs, X.evals, X.centroid, (VxInfo*)V.h_info);
   };
   if (n > 524288) launch_leaf(std::integral_constant<int, 4>{});
   else if (n > 262144) launch_leaf(std::integral_constant<int, 2>{});
   else launch_leaf(std::integral_constant<int, 1>{});
   LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+// What a chain that starts with k_vx_extent needs before its first launch (the covariance grid's, the centroid filter's): the extents + VxInfo buffer in its start state
+// (k_vx_extent's last workgroup restores it after every run), the floor of the cell capacity — 262 143 cells (1 MB; 18-bit keys = two 9-bit sort passes): a 32 m x 32 m x
+// 32 m map at 0.5 m; grown on demand — and the width of the sorted keys: keys < cells <= capacity <= 2^31 - 1, the invalid key = 2^bits - 1 >= capacity above them
+static int vx_chain_start(lvx_ctx* c, DevBuf& extents, long long& cells_cap, int* sort_bits) {
+  if (cells_cap < (1 << 18) - 1) cells_cap = (1 << 18) - 1;
+  int bits = 1; while ((1ll << bits) - 1 < cells_cap && bits < 31) ++bits;
+  *sort_bits = bits;
+  if (extents.p) return LVX_OK;
+  const int rc = dev_alloc(c, extents, 64 + sizeof(VxInfo)); if (rc) return rc;
+  const int mm0[7] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
+  LVX_HIP(c, hipMemcpyAsync(extents.p, mm0, sizeof(mm0), hipMemcpyHostToDevice, c->stream));
+  LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
 }
 static int voxel_build_device(lvx_ctx* c, const float4* d_pts, int n, float leaf, int min_pts, double eig_mult) {
@@ -2250,15 +2317,7 @@ static int voxel_build_device(lvx_ctx* c, const float4* d_pts, int n, float leaf
   std::memset(&V.grid, 0, sizeof(V.grid));
   if (n == 0) return LVX_OK;
   if (!V.h_info) LVX_HIP(c, hipHostMalloc(&V.h_info, sizeof(VxInfo), hipHostMallocDefault));
-  if (V.cells_cap < (1 << 18) - 1) V.cells_cap = (1 << 18) - 1;   // 262 143 cells (1 MB; 18-bit keys = two 9-bit sort passes): a 32 m x 32 m x 32 m map at 0.5 m; grown on demand (vox_info)
-  int bits = 1; while ((1ll << bits) - 1 < (long long)V.cells_cap && bits < 31) ++bits;   // keys < cells <= capacity <= 2^31 - 1, the invalid key = 2^bits - 1 >= capacity above them
-  V.sort_bits = bits;
-  if (!V.misc.p) {   // extents in their start state (k_vx_extent's last workgroup restores it after every build)
-    if ((rc = dev_alloc(c, V.misc, 64 + sizeof(VxInfo)))) return rc;
-    const int mm0[7] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
-    LVX_HIP(c, hipMemcpyAsync(V.misc.p, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
-    LVX_HIP(c, hipStreamSynchronize(st));
-  }
+  if ((rc = vx_chain_start(c, V.misc, V.cells_cap, &V.sort_bits))) return rc;
   if ((rc = dev_alloc(c, V.keys, (size_t)n * 4 * 2))) return rc;
   if ((rc = dev_alloc(c, V.vals, (size_t)n * 4 * 2))) return rc;
   if ((rc = dev_alloc(c, V.runs, ((size_t)n * 3 + 2 + 2 * (((size_t)n + 255) / 256) + 8) * 4))) return rc;
@@ -2352,21 +2411,15 @@ static int downsample_device(lvx_ctx* c, const float4* d_pts, int n, float leaf,
   if (n == 0) return LVX_OK;
   int rc;
   if (!c->ds_pinned) LVX_HIP(c, hipHostMalloc(&c->ds_pinned, sizeof(DsHost), hipHostMallocDefault));
-  if (c->ds_cells_cap < (1 << 18) - 1) c->ds_cells_cap = (1 << 18) - 1;
-  if (!c->d_ds[0].p) {   // extents in their start state (k_vx_extent's last workgroup restores it)
-    if ((rc = dev_alloc(c, c->d_ds[0], 64 + sizeof(VxInfo)))) return rc;
-    const int mm0[7] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000, 0};
-    LVX_HIP(c, hipMemcpyAsync(c->d_ds[0].p, mm0, sizeof(mm0), hipMemcpyHostToDevice, st));
-    LVX_HIP(c, hipStreamSynchronize(st));
-  }
   const int n_tiles = (n + 255) / 256;
   if ((rc = dev_alloc(c, c->d_ds[1], (size_t)n * 4 * 2))) return rc;
   if ((rc = dev_alloc(c, c->d_ds[2], (size_t)n * 4 * 2))) return rc;
   if ((rc = dev_alloc(c, c->d_ds[4], (size_t)n_tiles * 4))) return rc;
-  int* d_mm = (int*)c->d_ds[0].p;
-  VxInfo* d_info = (VxInfo*)((char*)c->d_ds[0].p + 64);
   for (int round = 0;; ++round) {
-    int bits = 1; while ((1ll << bits) - 1 < c->ds_cells_cap && bits < 31) ++bits;   // keys < cells <= capacity <= 2^31 - 1 < the invalid key 2^bits - 1
+    int bits;
+    if ((rc = vx_chain_start(c, c->d_ds[0], c->ds_cells_cap, &bits))) return rc;   // (a second round: the key range has grown)
+    int* d_mm = (int*)c->d_ds[0].p;
+    VxInfo* d_info = (VxInfo*)((char*)c->d_ds[0].p + 64);
     VxSort S{(unsigned*)c->d_ds[1].p, (int*)c->d_ds[2].p, nullptr, 0, bits};
     if (n > VX_OWN_SORT_MAX) LVX_HIP(c, rocprim::radix_sort_pairs(nullptr, S.rocprim_bytes, S.keys, S.keys + n, S.vals, S.vals + n, (size_t)n, 0, (unsigned)bits, st));
     if ((rc = dev_alloc(c, c->d_ds[3], vx_sort_tmp_bytes(S.rocprim_bytes)))) return rc;
@@ -2422,36 +2475,32 @@ int lvx_voxel_get(lvx_ctx* c, int32_t* leaf_key, int32_t* leaf_n, double* mean, 
   LVX_HIP(c, hipSetDevice(c->device));
   { const int rc = vox_info(c); if (rc) return rc; }
   LVX_HIP(c, hipStreamSynchronize(c->stream));
-  const lvx_ctx::Voxels& V = c->vox;
-  const size_t nl = (size_t)V.n_leaves, n = (size_t)V.n_points, cap = (size_t)V.cap;
+  const size_t nl = (size_t)c->vox.n_leaves, n = (size_t)c->vox.n_points;
   if (nl == 0) { if (offsets) offsets[0] = 0; return LVX_OK; }
-  const int* lk = (const int*)V.leaf_i.p;
-  const double* d = (const double*)V.leaf_d.p;
-  if (leaf_key) LVX_HIP(c, hipMemcpy(leaf_key, lk, nl * 4, hipMemcpyDeviceToHost));
-  if (leaf_n) LVX_HIP(c, hipMemcpy(leaf_n, lk + cap, nl * 4, hipMemcpyDeviceToHost));
-  if (mean) LVX_HIP(c, hipMemcpy(mean, d, nl * 24, hipMemcpyDeviceToHost));
-  if (cov) LVX_HIP(c, hipMemcpy(cov, d + 3 * cap, nl * 72, hipMemcpyDeviceToHost));
-  if (icov) LVX_HIP(c, hipMemcpy(icov, d + 12 * cap, nl * 72, hipMemcpyDeviceToHost));
-  if (evecs) LVX_HIP(c, hipMemcpy(evecs, d + 21 * cap, nl * 72, hipMemcpyDeviceToHost));
-  if (evals) LVX_HIP(c, hipMemcpy(evals, d + 30 * cap, nl * 24, hipMemcpyDeviceToHost));
-  if (centroid) LVX_HIP(c, hipMemcpy(centroid, V.leaf_f.p, nl * 12, hipMemcpyDeviceToHost));
+  const VoxelView X = vox_view(c);
+  if (leaf_key) LVX_HIP(c, hipMemcpy(leaf_key, X.leaf_key, nl * 4, hipMemcpyDeviceToHost));
+  if (leaf_n) LVX_HIP(c, hipMemcpy(leaf_n, X.leaf_n, nl * 4, hipMemcpyDeviceToHost));
+  if (mean) LVX_HIP(c, hipMemcpy(mean, X.mean, nl * 24, hipMemcpyDeviceToHost));
+  if (cov) LVX_HIP(c, hipMemcpy(cov, X.cov, nl * 72, hipMemcpyDeviceToHost));
+  if (icov) LVX_HIP(c, hipMemcpy(icov, X.icov, nl * 72, hipMemcpyDeviceToHost));
+  if (evecs) LVX_HIP(c, hipMemcpy(evecs, X.evecs, nl * 72, hipMemcpyDeviceToHost));
+  if (evals) LVX_HIP(c, hipMemcpy(evals, X.evals, nl * 24, hipMemcpyDeviceToHost));
+  if (centroid) LVX_HIP(c, hipMemcpy(centroid, X.centroid, nl * 12, hipMemcpyDeviceToHost));
   if (offsets) {
-    const unsigned* offs = (const unsigned*)V.runs.p + 2 * n;
-    const unsigned* counts = (const unsigned*)V.runs.p + n;
-    LVX_HIP(c, hipMemcpy(offsets, offs, nl * 4, hipMemcpyDeviceToHost));
-    unsigned lc = 0; LVX_HIP(c, hipMemcpy(&lc, counts + (nl - 1), 4, hipMemcpyDeviceToHost));
+    LVX_HIP(c, hipMemcpy(offsets, X.offs, nl * 4, hipMemcpyDeviceToHost));
+    unsigned lc = 0; LVX_HIP(c, hipMemcpy(&lc, X.counts + (nl - 1), 4, hipMemcpyDeviceToHost));
     offsets[nl] = offsets[nl - 1] + (int)lc;
   }
-  if (point_ids && n > 0) LVX_HIP(c, hipMemcpy(point_ids, (const int*)V.vals.p + n, n * 4, hipMemcpyDeviceToHost));
+  if (point_ids && n > 0) LVX_HIP(c, hipMemcpy(point_ids, X.sorted_ids, n * 4, hipMemcpyDeviceToHost));
   return LVX_OK;
 }
 static int lookup_device(lvx_ctx* c, const float4* q_d, int nq, int* ids_d, int K) {
   { const int rc = vox_info(c); if (rc) return rc; }
   const lvx_ctx::Voxels& V = c->vox;
   if (!V.cells.p || V.n_leaves == 0) { LVX_HIP(c, hipMemsetAsync(ids_d, 0xff, (size_t)nq * 4 * K, c->stream)); return LVX_OK; }
-  VxGrid g; std::memcpy(&g, &V.grid, sizeof(g));
-  if (K == 7) hipLaunchKernelGGL(k_vx_lookup<7>, dim3((nq + 255) / 256), dim3(256), 0, c->stream, q_d, nq, V.leaf, V.min_pts, g, (const int*)V.cells.p, (const int*)V.leaf_i.p + V.cap, ids_d);
-  else hipLaunchKernelGGL(k_vx_lookup<1>, dim3((nq + 255) / 256), dim3(256), 0, c->stream, q_d, nq, V.leaf, V.min_pts, g, (const int*)V.cells.p, (const int*)V.leaf_i.p + V.cap, ids_d);
+  const VoxelView X = vox_view(c);
+  if (K == 7) hipLaunchKernelGGL(k_vx_lookup<7>, dim3((nq + 255) / 256), dim3(256), 0, c->stream, q_d, nq, X.leaf, X.min_pts, X.g, (const int*)X.cells, (const int*)X.leaf_n, ids_d);
+  else hipLaunchKernelGGL(k_vx_lookup<1>, dim3((nq + 255) / 256), dim3(256), 0, c->stream, q_d, nq, X.leaf, X.min_pts, X.g, (const int*)X.cells, (const int*)X.leaf_n, ids_d);
   LVX_HIP(c, hipGetLastError());
   return LVX_OK;
 }
@@ -2483,56 +2532,63 @@ int lvx_voxel_lookup1_d(lvx_ctx* c, int nq, const float* xyzi4_d, int32_t* leaf_
   return lookup_device(c, (const float4*)xyzi4_d, nq, leaf_ids1_d, 1);
 }
 
-// S scans [S][H][W] against one plane table; flags [S][H * W].  Work buffers (bitmasks 4 P H ceil(W / 32) bytes per scan, counts) live in d_assoc[3] — a buffer
-// nothing else writes, because it is cleared only when (re)allocated or re-shaped (k_assoc_select leaves it zero).
-// geometry, per-cell counts, offsets and lists of the association grid (d_assoc[0], d_assoc[1]); have = it is already built for this table
-static int assoc_grid_build(lvx_ctx* c, int P, const double* planes_d, bool have) {
-  if (have) return LVX_OK;
+// The association's launch sequences, once for the synchronous entry points below and for the one-stop round of lvx_data_association.  They only enqueue on the
+// context's stream; their caller synchronises.  P: launch extent (planes, or their capacity); P_d: device count behind that capacity (null: the extent is the count);
+// list_cap: entries the cells' lists may take (0x7fffffff: no bound, the lists are sized from the counted total); mirror: pinned words {map pose valid, planes, list
+// entries} the last launch writes for the host (null: nobody reads them).
+// The grid in two steps around the one thing a caller without a list capacity must learn from the device (the lists' total, at cell_off[SA_CELLS]): geometry + per-cell
+// counts + offsets, then the lists (A.list must hold them).
+static int assoc_grid_count_enqueue(lvx_ctx* c, int P, const double* planes_d, const int* P_d, int list_cap, AssocGridView* A) {
   c->assoc_map_ready = false;   // the grid buffers are about to hold another table's grid
+  const int rc = assoc_grid_view(c, std::max(P, 1), A); if (rc) return rc;
+  hipLaunchKernelGGL(k_assoc_grid_geom, dim3(1), dim3(256), 0, c->stream, P, planes_d, A->geom, P_d, A->cell_cnt);
+  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P + 127) / 128)), dim3(128), 0, c->stream, P, planes_d, (const AssocGrid*)A->geom, A->cell_cnt, A->cursor, (int*)nullptr, 0, A->aos, P_d, list_cap);
+  hipLaunchKernelGGL(k_assoc_grid_scan, dim3(1), dim3(1024), 0, c->stream, (const int*)A->cell_cnt, A->cell_off, A->cursor, list_cap);
+  return LVX_OK;
+}
+static void assoc_grid_fill_enqueue(lvx_ctx* c, int P, const double* planes_d, const int* P_d, int list_cap, const AssocGridView& A, int* mirror, const int* pose_valid) {
+  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P + 127) / 128)), dim3(128), 0, c->stream, P, planes_d, (const AssocGrid*)A.geom, A.cell_cnt, A.cursor, A.list, 1, (double*)nullptr, P_d, list_cap,
+                     mirror, pose_valid);
+}
+// hits + selection of S scans [S][H][W] against the grid A: flags [S][H * W]; flags_init (null or flags): k_assoc_hits writes the "no surfel" start state there itself
+static void assoc_hits_enqueue(lvx_ctx* c, const float4* scans_d, int S, int H, int W, int P, double radius, int sel, const AssocGridView& A, const HitMask& M, int* flags_init, int* flags_d) {
+  hipLaunchKernelGGL(k_assoc_hits, dim3((unsigned)((H * W + 255) / 256), (unsigned)S), dim3(256), 0, c->stream, scans_d, H, W, P, (const double*)A.aos, radius, (const AssocGrid*)A.geom, (const int*)A.cell_off,
+                     (const int*)A.list, M.bits, M.occ, M.wpr, M.oshift, flags_init);
+  hipLaunchKernelGGL(k_assoc_select, dim3((unsigned)(((size_t)S * P * H + 255) / 256)), dim3(256), 0, c->stream, M.bits, M.occ, S, H, W, P, M.wpr, M.oshift, sel, flags_d);
+}
+// the association grid of a plane table the host knows the size of: one host stop for the total of the cells' lists (their allocation)
+static int assoc_grid_build(lvx_ctx* c, int P, const double* planes_d) {
   int rc;
-  const size_t grid_bytes = (sizeof(AssocGrid) + (size_t)(3 * SA_CELLS + 8) * 4 + 15) & ~(size_t)15;
-  if ((rc = dev_alloc(c, c->d_assoc[0], grid_bytes + (size_t)P * 80))) return rc;
-  AssocGrid* gd = (AssocGrid*)c->d_assoc[0].p; int* ccnt = (int*)(gd + 1); int* coff = ccnt + SA_CELLS; int* ccur = coff + SA_CELLS + 1;
-  double* aos = (double*)((char*)c->d_assoc[0].p + grid_bytes);
-  hipLaunchKernelGGL(k_assoc_grid_geom, dim3(1), dim3(256), 0, c->stream, P, planes_d, gd, (const int*)nullptr, ccnt);
-  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P + 127) / 128)), dim3(128), 0, c->stream, P, planes_d, (const AssocGrid*)gd, ccnt, ccur, (int*)nullptr, 0, aos, (const int*)nullptr, 0x7fffffff);
-  hipLaunchKernelGGL(k_assoc_grid_scan, dim3(1), dim3(1024), 0, c->stream, (const int*)ccnt, coff, ccur, 0x7fffffff);
+  AssocGridView A;
+  if ((rc = assoc_grid_count_enqueue(c, P, planes_d, nullptr, 0x7fffffff, &A))) return rc;
   int total = 0;
-  LVX_HIP(c, hipMemcpyAsync(&total, coff + SA_CELLS, 4, hipMemcpyDeviceToHost, c->stream));
+  LVX_HIP(c, hipMemcpyAsync(&total, A.cell_off + SA_CELLS, 4, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
   c->assoc_list_total = total;
   if ((rc = dev_alloc(c, c->d_assoc[1], (size_t)std::max(total, 1) * 4))) return rc;
-  int* clist = (int*)c->d_assoc[1].p;
-  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P + 127) / 128)), dim3(128), 0, c->stream, P, planes_d, (const AssocGrid*)gd, ccnt, ccur, clist, 1, (double*)nullptr, (const int*)nullptr, 0x7fffffff);
+  A.list = (int*)c->d_assoc[1].p;
+  assoc_grid_fill_enqueue(c, P, planes_d, nullptr, 0x7fffffff, A, nullptr, nullptr);
   return LVX_OK;
 }
+// S scans [S][H][W] against one plane table; flags [S][H * W]
 static int assoc_device(lvx_ctx* c, const float4* scans_d, int S, int H, int W, int P, const double* planes_d, double radius, int sel, int* flags_d) {
   if (P <= 0 || H <= 0 || W <= 0 || S <= 2) LVX_HIP(c, hipMemsetAsync(flags_d, 0xff, (size_t)std::max(S, 0) * H * W * 4, c->stream));   // (S > 2: k_assoc_hits writes the start state itself)
   if (P <= 0 || H <= 0 || W <= 0 || S <= 0) return LVX_OK;
-  const int wpr = (W + 31) / 32;
-  const size_t rings = (size_t)S * P * H, bits_bytes = (rings * wpr * 4 + 7) & ~(size_t)7, bytes = bits_bytes + rings * 8;
-  const int oshift = wpr > 64 ? 1 : 0;   // (W <= SA_WMAX = 4096: at most 128 mask words per ring, two per occupancy bit)
+  const size_t rings = (size_t)S * P * H;
   int rc;
-  if (!c->d_assoc[3].p || c->d_assoc[3].bytes < bytes || c->assoc_rings != rings || c->assoc_wpr != wpr) {   // (re)allocated or re-shaped: clear once; k_assoc_select leaves it clean
-    if ((rc = dev_alloc(c, c->d_assoc[3], bytes))) return rc;
-    LVX_HIP(c, hipMemsetAsync(c->d_assoc[3].p, 0, c->d_assoc[3].bytes, c->stream));
-    c->assoc_rings = rings; c->assoc_wpr = wpr;
-  }
-  unsigned* bits = (unsigned*)c->d_assoc[3].p; unsigned long long* occ = (unsigned long long*)((char*)c->d_assoc[3].p + bits_bytes);
+  HitMask M;
+  if ((rc = assoc_hit_mask(c, rings, W, &M))) return rc;
   if (S <= 2) {   // a scan or two: all pairs beat the grid build
-    hipLaunchKernelGGL(k_assoc_hits_allpairs, dim3((unsigned)((H * W + 255) / 256), (unsigned)((P + SA_PC - 1) / SA_PC), (unsigned)S), dim3(256), 0, c->stream, scans_d, H, W, P, planes_d, radius, bits, occ, wpr, oshift);
-    hipLaunchKernelGGL(k_assoc_select, dim3((unsigned)((rings + 255) / 256)), dim3(256), 0, c->stream, bits, occ, S, H, W, P, wpr, oshift, sel, flags_d);
+    hipLaunchKernelGGL(k_assoc_hits_allpairs, dim3((unsigned)((H * W + 255) / 256), (unsigned)((P + SA_PC - 1) / SA_PC), (unsigned)S), dim3(256), 0, c->stream, scans_d, H, W, P, planes_d, radius, M.bits, M.occ, M.wpr, M.oshift);
+    hipLaunchKernelGGL(k_assoc_select, dim3((unsigned)((rings + 255) / 256)), dim3(256), 0, c->stream, M.bits, M.occ, S, H, W, P, M.wpr, M.oshift, sel, flags_d);
     LVX_HIP(c, hipGetLastError());
     return LVX_OK;
   }
   // the surfel grid (depends on the plane table only): built here, or once by lvx_surfel_map_prepare_d for every later call with that table
-  if ((rc = assoc_grid_build(c, P, planes_d, c->assoc_map_ready && c->assoc_map_planes == planes_d && c->assoc_map_P == P))) return rc;
-  AssocGrid* gd = (AssocGrid*)c->d_assoc[0].p; int* ccnt = (int*)(gd + 1); int* coff = ccnt + SA_CELLS; int* clist = (int*)c->d_assoc[1].p;
-  (void)ccnt;
-  const double* aos = (const double*)((const char*)c->d_assoc[0].p + ((sizeof(AssocGrid) + (size_t)(3 * SA_CELLS + 8) * 4 + 15) & ~(size_t)15));
-  hipLaunchKernelGGL(k_assoc_hits, dim3((unsigned)((H * W + 255) / 256), (unsigned)S), dim3(256), 0, c->stream, scans_d, H, W, P, aos, radius, (const AssocGrid*)gd, (const int*)coff, (const int*)clist,
-                     bits, occ, wpr, oshift, flags_d);
-  hipLaunchKernelGGL(k_assoc_select, dim3((unsigned)((rings + 255) / 256)), dim3(256), 0, c->stream, bits, occ, S, H, W, P, wpr, oshift, sel, flags_d);
+  if (!(c->assoc_map_ready && c->assoc_map_planes == planes_d && c->assoc_map_P == P) && (rc = assoc_grid_build(c, P, planes_d))) return rc;
+  AssocGridView A;
+  if ((rc = assoc_grid_view(c, 0, &A))) return rc;
+  assoc_hits_enqueue(c, scans_d, S, H, W, P, radius, sel, A, M, flags_d, flags_d);
   LVX_HIP(c, hipGetLastError());
   return LVX_OK;
 }
@@ -2563,7 +2619,7 @@ int lvx_surfel_map_prepare_d(lvx_ctx* c, int n_planes, const double* planes10_d)
   LVX_HIP(c, hipSetDevice(c->device));
   c->assoc_map_ready = false;
   if (n_planes == 0) return LVX_OK;
-  int rc = assoc_grid_build(c, n_planes, planes10_d, false);
+  int rc = assoc_grid_build(c, n_planes, planes10_d);
   if (rc) return rc;
   c->assoc_map_planes = planes10_d; c->assoc_map_P = n_planes; c->assoc_map_ready = true;
   return LVX_OK;
@@ -2750,27 +2806,32 @@ static int surfel_compact_launch(lvx_ctx* c, const SurfelPlaneDev* all, const in
   hipLaunchKernelGGL(k_surfel_compact_mb, dim3((unsigned)std::max(nb, 1)), dim3(256), 0, c->stream, all, flag, nl, recs, d_cnt, info, (unsigned long long*)c->d_pub.p + SE_MAXWG, c->compact_epoch);
   return LVX_OK;
 }
+// setSurfelMap over n leaves of the context's grid (n: the leaf count, or a capacity with the true count on the device at n_d): candidates in d_up[4] / d_up[5],
+// compacted into dst = [records | plane table], the plane count at *d_cnt (device).  Enqueues only.
+static int surfel_extract_enqueue(lvx_ctx* c, double p_lambda, double dist_threshold, int min_leaf_points, int min_inliers, int n, const VxInfo* n_d, DevBuf& dst, int** d_cnt) {
+  int rc;
+  if ((rc = dev_alloc(c, c->d_up[4], (size_t)n * sizeof(SurfelPlaneDev)))) return rc;
+  if ((rc = dev_alloc(c, c->d_up[5], (size_t)n * 4))) return rc;
+  if (c->assoc_map_planes == (const double*)c->d_up[5].p) lvx_surfel_map_release(c);
+  if ((rc = dev_alloc(c, dst, (size_t)n * (sizeof(SurfelPlaneDev) + 80) + 64))) return rc;
+  *d_cnt = (int*)((char*)dst.p + dst.bytes - 16);
+  const VoxelView X = vox_view(c);
+  hipLaunchKernelGGL(k_surfel_extract, dim3((n + 3) / 4), dim3(256), 0, c->stream, (const float4*)c->vox.d_pts, (const unsigned*)X.counts, (const unsigned*)X.offs, (const int*)X.sorted_ids, n, (const int*)X.leaf_n,
+                     (const double*)X.mean, (const double*)X.evecs, (const double*)X.evals, p_lambda, dist_threshold, min_leaf_points, min_inliers, (SurfelPlaneDev*)c->d_up[4].p, (int*)c->d_up[5].p, n_d);
+  LVX_HIP(c, hipGetLastError());
+  return surfel_compact_launch(c, (const SurfelPlaneDev*)c->d_up[4].p, (const int*)c->d_up[5].p, n, (SurfelPlaneDev*)dst.p, *d_cnt, n_d);
+}
 // setSurfelMap over the leaves of the context's voxel grid: the accepted planes in voxel-key (std::map) order
 static int surfel_extract_device(lvx_ctx* c, double p_lambda, double dist_threshold, int min_leaf_points, int min_inliers, std::vector<SurfelPlaneDev>& out, DevBuf& dst) {
   out.clear();
   { const int rc0 = vox_info(c); if (rc0) return rc0; }
-  const lvx_ctx::Voxels& V = c->vox;
-  const int nl = V.n_leaves, n = V.n_points; const size_t cap = (size_t)V.cap;
+  const int nl = c->vox.n_leaves;
   if (nl == 0) return LVX_OK;   // no voxel build yet, or one that found no leaf: an empty map (include/lvx.h)
   int rc;
-  if ((rc = dev_alloc(c, c->d_up[4], (size_t)nl * sizeof(SurfelPlaneDev)))) return rc;
-  if ((rc = dev_alloc(c, c->d_up[5], (size_t)nl * 4))) return rc;
-  if (c->assoc_map_planes == (const double*)c->d_up[5].p) lvx_surfel_map_release(c);
-  const unsigned* counts = (const unsigned*)V.runs.p + n; const unsigned* offs = (const unsigned*)V.runs.p + 2 * (size_t)n;
-  const int* lk = (const int*)V.leaf_i.p; const double* d = (const double*)V.leaf_d.p;
-  { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
-    hipLaunchKernelGGL(k_surfel_extract, dim3((nl + 3) / 4), dim3(256), 0, c->stream, (const float4*)V.d_pts, counts, offs, (const int*)V.vals.p + n, nl, lk + cap, d, d + 21 * cap,
-                       d + 30 * cap, p_lambda, dist_threshold, min_leaf_points, min_inliers, (SurfelPlaneDev*)c->d_up[4].p, (int*)c->d_up[5].p, (const VxInfo*)nullptr); }
-  LVX_HIP(c, hipGetLastError());
+  int* d_cnt = nullptr;
   // compaction on the device: [records | plane table] in dst, the count comes back (4 bytes), then the records
-  if ((rc = dev_alloc(c, dst, (size_t)nl * (sizeof(SurfelPlaneDev) + 80) + 64))) return rc;
-  int* d_cnt = (int*)((char*)dst.p + dst.bytes - 16);
-  if ((rc = surfel_compact_launch(c, (const SurfelPlaneDev*)c->d_up[4].p, (const int*)c->d_up[5].p, nl, (SurfelPlaneDev*)dst.p, d_cnt, nullptr))) return rc;
+  { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+    if ((rc = surfel_extract_enqueue(c, p_lambda, dist_threshold, min_leaf_points, min_inliers, nl, nullptr, dst, &d_cnt))) return rc; }
   int P = 0;
   LVX_HIP(c, hipMemcpyAsync(&P, d_cnt, 4, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
@@ -2815,62 +2876,40 @@ int lvx_assoc_default_options(lvx_assoc_options* o) {
 // learned from the previous call (kernels read the true counts from device memory and clamp to the capacity), waits ONCE at the end, and looks at what the device
 // mirrored into pinned memory — a count above its capacity (or a cell table that was too small) discards the attempt and the synchronous chain runs.
 static int da_capacity(int have, int need, int slack) { return (have >= need && (long long)have <= 4ll * need + 4ll * slack) ? have : need + need / 8 + slack; }
+// the chronological SurfelPoint lists of the flags in d_da[6]: outputs strided by the CAPACITY (every scan point could be a SurfelPoint), count + write in one call,
+// one host synchronisation
+static int da_emit(lvx_ctx* c, int S, int H, int W, size_t npt, int32_t* total) {
+  SurfelOut out;
+  const int rc = surfel_point_arrays(c, npt, true, &out); if (rc) return rc;
+  return lvx_surfel_emit_d(c, S, H, W, (const int32_t*)c->d_da[6].p, (const float*)c->d_da[4].p, (const lvx_point_xyzit*)c->d_da[0].p, (int)npt, out.pt, out.pt_map, out.t, out.plane, total, nullptr);
+}
 // returns LVX_OK, an error, or 1 = a capacity was exceeded (nothing of the attempt is kept)
 static int da_speculative(lvx_ctx* c, const lvx_assoc_options& o, int S, int H, int W, size_t npt, const int* dv, int32_t* n_planes, int32_t* n_points) {
-  hipStream_t st = c->stream;
   int rc;
   lvx_ctx::Voxels& V = c->vox;
   if (!c->da_pinned) LVX_HIP(c, hipHostMalloc((void**)&c->da_pinned, 64, hipHostMallocDefault));
   const int nl_cap = std::min<long long>(c->da_cap_nl, (long long)npt), P_cap = std::min(c->da_cap_P, nl_cap), list_cap = c->da_cap_list;
   if ((rc = voxel_build_device(c, (const float4*)c->d_da[4].p, (int)npt, o.ndt_resolution, o.min_points_per_voxel, o.min_covar_eigvalue_mult))) return rc;
-  const VxInfo* d_info = (const VxInfo*)((const char*)V.misc.p + 64);
-  const int n = V.n_points; const size_t cap = (size_t)V.cap;
-  // setSurfelMap over the first min(leaves, nl_cap) leaves
-  if ((rc = dev_alloc(c, c->d_up[4], (size_t)nl_cap * sizeof(SurfelPlaneDev)))) return rc;
-  if ((rc = dev_alloc(c, c->d_up[5], (size_t)nl_cap * 4))) return rc;
-  DevBuf& dst = c->d_da[5];
-  if ((rc = dev_alloc(c, dst, (size_t)nl_cap * (sizeof(SurfelPlaneDev) + 80) + 64))) return rc;
-  int* d_cnt = (int*)((char*)dst.p + dst.bytes - 16);
-  { const unsigned* counts = (const unsigned*)V.runs.p + n; const unsigned* offs = (const unsigned*)V.runs.p + 2 * (size_t)n;
-    const int* lk = (const int*)V.leaf_i.p; const double* d = (const double*)V.leaf_d.p;
-    hipLaunchKernelGGL(k_surfel_extract, dim3((nl_cap + 3) / 4), dim3(256), 0, st, (const float4*)V.d_pts, counts, offs, (const int*)V.vals.p + n, nl_cap, lk + cap, d, d + 21 * cap, d + 30 * cap,
-                       o.plane_lambda, o.fit_threshold, o.min_leaf_points, o.min_inliers, (SurfelPlaneDev*)c->d_up[4].p, (int*)c->d_up[5].p, d_info);
-    if ((rc = surfel_compact_launch(c, (const SurfelPlaneDev*)c->d_up[4].p, (const int*)c->d_up[5].p, nl_cap, (SurfelPlaneDev*)dst.p, d_cnt, d_info))) return rc; }
+  const VxInfo* d_info = vox_view(c).info;
+  // setSurfelMap over the first min(leaves, nl_cap) leaves: records + the association's plane table in d_da[5], their count at d_cnt
+  int* d_cnt = nullptr;
+  if ((rc = surfel_extract_enqueue(c, o.plane_lambda, o.fit_threshold, o.min_leaf_points, o.min_inliers, nl_cap, d_info, c->d_da[5], &d_cnt))) return rc;
   // the association grid of min(planes, P_cap) planes, lists of list_cap entries
-  const size_t grid_bytes = (sizeof(AssocGrid) + (size_t)(3 * SA_CELLS + 8) * 4 + 15) & ~(size_t)15;
-  c->assoc_map_ready = false;
-  if ((rc = dev_alloc(c, c->d_assoc[0], grid_bytes + (size_t)P_cap * 80))) return rc;
+  const double* recs = (const double*)c->d_da[5].p;
+  AssocGridView A;
   if ((rc = dev_alloc(c, c->d_assoc[1], (size_t)std::max(list_cap, 1) * 4))) return rc;
-  AssocGrid* gd = (AssocGrid*)c->d_assoc[0].p; int* ccnt = (int*)(gd + 1); int* coff = ccnt + SA_CELLS; int* ccur = coff + SA_CELLS + 1; int* clist = (int*)c->d_assoc[1].p;
-  double* aos = (double*)((char*)c->d_assoc[0].p + grid_bytes);
-  const double* recs = (const double*)dst.p;
-  hipLaunchKernelGGL(k_assoc_grid_geom, dim3(1), dim3(256), 0, st, P_cap, recs, gd, (const int*)d_cnt, ccnt);
-  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P_cap + 127) / 128)), dim3(128), 0, st, P_cap, recs, (const AssocGrid*)gd, ccnt, ccur, (int*)nullptr, 0, aos, (const int*)d_cnt, list_cap);
-  hipLaunchKernelGGL(k_assoc_grid_scan, dim3(1), dim3(1024), 0, st, (const int*)ccnt, coff, ccur, list_cap);
-  hipLaunchKernelGGL(k_assoc_grid_fill, dim3((unsigned)((P_cap + 127) / 128)), dim3(128), 0, st, P_cap, recs, (const AssocGrid*)gd, ccnt, ccur, clist, 1, (double*)nullptr, (const int*)d_cnt, list_cap,
-                     c->da_pinned, dv);
-  // flags of every scan: rings strided by the plane CAPACITY (rings of planes that do not exist stay empty)
-  const int wpr = (W + 31) / 32, chunk = 64;   // (flags: d_da[6], set to -1 by the de-skew kernel)
-  { const size_t rings = (size_t)std::min(chunk, S) * P_cap * H, bits_bytes = (rings * wpr * 4 + 7) & ~(size_t)7, bytes = bits_bytes + rings * 8;
-    const int oshift = wpr > 64 ? 1 : 0;
-    if (!c->d_assoc[3].p || c->d_assoc[3].bytes < bytes || c->assoc_rings != rings || c->assoc_wpr != wpr) {
-      if ((rc = dev_alloc(c, c->d_assoc[3], bytes))) return rc;
-      LVX_HIP(c, hipMemsetAsync(c->d_assoc[3].p, 0, c->d_assoc[3].bytes, st));
-      c->assoc_rings = rings; c->assoc_wpr = wpr;
-    }
-    unsigned* bits = (unsigned*)c->d_assoc[3].p; unsigned long long* occ = (unsigned long long*)((char*)c->d_assoc[3].p + bits_bytes);
-    for (int s0 = 0; s0 < S; s0 += chunk) {
-      const int ns = std::min(chunk, S - s0);
-      const float4* sc = (const float4*)c->d_da[4].p + (size_t)s0 * H * W;
-      hipLaunchKernelGGL(k_assoc_hits, dim3((unsigned)((H * W + 255) / 256), (unsigned)ns), dim3(256), 0, st, sc, H, W, P_cap, (const double*)aos, o.radius, (const AssocGrid*)gd, (const int*)coff, (const int*)clist, bits, occ, wpr, oshift, (int*)nullptr);
-      hipLaunchKernelGGL(k_assoc_select, dim3((unsigned)(((size_t)ns * P_cap * H + 255) / 256)), dim3(256), 0, st, bits, occ, ns, H, W, P_cap, wpr, oshift, o.selected_per_ring, (int*)c->d_da[6].p + (size_t)s0 * H * W);
-    } }
+  if ((rc = assoc_grid_count_enqueue(c, P_cap, recs, d_cnt, list_cap, &A))) return rc;
+  assoc_grid_fill_enqueue(c, P_cap, recs, d_cnt, list_cap, A, c->da_pinned, dv);
+  // flags of every scan (d_da[6], set to -1 by the de-skew kernel): rings strided by the plane CAPACITY (rings of planes that do not exist stay empty)
+  const int chunk = 64;
+  HitMask M;
+  if ((rc = assoc_hit_mask(c, (size_t)std::min(chunk, S) * P_cap * H, W, &M))) return rc;
+  for (int s0 = 0; s0 < S; s0 += chunk)
+    assoc_hits_enqueue(c, (const float4*)c->d_da[4].p + (size_t)s0 * H * W, std::min(chunk, S - s0), H, W, P_cap, o.radius, o.selected_per_ring, A, M, nullptr, (int*)c->d_da[6].p + (size_t)s0 * H * W);
   LVX_HIP(c, hipGetLastError());
   // SurfelPoint lists (capacity-strided), then THE host stop
   int32_t total = 0;
-  if ((rc = dev_alloc(c, c->d_da[7], npt * (24 + 24 + 8 + 4) + 64))) return rc;
-  { double* d_pt = (double*)c->d_da[7].p; double* d_pm = d_pt + 3 * npt; double* d_t = d_pm + 3 * npt; int32_t* d_pl = (int32_t*)(d_t + npt);
-    if ((rc = lvx_surfel_emit_d(c, S, H, W, (const int32_t*)c->d_da[6].p, (const float*)c->d_da[4].p, (const lvx_point_xyzit*)c->d_da[0].p, (int)npt, d_pt, d_pm, d_t, d_pl, &total, nullptr))) return rc; }
+  if ((rc = da_emit(c, S, H, W, npt, &total))) return rc;
   V.pending = false;
   VxInfo inf; std::memcpy(&inf, V.h_info, sizeof(inf));
   const int hv = c->da_pinned[0], P = c->da_pinned[1], ltot = c->da_pinned[2];
@@ -2915,11 +2954,8 @@ static int da_sync_chain(lvx_ctx* c, const lvx_assoc_options& o, const float4* m
   rc = lvx_surfel_assoc_batch_d(c, S, H, W, (const float*)c->d_da[4].p, P, planes_d, o.radius, o.selected_per_ring, (int32_t*)c->d_da[6].p);
   lvx_surfel_map_release(c);
   if (rc) return rc;
-  // outputs strided by the CAPACITY (every scan point could be a SurfelPoint): count + write in one call, one host synchronisation
   int32_t total = 0;
-  if ((rc = dev_alloc(c, c->d_da[7], npt * (24 + 24 + 8 + 4) + 64))) return rc;
-  { double* d_pt = (double*)c->d_da[7].p; double* d_pm = d_pt + 3 * npt; double* d_t = d_pm + 3 * npt; int32_t* d_pl = (int32_t*)(d_t + npt);
-    if ((rc = lvx_surfel_emit_d(c, S, H, W, (const int32_t*)c->d_da[6].p, (const float*)c->d_da[4].p, (const lvx_point_xyzit*)c->d_da[0].p, (int)npt, d_pt, d_pm, d_t, d_pl, &total, nullptr))) return rc; }
+  if ((rc = da_emit(c, S, H, W, npt, &total))) return rc;
   c->da_points = total;
   if (n_points) *n_points = total;
   return LVX_OK;
@@ -3083,12 +3119,12 @@ int lvx_get_surfel_points(lvx_ctx* c, int max_points, double* pt3, double* pt_ma
   const size_t total = (size_t)c->da_points, n = std::min((size_t)max_points, total);
   if (n == 0) return LVX_OK;
   LVX_HIP(c, hipSetDevice(c->device));
-  const size_t cap = (size_t)c->da_S * c->da_H * c->da_W;   // the lists are strided by the capacity (lvx_data_association)
-  const double* d_pt = (const double*)c->d_da[7].p; const double* d_pm = d_pt + 3 * cap; const double* d_t = d_pm + 3 * cap; const int32_t* d_pl = (const int32_t*)(d_t + cap);
-  if (pt3) LVX_HIP(c, hipMemcpyAsync(pt3, d_pt, n * 24, hipMemcpyDeviceToHost, c->stream));
-  if (pt_map3) LVX_HIP(c, hipMemcpyAsync(pt_map3, d_pm, n * 24, hipMemcpyDeviceToHost, c->stream));
-  if (t) LVX_HIP(c, hipMemcpyAsync(t, d_t, n * 8, hipMemcpyDeviceToHost, c->stream));
-  if (plane) LVX_HIP(c, hipMemcpyAsync(plane, d_pl, n * 4, hipMemcpyDeviceToHost, c->stream));
+  SurfelOut d;
+  surfel_point_arrays(c, (size_t)c->da_S * c->da_H * c->da_W, false, &d);   // the lists are strided by the capacity (lvx_data_association)
+  if (pt3) LVX_HIP(c, hipMemcpyAsync(pt3, d.pt, n * 24, hipMemcpyDeviceToHost, c->stream));
+  if (pt_map3) LVX_HIP(c, hipMemcpyAsync(pt_map3, d.pt_map, n * 24, hipMemcpyDeviceToHost, c->stream));
+  if (t) LVX_HIP(c, hipMemcpyAsync(t, d.t, n * 8, hipMemcpyDeviceToHost, c->stream));
+  if (plane) LVX_HIP(c, hipMemcpyAsync(plane, d.plane, n * 4, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
 }
@@ -3203,17 +3239,9 @@ int ndt_workspace(lvx_ctx* c, int n, NdtDev* W) {
   LVX_HIP(c, hipMemsetAsync(W->out, 0, 64 * 8, c->stream));
   return LVX_OK;
 }
-struct NdtGridArgs { VxGrid g; const int* cells; const int* leaf_n; const double* mean; const double* icov; const float* centroid; float leaf; int min_pts; };
-NdtGridArgs ndt_grid(const lvx_ctx* c) {
-  const lvx_ctx::Voxels& V = c->vox;
-  NdtGridArgs G; std::memcpy(&G.g, &V.grid, sizeof(G.g));
-  const size_t nl = (size_t)V.cap;   // leaf arrays are strided by the capacity
-  G.cells = (const int*)V.cells.p; G.leaf_n = (const int*)V.leaf_i.p + nl; G.mean = (const double*)V.leaf_d.p; G.icov = G.mean + 12 * nl; G.centroid = (const float*)V.leaf_f.p; G.leaf = V.leaf; G.min_pts = V.min_pts;
-  return G;
-}
 // one computeDerivatives on the device: score, gradient, Hessian at p6 (transform M16 applied in the kernel, or the caller's transformed cloud trn_d)
 int ndt_eval(lvx_ctx* c, const NdtDev& W, int n, const float4* src_d, const float4* trn_d, const float* M16, const double* p6, double outlier_ratio, int search, int compute_hessian, double* h43) {
-  const NdtGridArgs G = ndt_grid(c);
+  const VoxelView G = vox_view(c);
   const NdtTables T = ndt_tables(p6, (double)G.leaf, outlier_ratio);
   const NdtMat M = ndt_mat12(M16);
   const dim3 grid((unsigned)W.blocks), blk(256);
@@ -3229,7 +3257,7 @@ int ndt_eval(lvx_ctx* c, const NdtDev& W, int n, const float4* src_d, const floa
   return LVX_OK;
 }
 int ndt_hessian(lvx_ctx* c, const NdtDev& W, int n, const float4* src_d, const float* M16, const double* p6, double outlier_ratio, int search, double* h36) {
-  const NdtGridArgs G = ndt_grid(c);
+  const VoxelView G = vox_view(c);
   const NdtTables T = ndt_tables(p6, (double)G.leaf, outlier_ratio);
   const NdtMat M = ndt_mat12(M16);
   const dim3 grid((unsigned)W.blocks), blk(256);
@@ -3583,7 +3611,7 @@ int lvx_voxel_lookup_rel(lvx_ctx* c, int nq, const float* xyzi4, int n_rel, cons
   if ((rc = upload(c, c->d_up[2], xyzi4, (size_t)nq * 16))) return rc;
   if ((rc = upload(c, c->d_up[6], rel3, (size_t)n_rel * 12))) return rc;
   if ((rc = dev_alloc(c, c->d_up[3], ne * 4))) return rc;
-  const NdtGridArgs G = ndt_grid(c);
+  const VoxelView G = vox_view(c);
   { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
     hipLaunchKernelGGL(k_vx_lookup_rel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_up[2].p, nq, G.leaf, G.min_pts, G.g, G.cells, G.leaf_n, n_rel,
                        (const int*)c->d_up[6].p, (int*)c->d_up[3].p); }
@@ -3612,7 +3640,7 @@ static int radius_device(lvx_ctx* c, int nq, const float4* q_d, double radius, i
     if (count_d) LVX_HIP(c, hipMemsetAsync(count_d, 0, (size_t)nq * 4, c->stream));
     return LVX_OK;
   }
-  const NdtGridArgs G = ndt_grid(c);
+  const VoxelView G = vox_view(c);
   { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
     hipLaunchKernelGGL(k_vx_radius, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, c->stream, q_d, nq, G.leaf, radius, G.min_pts, G.g, G.cells, G.leaf_n, G.centroid, ids_d, d2_d, count_d); }
   LVX_HIP(c, hipGetLastError());

@@ -81,6 +81,35 @@ def test_product_library_does_not_link_the_oracle(liblvx):
     assert "orc_" not in syms
 
 
+def _build_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("lvx_build_table", os.path.join(ROOT, "lvi-exc_amd", "build.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_every_source_names_its_fp_contract_mode():
+    """build.py's CONTRACT table names every csrc/*.hip (no source falls through to a default) and names nothing that is gone.  Every file that holds upstream code
+    (it includes lvx_stdsort.h or lvx_vxradius.h, which the host checks restate bit for bit) or is compared bit for bit against a g++ build of its header (render, traj,
+    rotinit) is built without FMA contraction.  A source the table does not know is an error of the build, not a default."""
+    mod = _build_module()
+    csrc = os.path.join(ROOT, "lvi-exc_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    assert len(names) >= 9
+    assert sorted(mod.CONTRACT) == names
+    assert all(v in ("off", mod.DEFAULT) for v in mod.CONTRACT.values())
+    upstream = [f for f in names if re.search(r'#include "lvx_(stdsort|vxradius)\.h"', open(os.path.join(csrc, f)).read())]
+    assert "lvx_upstream.hip" in upstream
+    for f in upstream + ["lvx_render.hip", "lvx_traj.hip", "lvx_rotinit.hip"]:
+        assert mod.CONTRACT[f] == "off" and mod.contract(f) == "off", f
+    assert mod.contract("lvx_eval") == mod.DEFAULT_CONTRACT and mod.contract(os.path.join(csrc, "lvx_upstream.hip")) == "off"
+    with pytest.raises(RuntimeError):
+        mod.contract("lvx_not_a_source.hip")
+    # the experiment builds take the mode from the same table
+    assert "build.py --contract" in open(os.path.join(ROOT, "tools", "build_variant.sh")).read()
+
+
 def test_graft_entry_build():
     import importlib
     ge = importlib.import_module("__graft_entry__")

@@ -5,7 +5,7 @@ set -e
 FILE=$1; TAG=$2; DEFS=$3
 cd "$(dirname "$0")/../lvi-exc_amd"
 python build.py > /dev/null
-CONTRACT=fast; [ "$FILE" = "lvx_upstream" ] && CONTRACT=off
+CONTRACT=$(python build.py --contract "$FILE")   # build.py's table is the only one
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics -fno-gpu-rdc -Wno-unused-result -ffp-contract=$CONTRACT $DEFS -c csrc/$FILE.hip -o /tmp/${FILE}_var_$TAG.o
 OBJS=""
 for s in csrc/*.hip; do
