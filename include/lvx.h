@@ -607,6 +607,39 @@ int lvx_get_surfel_points(lvx_ctx* ctx, int max_points, double* pt3, double* pt_
 /* parity / debug: the de-skewed scans of the last lvx_data_association, [n_scans][H][W][4] float */
 int lvx_get_scans_in_map(lvx_ctx* ctx, float* xyzi4);
 
+/* scan ingestion: VLP-16 packets to organised raw scans ---------------------------------------------------------------*/
+/* licalib::VelodyneCorrection::unpack_scan (src/lvi_exc/include/utils/vlp_common.h:51-149, called per scan from LioDataset::read, dataset_reader.h:152-157) for every
+ * scan of a recording, on the device: the context's raw scans come from the 1206-byte packets (12 blocks of {header, rotation, 32 x {distance, intensity}} + 6 trailer
+ * bytes) instead of from host-unpacked records — a tenth of the bytes.  Per point, in the reference's arithmetic (csrc/lvx_vlp16.h): azimuth interpolated per firing
+ * from the block rotations (block 11 reuses the difference of block 10), rotation-table products with the reference's own float cosf / sinf tables (built on the host,
+ * once per context), the stored point (y, -x, z), row scan_mapping_16[dsr], column 2 * block_counter + firing, timestamp scan_stamp + (row * 2.304e-6 + column *
+ * 55.296e-6) — indexed with the MAPPED row, as the reference does.  A range outside [min_range, max_range]: x = y = z = NaN, intensity 0, timestamp kept.  A corrected
+ * azimuth outside the angle window [min_angle, max_angle] (min > max: the window wraps): the record is 32 zero bytes, as the reference's value-initialised cloud.
+ * Block headers are not checked (the reference does not); n_bad_headers counts the blocks that are not 0xEEFF.  pad / pad2 of every record are 0.
+ * W = 0: 24 x the longest scan's packet count.  The reference sizes each cloud to its own 24 x packets columns; the context keeps ONE W, so the columns beyond
+ * 24 x packets of a shorter scan hold "no return" — x = y = z = NaN, intensity 0, timestamp 0 (the association skips NaN, the emission skips timestamp 0).  That is the
+ * one deviation.
+ * LVX_E_ARG: a scan of more than 76 packets (the reference's time table ends at column 1824 and it would read past it), W smaller than 24 x the longest scan or above
+ * 4096, offsets that decrease, NULL arguments; the context and its previous scans stay as they were. */
+#define LVX_VLP16_PACKET_BYTES 1206
+typedef struct lvx_vlp16_options { double min_range, max_range; int32_t min_angle, max_angle; } lvx_vlp16_options;   /* 0.6, 150, 0, 36000 (vlp_common.h:186-189) */
+typedef struct lvx_vlp16_info { int64_t n_packets, n_in_range, n_out_of_range, n_outside_window, n_bad_headers; int32_t W, reserved; } lvx_vlp16_info;
+int lvx_vlp16_default_options(lvx_vlp16_options* opt);
+/* scans [s] = packets [packet_offsets[s] .. packet_offsets[s+1]) of `packets` ([n][1206] bytes, host); scan_stamp[s] = the message's header stamp.
+ * Result: the context's raw scans exactly as lvx_set_scans(ctx, n_scans, 16, W, ...) would leave them (the association state is reset as there).  opt, info may be NULL. */
+int lvx_set_scans_vlp16(lvx_ctx* ctx, int n_scans, const int32_t* packet_offsets, const uint8_t* packets, const double* scan_stamp, int W, const lvx_vlp16_options* opt,
+                        lvx_vlp16_info* info);
+/* the same into a caller's host buffer [n_scans][16][W], context scans untouched */
+int lvx_vlp16_unpack(lvx_ctx* ctx, int n_scans, const int32_t* packet_offsets, const uint8_t* packets, const double* scan_stamp, int W, const lvx_vlp16_options* opt,
+                     lvx_point_xyzit* out, lvx_vlp16_info* info);
+/* unpack_scan's second overload (vlp_common.h:152-176): organised H x W xyz-intensity clouds ([n_scans][H][W][4] float, host) whose times are
+ * scan_stamp[s] + (h * 2.304e-6 + w * 55.296e-6); the context's raw scans as lvx_set_scans(ctx, n_scans, H, W, ...) would leave them.  H <= 16 and W <= 1824 (the
+ * reference's time table), otherwise LVX_E_ARG. */
+int lvx_set_scans_organised(lvx_ctx* ctx, int n_scans, int H, int W, const float* xyzi4, const double* scan_stamp);
+/* parity / hand-over: scans [first, first + n) of the context, however they were set, [n][H][W] records.  LVX_E_STATE: the context has no scans; LVX_E_ARG: a range
+ * outside them. */
+int lvx_get_scans_raw(lvx_ctx* ctx, int first, int n, lvx_point_xyzit* out);
+
 /* SurfelAssociation::associateVisualPointsWithPlanes (surfel_association.cpp:161-214) over the landmark table of lvx_set_landmarks and the inverse depths in `state`:
  * plane_of_landmark[l] = index of the surfel whose AABB strictly contains the landmark (map frame) within 2 * radius of its plane — the highest such index, as the
  * reference's loop leaves it — or -1 (also for rho < 0.05 and for reference views outside the spline).  q_LtoC (x, y, z, w), t_LinC: LiDAR pose in the camera frame. */

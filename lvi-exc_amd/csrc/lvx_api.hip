@@ -96,6 +96,7 @@ void lvx_destroy(lvx_ctx* c) {
   for (auto& b : c->d_rn) if (b.p) (void)hipFree(b.p);
   for (auto& b : c->d_ds) if (b.p) (void)hipFree(b.p);
   for (auto& b : c->d_od) if (b.p) (void)hipFree(b.p);
+  for (auto& b : c->d_vlp) if (b.p) (void)hipFree(b.p);
   if (c->ds_pinned) (void)hipHostFree(c->ds_pinned);
   for (DevBuf* b : {&c->d_da_key, &c->d_da_aux}) if (b->p) (void)hipFree(b->p);
   for (auto& b : c->d_chunk) if (b.p) (void)hipFree(b.p);

@@ -190,6 +190,9 @@ struct lvx_ctx {
   lvx::DevBuf d_ds[5]; long long ds_cells_cap = 0; void* ds_pinned = nullptr;
   // lvx_lidar_odometry: [0] the current scan as xyzi, [1] its filtered source cloud (also the work buffers of the host-array filter call), [2] the key-scan map cloud
   lvx::DevBuf d_od[3]; long long od_map_n = -1;   // points in the map cloud; -1 = no odometry run yet
+  // VLP-16 scan ingestion (lvx_vlp16.h): [0] the host-built tables cos_rot | sin_rot | cos_vert | sin_vert (vlp_tables: uploaded), [1] packets or the xyzi cloud of the
+  // organised overload, [2] counters | scan stamps | packet offsets, [3] the records of lvx_vlp16_unpack
+  lvx::DevBuf d_vlp[4]; bool vlp_tables = false;
   lvx::DevBuf d_da[8]; int da_S = 0, da_H = 0, da_W = 0, da_points = 0; std::vector<lvx_surfel_plane> da_planes;
   // lvx_data_association without host stops (round 5): capacities learned from the previous call (leaves, planes, association-grid list entries; 0 = none yet, the call
   // runs the synchronous path), the pinned mirror the device writes its counts into, the planes still to fetch from d_da[5] when somebody asks for them

@@ -5,6 +5,7 @@
 //   lvx_voxel_lookup7   getNeighborhoodAtPoint7                     (same file :378-438)
 //   lvx_voxel_radius_search  VoxelGridCovariance::radiusSearch      (voxel_grid_covariance_omp.h:473-502; lvx_vxradius.h)
 //   lvx_surfel_assoc    SurfelAssociation::getAssociation           (src/lvi_exc/src/core/surfel_association.cpp:111-138,296-331)
+//   lvx_set_scans_vlp16 VelodyneCorrection::unpack_scan             (src/lvi_exc/include/utils/vlp_common.h:51-255; lvx_vlp16.h)
 // These are HBM/latency-bound integer + float kernels (no MFMA).  Float expressions keep the reference's evaluation order and the
 // library is built with -ffp-contract=off, so scan registration is bit-exact against the serial code.
 #include <string.h>
@@ -20,6 +21,7 @@
 #include "lvx_ctx.h"
 #include "lvx_pose.h"
 #include "lvx_stdsort.h"
+#include "lvx_vlp16.h"
 #include "lvx_vxradius.h"
 
 namespace lvx {
@@ -2006,6 +2008,84 @@ __global__ void k_transform_append(const float4* __restrict__ scan, int n, Pose1
   out[i] = (isfinite(q.x) && isfinite(q.y) && isfinite(q.z)) ? xf_pose16(T.m, q) : q;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------
+// VLP-16 scan ingestion (lvx_vlp16.h): packets -> organised raw scans [n_scans][16][W]
+// ------------------------------------------------------------------------------------------------------------------------
+static_assert(sizeof(VlpPoint) == 32 && sizeof(VlpPoint) == sizeof(lvx_point_xyzit), "record layout");
+// The counters are VLP_COUNT_SLOTS records of {in range, out of range, outside the window, wrong headers}, one 128-byte line each; a workgroup adds into the record
+// of its packet index, the host sums the records.  (On ONE record the 45 600 workgroups of a 600-scan recording queue up behind four addresses: measured, the kernel
+// then takes 0.57 ms instead of 0.21.)
+#define VLP_COUNT_SLOTS 64
+struct VlpJob { const uint8_t* packets; const int* off; const double* stamp; int n_scans, W; VlpTables T; VlpOptions o; VlpPoint* out; unsigned long long* counts; };
+__device__ __forceinline__ void vlp_store(VlpPoint* dst, const VlpPoint& p) {   // one record as two 16-byte stores
+  float4 v[2];
+  memcpy(v, &p, 32);
+  ((float4*)dst)[0] = v[0]; ((float4*)dst)[1] = v[1];
+}
+// One workgroup per packet, blockIdx.x = the packet's index over all scans.  The 1206 bytes come in as 603 16-bit loads (a packet starts at a multiple of 1206 bytes:
+// 2-byte alignment is all there is).  Thread i owns the record (row i / 24, local column i % 24) of the packet's 16 x 24 tile, computes it from LDS and puts it into
+// the LDS tile; the tile then leaves as 768 16-byte stores, thread i taking chunks i and i + 384: every row is one contiguous run of 768 bytes.
+__global__ __launch_bounds__(384) void k_vlp16_unpack(VlpJob J) {
+  __shared__ __align__(16) uint16_t pk[608];
+  __shared__ __align__(16) VlpPoint rec[LVX_VLP16_ROWS * LVX_VLP16_COLS];
+  __shared__ int cnt[4];
+  __shared__ int scan_s;
+  const int p = (int)blockIdx.x, i = (int)threadIdx.x;
+  const uint16_t* src = (const uint16_t*)(J.packets + (size_t)p * LVX_VLP16_BYTES);
+  pk[i] = src[i];
+  if (i + 384 < LVX_VLP16_BYTES / 2) pk[i + 384] = src[i + 384];
+  if (i < 4) cnt[i] = 0;
+  if (i < 64) {   // wave 0: the last scan whose first packet is not behind p, off[s] <= p < off[s + 1] (empty scans are stepped over).  64 probes per round:
+    int lo = 0, hi = J.n_scans;   // two dependent loads at 600 scans where a one-lane bisection has ten, while the other waves stage the packet
+    while (hi - lo > 1) {         // off[lo] <= p < off[hi]; the offsets do not decrease, so the lanes whose probe is <= p form a prefix
+      const int step = (hi - lo + 63) >> 6, q = lo + step * (i + 1);
+      const int k = __popcll(__ballot(q < hi && J.off[q] <= p));
+      hi = min(hi, lo + step * (k + 1));
+      lo += step * k;
+    }
+    if (i == 0) scan_s = lo;
+  }
+  __syncthreads();
+  const int s = scan_s, pl = p - J.off[s];   // the packet's index in its scan
+  const int row = i / LVX_VLP16_COLS, lc = i - row * LVX_VLP16_COLS;
+  const int block = lc >> 1, firing = lc & 1, dsr = vlp16_dsr_of_row(row);
+  const uint8_t* packet = (const uint8_t*)pk;
+  VlpPoint pt; int r, c;
+  const int cls = vlp16_point(packet, block, firing, dsr, LVX_VLP16_BLOCKS * pl + block, J.stamp[s], J.T, J.o, &pt, &r, &c);
+  vlp_store(&rec[r * LVX_VLP16_COLS + (c - LVX_VLP16_COLS * pl)], pt);   // = rec[i]: (r, c) is (row, 24 pl + lc)
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {   // one LDS add per wave and class (384 threads = 6 full waves)
+    const unsigned long long m = __ballot(cls == k);
+    if ((i & 63) == 0 && m) atomicAdd(&cnt[k], __popcll(m));
+  }
+  if (i < LVX_VLP16_BLOCKS && vlp16_bad_header(packet, i)) atomicAdd(&cnt[3], 1);
+  __syncthreads();
+  const float4* tile = (const float4*)rec;
+  float4* out = (float4*)J.out;
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const int ch = i + 384 * k, rr = ch / 48, within = ch - rr * 48;
+    out[((((size_t)s * LVX_VLP16_ROWS + rr) * J.W + (size_t)LVX_VLP16_COLS * pl) << 1) + within] = tile[ch];
+  }
+  if (i < 4 && cnt[i]) atomicAdd(&J.counts[(p & (VLP_COUNT_SLOTS - 1)) * 16 + i], (unsigned long long)cnt[i]);
+}
+// the columns beyond 24 x packets of the scans shorter than W: "no return" (lvx_vlp16.h, DEVIATION)
+__global__ void k_vlp16_pad(const int* __restrict__ off, int W, size_t total, VlpPoint* out) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int w = (int)(idx % (size_t)W), s = (int)(idx / ((size_t)LVX_VLP16_ROWS * W));
+  if (w >= LVX_VLP16_COLS * (off[s + 1] - off[s])) vlp_store(out + idx, vlp16_padding());
+}
+// unpack_scan's second overload: [n_scans][H][W] xyzi -> records
+__global__ void k_vlp16_organised(const float4* __restrict__ xyzi, const double* __restrict__ stamp, int H, int W, size_t total, VlpPoint* out) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int w = (int)(idx % (size_t)W), h = (int)((idx / (size_t)W) % (size_t)H); const size_t s = idx / ((size_t)H * W);
+  const float4 q = xyzi[idx];
+  const float v[4] = {q.x, q.y, q.z, q.w};
+  vlp_store(out + idx, vlp16_organised_point(v, h, w, stamp[s]));
+}
+
 }  // namespace lvx
 
 using namespace lvx;
@@ -2854,13 +2934,151 @@ int lvx_surfel_extract(lvx_ctx* c, double p_lambda, double dist_threshold, int m
 }
 
 // ---- LIinitializer::DataAssociation, refinement branch (src/lvi_exc/test/lvi_initialize_surfel_orb.cpp:1180-1201), device-resident -------------------------------
+// new scans: the association forgets the planes and the capacities it learned on the scans before them
+static void da_reset(lvx_ctx* c, int n_scans, int H, int W) {
+  c->da_S = n_scans; c->da_H = H; c->da_W = W; c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_cap_nl = c->da_cap_P = c->da_cap_list = 0;
+}
 int lvx_set_scans(lvx_ctx* c, int n_scans, int H, int W, const lvx_point_xyzit* raw) {
   if (!c || n_scans < 0 || H < 0 || W < 0 || W > SA_WMAX || ((size_t)n_scans * H * W > 0 && !raw)) return c ? fail(c, LVX_E_ARG, "bad lvx_set_scans arguments (W <= 4096)") : LVX_E_ARG;
   LVX_HIP(c, hipSetDevice(c->device));
-  c->da_S = n_scans; c->da_H = H; c->da_W = W; c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_cap_nl = c->da_cap_P = c->da_cap_list = 0;
+  da_reset(c, n_scans, H, W);
   int rc = upload(c, c->d_da[0], raw, (size_t)n_scans * H * W * 32);
   if (rc) return rc;
   LVX_HIP(c, hipStreamSynchronize(c->stream));   // the caller's buffer may go away
+  return LVX_OK;
+}
+
+// ---- VLP-16 scan ingestion (lvx_vlp16.h): VelodyneCorrection::unpack_scan for every scan of a recording, on the device -------------------------------------------------
+int lvx_vlp16_default_options(lvx_vlp16_options* o) {
+  if (!o) return LVX_E_ARG;
+  o->min_range = 0.6; o->max_range = 150; o->min_angle = 0; o->max_angle = 36000;   // setParameters (vlp_common.h:186-189)
+  return LVX_OK;
+}
+// argument checks of both packet entry points; nothing of the context is touched.  *W: the width of the result
+static int vlp16_check(lvx_ctx* c, int n_scans, const int32_t* off, const uint8_t* packets, const double* stamp, int W_in, int* W) {
+  static_assert(sizeof(lvx_vlp16_options) == sizeof(VlpOptions) && LVX_VLP16_PACKET_BYTES == LVX_VLP16_BYTES, "lvx.h and lvx_vlp16.h agree");
+  if (!c) return LVX_E_ARG;
+  if (n_scans < 0 || (n_scans > 0 && (!off || !stamp))) return fail(c, LVX_E_ARG, "VLP-16 scans: negative count or NULL packet_offsets / scan_stamp");
+  *W = 0;
+  switch (n_scans > 0 ? vlp16_width(n_scans, off, W_in, W) : (W_in < 0 ? 3 : 0)) {
+    case 1: return fail(c, LVX_E_ARG, "VLP-16 scans: packet_offsets must start at >= 0 and not decrease");
+    case 2: return fail(c, LVX_E_ARG, "VLP-16 scans: a scan of more than 76 packets (the reference's time table ends at column 1824)");
+    case 3: return fail(c, LVX_E_ARG, "VLP-16 scans: W is smaller than 24 x the longest scan's packets");
+    default: break;
+  }
+  if (n_scans == 0) *W = W_in;
+  if (*W > SA_WMAX) return fail(c, LVX_E_ARG, "VLP-16 scans: W <= 4096");
+  if (n_scans > 0 && off[n_scans] > off[0] && !packets) return fail(c, LVX_E_ARG, "VLP-16 scans: NULL packets");
+  return LVX_OK;
+}
+// the records of all scans into dst (device, [n_scans][16][W]); waits for the stream: the caller's buffers may go away
+static int vlp16_unpack_device(lvx_ctx* c, int n_scans, const int32_t* off, const uint8_t* packets, const double* stamp, int W, const lvx_vlp16_options* opt, VlpPoint* dst,
+                               lvx_vlp16_info* info) {
+  int rc;
+  lvx_vlp16_options o;
+  if (opt) o = *opt; else lvx_vlp16_default_options(&o);
+  const long long n_packets = n_scans > 0 ? (long long)off[n_scans] - off[0] : 0;
+  unsigned long long counts[4] = {0, 0, 0, 0};
+  std::vector<unsigned long long> slots((size_t)VLP_COUNT_SLOTS * 16, 0);
+  if (n_scans > 0 && W > 0) {
+    if (!c->vlp_tables) {
+      std::vector<float> t(2 * LVX_VLP16_ROT + 32);
+      vlp16_build_tables(t.data(), t.data() + LVX_VLP16_ROT, t.data() + 2 * LVX_VLP16_ROT, t.data() + 2 * LVX_VLP16_ROT + 16);
+      if ((rc = upload_tmp(c, c->d_vlp[0], t.data(), t.size() * 4))) return rc;
+      c->vlp_tables = true;
+    }
+    // [counter records | stamps | offsets from 0]
+    const size_t o_stamp = (size_t)VLP_COUNT_SLOTS * 128, o_off = o_stamp + (size_t)n_scans * 8, small_bytes = o_off + ((size_t)n_scans + 1) * 4;
+    std::vector<unsigned char> small(small_bytes, 0);
+    memcpy(small.data() + o_stamp, stamp, (size_t)n_scans * 8);
+    bool shorter = false;
+    for (int s = 0; s <= n_scans; ++s) {
+      const int32_t v = off[s] - off[0];
+      memcpy(small.data() + o_off + (size_t)s * 4, &v, 4);
+      if (s < n_scans && LVX_VLP16_COLS * (off[s + 1] - off[s]) < W) shorter = true;
+    }
+    if ((rc = upload_tmp(c, c->d_vlp[2], small.data(), small_bytes))) return rc;
+    if (n_packets > 0 && (rc = upload(c, c->d_vlp[1], packets + (size_t)off[0] * LVX_VLP16_BYTES, (size_t)n_packets * LVX_VLP16_BYTES))) return rc;
+    char* sm = (char*)c->d_vlp[2].p;
+    const float* t = (const float*)c->d_vlp[0].p;
+    VlpJob J;
+    J.packets = (const uint8_t*)c->d_vlp[1].p; J.off = (const int*)(sm + o_off); J.stamp = (const double*)(sm + o_stamp); J.n_scans = n_scans; J.W = W;
+    J.T.cos_rot = t; J.T.sin_rot = t + LVX_VLP16_ROT; J.T.cos_vert = t + 2 * LVX_VLP16_ROT; J.T.sin_vert = t + 2 * LVX_VLP16_ROT + 16;
+    J.o.min_range = o.min_range; J.o.max_range = o.max_range; J.o.min_angle = o.min_angle; J.o.max_angle = o.max_angle;
+    J.out = dst; J.counts = (unsigned long long*)sm;
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      if (n_packets > 0) hipLaunchKernelGGL(k_vlp16_unpack, dim3((unsigned)n_packets), dim3(384), 0, c->stream, J);
+      if (shorter) {
+        const size_t total = (size_t)n_scans * LVX_VLP16_ROWS * W;
+        hipLaunchKernelGGL(k_vlp16_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, J.off, W, total, dst);
+      } }
+    LVX_HIP(c, hipGetLastError());
+    LVX_HIP(c, hipMemcpyAsync(slots.data(), sm, o_stamp, hipMemcpyDeviceToHost, c->stream));
+  }
+  LVX_HIP(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < VLP_COUNT_SLOTS; ++k) for (int j = 0; j < 4; ++j) counts[j] += slots[(size_t)k * 16 + j];
+  if (info) {
+    info->n_packets = n_packets; info->n_in_range = (int64_t)counts[0]; info->n_out_of_range = (int64_t)counts[1]; info->n_outside_window = (int64_t)counts[2];
+    info->n_bad_headers = (int64_t)counts[3]; info->W = W; info->reserved = 0;
+  }
+  return LVX_OK;
+}
+int lvx_set_scans_vlp16(lvx_ctx* c, int n_scans, const int32_t* packet_offsets, const uint8_t* packets, const double* scan_stamp, int W_in, const lvx_vlp16_options* opt,
+                        lvx_vlp16_info* info) {
+  int W = 0;
+  int rc = vlp16_check(c, n_scans, packet_offsets, packets, scan_stamp, W_in, &W);
+  if (rc) return rc;   // (the context and its scans are as they were)
+  LVX_HIP(c, hipSetDevice(c->device));
+  da_reset(c, 0, LVX_VLP16_ROWS, W);   // no scans until the new ones are complete
+  if ((rc = dev_alloc(c, c->d_da[0], (size_t)n_scans * LVX_VLP16_ROWS * W * 32))) return rc;
+  if ((rc = vlp16_unpack_device(c, n_scans, packet_offsets, packets, scan_stamp, W, opt, (VlpPoint*)c->d_da[0].p, info))) return rc;
+  c->da_S = n_scans;
+  return LVX_OK;
+}
+int lvx_vlp16_unpack(lvx_ctx* c, int n_scans, const int32_t* packet_offsets, const uint8_t* packets, const double* scan_stamp, int W_in, const lvx_vlp16_options* opt,
+                     lvx_point_xyzit* out, lvx_vlp16_info* info) {
+  int W = 0;
+  int rc = vlp16_check(c, n_scans, packet_offsets, packets, scan_stamp, W_in, &W);
+  if (rc) return rc;
+  const size_t bytes = (size_t)n_scans * LVX_VLP16_ROWS * W * 32;
+  if (bytes > 0 && !out) return fail(c, LVX_E_ARG, "lvx_vlp16_unpack: NULL out");
+  LVX_HIP(c, hipSetDevice(c->device));
+  if ((rc = dev_alloc(c, c->d_vlp[3], bytes))) return rc;
+  if ((rc = vlp16_unpack_device(c, n_scans, packet_offsets, packets, scan_stamp, W, opt, (VlpPoint*)c->d_vlp[3].p, info))) return rc;
+  if (bytes > 0) LVX_HIP(c, hipMemcpy(out, c->d_vlp[3].p, bytes, hipMemcpyDeviceToHost));
+  return LVX_OK;
+}
+int lvx_set_scans_organised(lvx_ctx* c, int n_scans, int H, int W, const float* xyzi4, const double* scan_stamp) {
+  if (!c) return LVX_E_ARG;
+  const size_t total = (n_scans > 0 && H > 0 && W > 0) ? (size_t)n_scans * H * W : 0;
+  if (n_scans < 0 || H < 0 || W < 0 || H > LVX_VLP16_ROWS || W > LVX_VLP16_MAX_W || (total > 0 && (!xyzi4 || !scan_stamp)))
+    return fail(c, LVX_E_ARG, "bad lvx_set_scans_organised arguments (H <= 16, W <= 1824: the reference's time table)");
+  LVX_HIP(c, hipSetDevice(c->device));
+  int rc;
+  da_reset(c, 0, H, W);
+  if ((rc = dev_alloc(c, c->d_da[0], total * 32))) return rc;
+  if (total > 0) {
+    if ((rc = upload(c, c->d_vlp[1], xyzi4, total * 16))) return rc;
+    if ((rc = upload(c, c->d_vlp[2], scan_stamp, (size_t)n_scans * 8))) return rc;
+    { ProfScope ps(c, LVX_KERNEL_UPSTREAM);
+      hipLaunchKernelGGL(k_vlp16_organised, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_vlp[1].p, (const double*)c->d_vlp[2].p, H, W, total,
+                         (VlpPoint*)c->d_da[0].p); }
+    LVX_HIP(c, hipGetLastError());
+  }
+  LVX_HIP(c, hipStreamSynchronize(c->stream));   // the caller's buffers may go away
+  c->da_S = n_scans;
+  return LVX_OK;
+}
+int lvx_get_scans_raw(lvx_ctx* c, int first, int n, lvx_point_xyzit* out) {
+  if (!c) return LVX_E_ARG;
+  if (c->da_S <= 0 || !c->d_da[0].p) return fail(c, LVX_E_STATE, "the context has no scans (lvx_set_scans / lvx_set_scans_vlp16 / lvx_set_scans_organised)");
+  if (first < 0 || n < 0 || (long long)first + n > c->da_S) return fail(c, LVX_E_ARG, "lvx_get_scans_raw: [first, first + n) is not inside the context's scans");
+  const size_t HW = (size_t)c->da_H * c->da_W;
+  if ((size_t)n * HW == 0) return LVX_OK;
+  if (!out) return fail(c, LVX_E_ARG, "lvx_get_scans_raw: NULL out");
+  LVX_HIP(c, hipSetDevice(c->device));
+  LVX_HIP(c, hipMemcpyAsync(out, (const char*)c->d_da[0].p + (size_t)first * HW * 32, (size_t)n * HW * 32, hipMemcpyDeviceToHost, c->stream));
+  LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
 }
 int lvx_assoc_default_options(lvx_assoc_options* o) {

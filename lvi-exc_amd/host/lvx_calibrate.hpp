@@ -38,6 +38,10 @@ struct CalibrateInput {
   std::vector<double> imu_t, gyro, acc;                            // [n], [n][3], [n][3]
   int H = 0, W = 0;                                                // organised scans
   std::vector<std::vector<lvx_point_xyzit>> scans;                 // raw LiDAR scans, [H * W] each (row-major h * W + w), per-point timestamps
+  // ... or, instead of `scans`, the recording's VLP-16 packets (velodyne_msgs/VelodyneScan: [n][1206] bytes back to back; scan s = packets [vlp16_packet_offsets[s],
+  // vlp16_packet_offsets[s + 1]); vlp16_stamps[s] = the message's header stamp): the device unpacks them (lvx_set_scans_vlp16 = LioDataset's VelodyneCorrection::unpack_scan),
+  // H becomes 16, W 24 x the longest scan (or the W given here, if larger), and scan_stamps defaults to vlp16_stamps
+  std::vector<uint8_t> vlp16_packets; std::vector<int32_t> vlp16_packet_offsets; std::vector<double> vlp16_stamps;
   double map_time = 0;
   // first map from odometry poses (optional): the scans' header stamps and the LOAM pose file (ReadPoseGT); simulation = the reference's flag: a scan takes the pose with
   // EXACTLY its stamp (loam_poses_map_.find, :1283-1290) instead of the nearest of the poses idx - 5 .. idx + 4 (findAssociatedPose, :1246-1260)
@@ -234,7 +238,7 @@ inline LidarOdometry RunLidarOdometry(lvx_ctx* ctx, const std::vector<double>& s
 class Calibrator {
  public:
   // `in` is copied: the calibrator may outlive the caller's object
-  Calibrator(int device, const CalibrateInput& in, const CalibrateOptions& opt) : in_(in), opt_(opt) {
+  Calibrator(int device, const CalibrateInput& in, const CalibrateOptions& opt) : in_(Resolved(in)), opt_(opt) {
     check(lvx_create(&ctx_, device, 0));
     check(lvx_set_spline(ctx_, in_.t0, in_.dt, in_.n_knots));
     check(lvx_set_camera(ctx_, &in_.camera));
@@ -247,6 +251,11 @@ class Calibrator {
       std::copy(in_.scans[s].begin(), in_.scans[s].end(), raw.begin() + s * HW);
     }
     if (!raw.empty()) check(lvx_set_scans(ctx_, (int)in_.scans.size(), in_.H, in_.W, raw.data()));
+    n_scans_ = in_.scans.size();
+    if (!in_.vlp16_stamps.empty()) {   // LioDataset::read's unpack_scan per message, on the device
+      check(lvx_set_scans_vlp16(ctx_, (int)in_.vlp16_stamps.size(), in_.vlp16_packet_offsets.data(), in_.vlp16_packets.data(), in_.vlp16_stamps.data(), in_.W, nullptr, &vlp16_info_));
+      n_scans_ = in_.vlp16_stamps.size();
+    }
   }
   ~Calibrator() { lvx_destroy(ctx_); }
   Calibrator(const Calibrator&) = delete;
@@ -257,7 +266,7 @@ class Calibrator {
     if ((int)state->size() != lvx_state_size(ctx_)) throw std::invalid_argument("state size does not match the problem");
     std::vector<StageReport> rep;
     if (opt_.solve0_so3_from_gyro) rep.push_back(Solve0(state));
-    if (opt_.lidar_odometry && in_.loam.all.empty() && !in_.scans.empty()) EnsureOdometry();
+    if (opt_.lidar_odometry && in_.loam.all.empty() && n_scans_ > 0) EnsureOdometry();
     const bool have_poses = !in_.loam.all.empty() || !odom_.pose16.empty();
     if (opt_.init_lidar_rotation && have_poses) rep.push_back(InitializeRotation(state));
     for (int it = 0; it < opt_.refine_iterations; ++it) {
@@ -365,7 +374,7 @@ class Calibrator {
       if (im.size() != px) throw std::invalid_argument("RenderMap: image size does not match the camera");
       std::copy(im.begin(), im.end(), pack.begin() + k * px); t[k] = image_t[(size_t)r.candidates[k]];
     }
-    r.cloud.assign(in_.scans.size() * (size_t)in_.H * in_.W, lvx_point_xyzrgb{});
+    r.cloud.assign(n_scans_ * (size_t)in_.H * in_.W, lvx_point_xyzrgb{});
     r.valid.assign(r.candidates.size(), 0);
     check(lvx_render_map(ctx_, state.data(), in_.map_time, 0, nullptr, (int)r.candidates.size(), pack.data(), in_.camera.cols, t.data(), nullptr, r.cloud.data(), r.valid.data(), &r.n_colored));
     return r;
@@ -374,7 +383,7 @@ class Calibrator {
   // lands; scan_of_pair / image_of_pair say which pair a mask belongs to, valid[i] = 0: a pose outside the spline (the mask is zero)
   struct Overlay { std::vector<int32_t> scan_of_pair, image_of_pair, valid; std::vector<uint8_t> masks; };
   Overlay OverlayScans(const std::vector<double>& state, const std::vector<double>& scan_t, const std::vector<double>& image_t) {
-    if (scan_t.size() != in_.scans.size()) throw std::invalid_argument("OverlayScans: one time per scan");
+    if (scan_t.size() != n_scans_) throw std::invalid_argument("OverlayScans: one time per scan");
     Overlay o;
     const std::vector<int32_t> m = MatchScanImages(scan_t, image_t);
     std::vector<double> st, it;
@@ -395,6 +404,10 @@ class Calibrator {
   }
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }
+  size_t n_scans() const { return n_scans_; }
+  int scan_height() const { return in_.H; }
+  int scan_width() const { return in_.W; }
+  const lvx_vlp16_info& vlp16_info() const { return vlp16_info_; }   // of the constructor's lvx_set_scans_vlp16 (zero without packets)
   const std::vector<int32_t>& key_scans() const { return key_scans_; }   // of the first-map association: 1 where the scan joined the key-scan map
   const LidarOdometry& odometry() const { return odom_; }                // CalibrateOptions::lidar_odometry: what RunLidarOdometry returned (empty before Run)
   lvx_ctx* context() { return ctx_; }
@@ -416,11 +429,11 @@ class Calibrator {
   // the scans' odometry poses from lvx_lidar_odometry, once (the scans do not change)
   void EnsureOdometry() {
     if (!odom_.pose16.empty()) return;
-    if (in_.scan_stamps.size() != in_.scans.size()) throw std::invalid_argument("scan_stamps: one header stamp per scan is needed for the LiDAR odometry");
+    if (in_.scan_stamps.size() != n_scans_) throw std::invalid_argument("scan_stamps: one header stamp per scan is needed for the LiDAR odometry");
     lvx_odom_options oo; lvx_odom_default_options(&oo);   // (oo.ndt.search: DIRECT7 as ndtInit sets it; 0 / 1 / 26 select KDTREE / DIRECT1 / DIRECT26)
     oo.ndt_resolution = opt_.ndt_resolution; oo.key_dist = opt_.key_scan_dist; oo.key_angle_deg = opt_.key_scan_angle_deg;
     odom_ = RunLidarOdometry(ctx_, in_.scan_stamps, &oo);
-    if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] LiDAR odometry: %zu scans, %d key scans\n", in_.scans.size(), (int)odom_.n_key);
+    if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] LiDAR odometry: %zu scans, %d key scans\n", n_scans_, (int)odom_.n_key);
   }
   // a scan's odometry pose: the pose file's (PoseOfScan), or — without one — the 4 x 4 lvx_lidar_odometry wrote for it, as it is
   bool pose_of_scan(int idx, double scan_t, double T[16]) const {
@@ -457,7 +470,7 @@ class Calibrator {
   // DataAssociation of the InitializationDone branch (lvi_initialize_surfel_orb.cpp:1175-1178): Mapping() with the LOAM poses, undistortScanInMap(odom_data_map), setSurfelMap
   // on the key-scan map's NDT grid, getAssociation per scan
   void FirstDataAssociation(const std::vector<double>& state) {
-    const size_t S = in_.scans.size();
+    const size_t S = n_scans_;
     if (in_.scan_stamps.size() != S) throw std::invalid_argument("scan_stamps: one header stamp per scan is needed for the first map");
     std::vector<double> poses(S * 16, 0.0); std::vector<int32_t> has(S, 0);
     for (size_t s = 0; s < S; ++s) has[s] = pose_of_scan((int)s, in_.scan_stamps[s], &poses[16 * s]) ? 1 : 0;
@@ -481,7 +494,7 @@ class Calibrator {
     if (n > 0) check(lvx_get_surfel_points(ctx_, n, sp_pt_.data(), sp_map_.data(), sp_t_.data(), sp_plane_.data()));
     if (opt_.keep_history) {
       AssociationRecord r; r.state = state; r.planes = planes_; r.pt = sp_pt_; r.pt_map = sp_map_; r.t = sp_t_; r.plane = sp_plane_;
-      if (opt_.keep_clouds) { r.scans_in_map.assign(in_.scans.size() * (size_t)in_.H * in_.W * 4, 0.f); check(lvx_get_scans_in_map(ctx_, r.scans_in_map.data())); }
+      if (opt_.keep_clouds) { r.scans_in_map.assign(n_scans_ * (size_t)in_.H * in_.W * 4, 0.f); check(lvx_get_scans_in_map(ctx_, r.scans_in_map.data())); }
       assoc_history_.push_back(std::move(r));
     }
     if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] association: %d surfels, %d surfel points (every %d-th is used)\n", np, n, opt_.downsample_step);
@@ -583,8 +596,23 @@ class Calibrator {
     if (rc == LVX_E_RANGE) throw std::range_error(msg);
     throw std::runtime_error(msg + " (lvx error " + std::to_string(rc) + ")");
   }
+  // CalibrateInput::vlp16_*: the shape of the scans the device will unpack, and the default scan_stamps
+  static CalibrateInput Resolved(CalibrateInput in) {
+    if (in.vlp16_stamps.empty()) return in;
+    if (!in.scans.empty()) throw std::invalid_argument("CalibrateInput: scans or vlp16_packets, not both");
+    const size_t n = in.vlp16_stamps.size();
+    if (in.vlp16_packet_offsets.size() != n + 1) throw std::invalid_argument("vlp16_packet_offsets: one more entry than vlp16_stamps");
+    int longest = 0;
+    for (size_t s = 0; s < n; ++s) longest = std::max(longest, in.vlp16_packet_offsets[s + 1] - in.vlp16_packet_offsets[s]);
+    if (in.vlp16_packet_offsets[0] < 0 || (size_t)in.vlp16_packet_offsets[n] * LVX_VLP16_PACKET_BYTES > in.vlp16_packets.size())
+      throw std::invalid_argument("vlp16_packet_offsets reach outside vlp16_packets");
+    in.H = 16; in.W = std::max(in.W, 24 * longest);
+    if (in.scan_stamps.empty()) in.scan_stamps = in.vlp16_stamps;
+    return in;
+  }
   lvx_ctx* ctx_ = nullptr;
   const CalibrateInput in_;
+  size_t n_scans_ = 0; lvx_vlp16_info vlp16_info_{};
   CalibrateOptions opt_;
   std::vector<AssociationRecord> assoc_history_;
   std::vector<double> hist_cost_, hist_radius_, stage_state_in_; std::vector<int32_t> hist_acc_;

@@ -153,6 +153,10 @@ class Context:
         if rc != OK:
             raise LvxError(rc, self._l.lvx_last_error(self._h).decode())
 
+    def set_scans_vlp16(self, packets, packet_offsets, scan_stamp, W=0, **options):
+        """Raw scans from VLP-16 packets, unpacked on the device: see set_scans_vlp16 below."""
+        return set_scans_vlp16(self, packets, packet_offsets, scan_stamp, W, **options)
+
     # --- problem description (same argument meaning as oracle.Oracle) ---
     def set_spline(self, t0, dt, n_knots):
         self._ck(self._l.lvx_set_spline(self._h, C.c_double(t0), C.c_double(dt), C.c_int(n_knots)))
@@ -903,6 +907,85 @@ def get_surfel_points(ctx, n_points):
 def get_scans_in_map(ctx, n_scans, H, W):
     out = np.zeros((n_scans, H, W, 4), np.float32)
     ctx._ck(ctx._l.lvx_get_scans_in_map(ctx._h, _p(out)))
+    return out
+
+
+class Vlp16Options(C.Structure):
+    """lvx_vlp16_options (include/lvx.h): VelodyneCorrection's range bounds [m] and angle window [hundredths of a degree]."""
+    _fields_ = [("min_range", C.c_double), ("max_range", C.c_double), ("min_angle", C.c_int32), ("max_angle", C.c_int32)]
+
+
+class Vlp16Info(C.Structure):
+    _fields_ = [("n_packets", C.c_int64), ("n_in_range", C.c_int64), ("n_out_of_range", C.c_int64), ("n_outside_window", C.c_int64), ("n_bad_headers", C.c_int64),
+                ("W", C.c_int32), ("reserved", C.c_int32)]
+
+
+VLP16_PACKET_BYTES = 1206
+
+
+def vlp16_default_options(**kw):
+    o = Vlp16Options()
+    rc = lib().lvx_vlp16_default_options(C.byref(o))
+    if rc != OK:
+        raise LvxError(rc, "lvx_vlp16_default_options")
+    for k, v in kw.items():
+        if k not in ("min_range", "max_range", "min_angle", "max_angle"):
+            raise TypeError("unknown VLP-16 option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def _vlp16_args(packets, packet_offsets, scan_stamp):
+    pk = np.frombuffer(packets, np.uint8) if isinstance(packets, (bytes, bytearray, memoryview)) else np.ascontiguousarray(packets, dtype=np.uint8).reshape(-1)
+    if pk.size % VLP16_PACKET_BYTES:
+        raise ValueError("packets: %d bytes is not a multiple of %d" % (pk.size, VLP16_PACKET_BYTES))
+    off, st = _i(np.asarray(packet_offsets).reshape(-1)), _d(np.asarray(scan_stamp, dtype=np.float64).reshape(-1))
+    if len(off) != len(st) + 1 or (len(st) and (off[0] < 0 or off[-1] > pk.size // VLP16_PACKET_BYTES)):
+        raise ValueError("packet_offsets: one more entry than scan_stamp, inside the packets")
+    return pk, off, st
+
+
+def _vlp16_info(i):
+    return {k: int(getattr(i, k)) for k, _ in Vlp16Info._fields_ if k != "reserved"}
+
+
+def set_scans_vlp16(ctx, packets, packet_offsets, scan_stamp, W=0, **options):
+    """The context's raw scans from VLP-16 packets, unpacked on the device (lvx_set_scans_vlp16): packets = bytes or uint8 [n][1206], scan s = packets
+    [packet_offsets[s], packet_offsets[s + 1]), scan_stamp[s] its header stamp; W = 0: 24 x the longest scan.  options: min_range, max_range, min_angle, max_angle.
+    Returns the info record as a dict (W, n_packets, n_in_range, n_out_of_range, n_outside_window, n_bad_headers)."""
+    pk, off, st = _vlp16_args(packets, packet_offsets, scan_stamp)
+    o, info = vlp16_default_options(**options), Vlp16Info()
+    ctx._ck(ctx._l.lvx_set_scans_vlp16(ctx._h, C.c_int(len(st)), _p(off), _p(pk), _p(st), C.c_int(W), C.byref(o), C.byref(info)))
+    ctx._n_scans = len(st)
+    return _vlp16_info(info)
+
+
+def vlp16_unpack(ctx, packets, packet_offsets, scan_stamp, W=0, **options):
+    """The same records into a host array (lvx_vlp16_unpack; the context's scans are untouched): (records [n_scans][16][W] POINT_XYZIT, info)."""
+    pk, off, st = _vlp16_args(packets, packet_offsets, scan_stamp)
+    o, info = vlp16_default_options(**options), Vlp16Info()
+    longest = int(np.diff(off).max()) if len(st) else 0
+    cap_w = max(int(W), 24 * max(longest, 0), 1)   # what the call can write when it accepts the arguments
+    out = np.zeros((len(st), 16, cap_w), POINT_XYZIT)
+    ctx._ck(ctx._l.lvx_vlp16_unpack(ctx._h, C.c_int(len(st)), _p(off), _p(pk), _p(st), C.c_int(W), C.byref(o), _p(out), C.byref(info)))
+    return out.reshape(-1)[:len(st) * 16 * info.W].reshape(len(st), 16, info.W), _vlp16_info(info)
+
+
+def set_scans_organised(ctx, xyzi, scan_stamp):
+    """Organised clouds [n_scans][H][W][4] float32 (x, y, z, intensity) with per-scan header stamps: the context's raw scans with the times of unpack_scan's
+    PointCloud2 overload (lvx_set_scans_organised)."""
+    xyzi = np.ascontiguousarray(xyzi, dtype=np.float32)
+    assert xyzi.ndim == 4 and xyzi.shape[3] == 4
+    st = _d(np.asarray(scan_stamp, dtype=np.float64).reshape(-1))
+    assert len(st) == xyzi.shape[0]
+    ctx._ck(ctx._l.lvx_set_scans_organised(ctx._h, C.c_int(xyzi.shape[0]), C.c_int(xyzi.shape[1]), C.c_int(xyzi.shape[2]), _p(xyzi), _p(st)))
+    ctx._n_scans = xyzi.shape[0]
+
+
+def get_scans_raw(ctx, first, n, H, W):
+    """Scans [first, first + n) of the context, however they were set (lvx_get_scans_raw): [n][H][W] POINT_XYZIT."""
+    out = np.zeros((max(n, 0), H, W), POINT_XYZIT)
+    ctx._ck(ctx._l.lvx_get_scans_raw(ctx._h, C.c_int(first), C.c_int(n), _p(out)))
     return out
 
 
