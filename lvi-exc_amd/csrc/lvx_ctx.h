@@ -123,7 +123,7 @@ struct lvx_ctx {
   std::function<void()> before_eval_sync;   // run_evaluate calls it right before it waits for the pass's cost: what the caller wants on the host after the SAME host stop (the LM loop: step norms, the candidate's diagonal and gradient norm)
   bool force_legacy = false;   // set when the fast assembly kernels hit a case only the per-segment kernels handle exactly
   lvx::DevBuf d_pre;   // So3Pre[N]
-  lvx::DevBuf d_repT;   // [rep.n][56] landmark-row records of the reprojection blocks (k_reproj_cross -> k_reproj_lmrows)
+  lvx::DevBuf d_repT;   // [rep.n][56] landmark-row records of the reprojection blocks (k_reproj_jac -> k_reproj_lmrows)
   lvx::DevBuf d_lm_grp; int lm_ngrp = 0, lm_gspread = 0;   // landmark groups of the elimination kernel (k_lm_schur_grp): [ngrp + 1 offsets | landmark ids sorted by first band position]
   lvx::DevBuf d_lmH, d_lm_p0, d_Hr, d_Br, d_red; int lm_wl = 0, lm_ls = 0; const double* p_Hs = nullptr;   // landmark rows (DevCommon::lmH); solver: band / border rows / [g_b | C | g_c] after the landmark elimination
   int hub_near_lo = 0, hub_near_hi = 0;   // band positions a residual can couple to a hub knot DIRECTLY (not through the pseudo pose): IMU / LiDAR rows within 4 knots, reprojection blocks within their span

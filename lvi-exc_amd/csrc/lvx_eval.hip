@@ -422,9 +422,27 @@ __global__ __launch_bounds__(64 * PW) void k_family(F fam, DevCommon cm, const u
 // ---------------------------------------------------------------------------------------------------------
 // u-independent SO3 quantities of every control-point pair (k, k+1) — log, |Omega|, J_r^-1 — once per pass instead of once per workgroup
 // (the fused kernels copy their CR + 4 entries into LDS) and once per row (reprojection Jacobian kernel): k_state_prepass below
-__device__ void hub_eval_thread(const DevCommon& cm, double t_map, int want_surf, int want_cs, HubShared* hubs, int s) {
+// the wavefront's exchange through LDS: what the lanes wrote before is visible to all of them behind it (one wavefront: no __syncthreads())
+__device__ __forceinline__ void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// pose at t_map of hub set s (0: surfel, 1: camera-surfel) and its hub_matrix on ONE wavefront (lvx_resid.h: hub_lanes_*); every lane looks the knot interval up
+template <bool NEED_V> __device__ __forceinline__ bool hub_pose_wave(const SplineRef& sp, const KnotRef& kh, int lane, HubLanes* X, HubShared* h) {
+  hub_lanes_pairs<NEED_V>(sp, kh, lane, X, &h->A);
+  wave_sync_lds();
+  if (!hub_lanes_ok(X)) return false;
+  hub_lanes_coefs(lane, X);
+  wave_sync_lds();
+  hub_lanes_knots<NEED_V>(lane, X, &h->A);
+  wave_sync_lds();
+  return true;
+}
+__device__ void hub_eval_wave(const DevCommon& cm, double t_map, int want_surf, int want_cs, HubShared* hubs, int s, int lane) {
+  __shared__ HubLanes xs[2];
   if (s > 1) return;
-  if ((s == 0 && !want_surf) || (s == 1 && !want_cs)) { hubs[s].ok = 0; return; }
+  if ((s == 0 && !want_surf) || (s == 1 && !want_cs)) { if (lane == 0) hubs[s].ok = 0; return; }
 #ifdef LVX_KTIME_FOLD   // tools/build_kt.sh FOLD: s_memtime ticks of the hub chain's phases (debug print), and when it ends (k_clear prints its last block's end)
   long long kt_[5] = {0, 0, 0, 0, 0}; long long kt0_ = __builtin_amdgcn_s_memtime(); const long long kts_ = kt0_;
 #define HKT(i) { const long long n_ = __builtin_amdgcn_s_memtime(); kt_[i] += n_ - kt0_; kt0_ = n_; }
@@ -437,24 +455,26 @@ __device__ void hub_eval_thread(const DevCommon& cm, double t_map, int want_surf
   const double tau = s == 0 ? cal.lidar.tau : cal.cam.tau;
   double s1[1][2]; hub_spans(t_map, tl, cm.sensor_mto, s1);
   HKT(0)
-  Segs sg; KnotRef kh; hubs[s].ok = 0;
-  if (!build_segments(sp, s1, 1, &sg)) return;
-  if (!seg_lookup(sp, sg, t_map + tau, &kh)) return;
+  Segs sg; KnotRef kh;
+  if (!build_segments(sp, s1, 1, &sg) || !seg_lookup(sp, sg, t_map + tau, &kh)) { if (lane == 0) hubs[s].ok = 0; return; }
   HKT(1)
-  if (!(tl ? pose_eval<true>(sp, kh, &hubs[s].A) : pose_eval<true, true>(sp, kh, &hubs[s].A))) { hubs[s].ok = -RES_NONUNIT; return; }   // a free offset differentiates through the hub's velocity / angular velocity
+  if (!(tl ? hub_pose_wave<false>(sp, kh, lane, &xs[s], &hubs[s]) : hub_pose_wave<true>(sp, kh, lane, &xs[s], &hubs[s]))) {   // a free offset differentiates through the hub's velocity / angular velocity
+    if (lane == 0) hubs[s].ok = -RES_NONUNIT;
+    return;
+  }
   HKT(2)
-  hub_matrix(hubs[s].A, hubs[s].M);   // once here instead of by one thread of each of the fold's ~600 workgroups
-  hubs[s].ok = 1;
+  hub_lanes_matrix(lane, &xs[s], hubs[s].M);   // once here instead of by one thread of each of the fold's ~600 workgroups
+  if (lane == 0) hubs[s].ok = 1;
   HKT(3)
 #ifdef LVX_KTIME_FOLD
-  printf("HKT hub set %d: cal+spans %lld segments+lookup %lld pose_eval %lld hub_matrix+stores %lld | total %lld, ends at %lld (ticks of s_memtime)\n", s, kt_[0], kt_[1], kt_[2], kt_[3],
-         (long long)__builtin_amdgcn_s_memtime() - kts_, (long long)__builtin_amdgcn_s_memtime());
+  if (lane == 0) printf("HKT hub set %d: cal+spans %lld segments+lookup %lld pose_eval %lld hub_matrix+stores %lld | total %lld, ends at %lld (ticks of s_memtime)\n", s, kt_[0], kt_[1], kt_[2], kt_[3],
+                        (long long)__builtin_amdgcn_s_memtime() - kts_, (long long)__builtin_amdgcn_s_memtime());
 #endif
 }
 // everything that depends on the state only: blocks [0, nblk_tab) fill the control-point-pair table, the next block evaluates the shared
-// t_map poses; run by the first blocks of the pass's clear kernel (k_clear)
+// t_map poses, one wavefront per hub set; run by the first blocks of the pass's clear kernel (k_clear)
 __device__ __forceinline__ void state_prepass_block(const DevCommon& cm, So3Pre* tab, int nblk_tab, double t_map, int want_surf, int want_cs, HubShared* hubs, int blk) {
-  if (blk >= nblk_tab) { hub_eval_thread(cm, t_map, want_surf, want_cs, hubs, threadIdx.x); return; }
+  if (blk >= nblk_tab) { hub_eval_wave(cm, t_map, want_surf, want_cs, hubs, threadIdx.x >> 6, threadIdx.x & 63); return; }
   const int k = blk * blockDim.x + threadIdx.x;
   if (k >= cm.N) return;
   const double* so3 = cm.state + 3 * (size_t)cm.N;
@@ -811,44 +831,52 @@ __global__ __launch_bounds__(64 * RX_NW) void k_reproj_cross(RepCross rc, DevCom
   }
 }
 
-// Landmark rows from the per-block records of k_reproj_cross: a wavefront OWNS landmark l — it sums the records of the landmark's blocks into
-// an LDS image of the row [band couplings | border couplings | H_ll | g_l] and stores the whole row (no atomics, nothing to clear beforehand).
+// Landmark rows from the per-block records RepLmRows::T (formed by k_reproj_jac, where the rows sit in registers): a wavefront OWNS landmark l — it sums the records of
+// the landmark's blocks into an LDS image of the row [band couplings | border couplings | H_ll | g_l] and stores the whole row (no atomics, nothing to clear beforehand).
+// The kernel's duration is the latency of its slowest wavefront (every wavefront is resident at once), so the loads are issued together: lane b fetches the index and the two
+// knot intervals of block b (up to 64 blocks per round), then the records and the positions of a GROUP of LMR_G blocks are requested before the first LDS add — a ten-view
+// landmark waits for three dependent rounds (index, intervals, records + positions), not for three per trip of four.  The adds of a slot keep ascending block order.
+constexpr int LMR_G = 16;
 struct RepLmRows { const double* T; const int* k; int n; const int* ptr; const int* rows; int L; };   // blocks of landmark l: rows[ptr[l] .. ptr[l + 1])
 template <bool TAU>
 __global__ __launch_bounds__(256) void k_reproj_lmrows(RepLmRows q, DevCommon cm) {
   constexpr int RW = 56 + (TAU ? 1 : 0);   // record: [ref knots 24 | obs knots 24 | camera 6 | H_ll | g_l (| camera time offset)]
   extern __shared__ double rowbuf[];   // 4 x [lm_ls]
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;   // (the landmark and its block range are scalars)
   const int l = blockIdx.x * 4 + wv;
   if (l >= q.L) return;
+  const int j0 = q.ptr[l], j1 = q.ptr[l + 1], p0 = cm.lm_p0[l], N = cm.N;
+  // what a lane's position does not take from the block: camera columns, H_ll / g_l (54, 55), the camera time offset (56)
+  const int pc_fix = lane < 48 ? LVX_DEAD : (lane < 54 ? cm.ord[6 * N + 15 + (lane - 48)] : (lane < 56 ? LVX_LM_BASE : (lane < RW ? cm.ord[6 * N + 21] : LVX_DEAD)));
+  const int c24 = lane < 24 ? lane : lane - 24;   // knot column of the lane inside its pose's four knots: ord[6 * (k + c / 6) + c % 6] = ord[6 * k + c]
   double* rb = rowbuf + (size_t)wv * cm.lm_ls;
   for (int k = lane; k < cm.lm_ls; k += 64) rb[k] = 0.0;
-  const int j0 = q.ptr[l], j1 = q.ptr[l + 1], p0 = cm.lm_p0[l], N = cm.N;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
-  for (int jb = j0; jb < j1; jb += 4) {   // 4 blocks in flight
-    double val[4]; int pc[4];
+  for (int jc = j0; jc < j1; jc += 64) {   // every trip count below is wave-uniform: the lane exchanges read active lanes only
+    const int nc = min(64, j1 - jc);
+    int bi = 0, bkr = 0, bko = -1;   // lane b: block jc + b
+    if (lane < nc) { bi = q.rows[jc + lane]; bkr = q.k[bi]; bko = q.k[(size_t)q.n + bi]; }
+    for (int g0 = 0; g0 < nc; g0 += LMR_G) {
+      double val[LMR_G]; int pc[LMR_G];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      val[u] = 0.0; pc[u] = LVX_DEAD;
-      if (jb + u < j1 && lane < RW) {
-        const int i = q.rows[jb + u];
-        const int kr = q.k[i], ko = q.k[(size_t)q.n + i];
-        if (ko >= 0) {
-          val[u] = q.T[(size_t)i * RW + lane];
-          const int c = lane < 24 ? lane : lane - 24;
-          pc[u] = lane < 48 ? cm.ord[6 * ((lane < 24 ? kr : ko) + c / 6) + c % 6] : (lane < 54 ? cm.ord[6 * N + 15 + (lane - 48)] : (lane < 56 ? LVX_LM_BASE : cm.ord[6 * N + 21]));   // 54: H_ll, 55: g_l, 56: camera time offset
-        }
+      for (int u = 0; u < LMR_G; ++u) {
+        val[u] = 0.0; pc[u] = LVX_DEAD;
+        if (g0 + u >= nc) continue;
+        const int i = __builtin_amdgcn_readlane(bi, g0 + u), kr = __builtin_amdgcn_readlane(bkr, g0 + u), ko = __builtin_amdgcn_readlane(bko, g0 + u);
+        if (ko < 0 || lane >= RW) continue;   // a skipped block: its record is never read
+        val[u] = q.T[(size_t)i * RW + lane];
+        pc[u] = lane < 48 ? cm.ord[6 * (lane < 24 ? kr : ko) + c24] : pc_fix;
       }
-    }
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      if (pc[u] == LVX_DEAD || val[u] == 0.0) continue;
-      int slot;
-      if (lane == 54 || lane == 55) slot = cm.lm_wl + cm.nbd + (lane - 54);
-      else if (pc[u] >= 0) { slot = pc[u] - p0; if (slot < 0 || slot >= cm.lm_wl) { atomicOr(cm.err, 4); continue; } }
-      else slot = cm.lm_wl + (-1 - pc[u]);
-      atomicAdd(&rb[slot], val[u]);   // LDS: the same variable can appear through both poses of a block
+      for (int u = 0; u < LMR_G; ++u) {
+        if (pc[u] == LVX_DEAD || val[u] == 0.0) continue;
+        int slot;
+        if (lane == 54 || lane == 55) slot = cm.lm_wl + cm.nbd + (lane - 54);
+        else if (pc[u] >= 0) { slot = pc[u] - p0; if (slot < 0 || slot >= cm.lm_wl) { atomicOr(cm.err, 4); continue; } }
+        else slot = cm.lm_wl + (-1 - pc[u]);
+        atomicAdd(&rb[slot], val[u]);   // LDS: the same variable can appear through both poses of a block
+      }
     }
   }
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2954,7 +2982,7 @@ __global__ __launch_bounds__(256) void k_clear(ClearList cl, BandClear bc, int n
   }
   const int first = npre + bc.nblk + bc.hub_blk;
   const size_t stride = (size_t)(gridDim.x - first) * blockDim.x, t0 = (size_t)(blockIdx.x - first) * blockDim.x + threadIdx.x;
-  for (int b = 0; b < cl.n; ++b) {   // 4 stores per trip: the prepass code leaves this kernel 2 wavefronts per SIMD, the stores keep HBM busy anyway
+  for (int b = 0; b < cl.n; ++b) {   // 4 stores per trip: measured again at 7 wavefronts per SIMD (the hub block on a wavefront: 72 VGPRs) — k_clear 14.0 us, with 2 stores 18.2, with 1 store 17.9
     const size_t nw = cl.words[b];
     size_t i = t0;
     for (; i + 3 * stride < nw; i += 4 * stride) {
@@ -3124,7 +3152,7 @@ template <class Fn> static int with_tau(bool tau, Fn&& fn) { return tau ? fn(std
 static int step_clear(Pass& p) {
   lvx_ctx* ctx = p.ctx; DevCommon& cm = p.cm; const uint32_t what = p.what; hipStream_t st = p.st;
   const bool fast = p.fast, fb = p.fb, fast_surf = p.fast_surf, fast_cs = p.fast_cs, imu_own = p.imu_own;
-  // the control-point-pair table and the shared t_map poses (one thread, ~25 us) depend on the state only: the first blocks of the clear kernel
+  // the control-point-pair table and the shared t_map poses (one wavefront per hub set) depend on the state only: the first blocks of the clear kernel
   const int nblk_tab = fast ? (ctx->N + 255) / 256 : 0, npre = fast ? nblk_tab + ((fast_surf || fast_cs) ? 1 : 0) : 0;
   ClearList cl{}; BandClear bc{};
   auto add = [&](void* ptr, size_t bytes) { if (cl.n < 16) { cl.p[cl.n] = (uint4*)ptr; cl.words[cl.n] = (bytes + 15) / 16; cl.n++; } };

@@ -472,6 +472,101 @@ LVX_HD void hub_matrix(const PoseEval& h, double M[6][24]) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// The hub pose — pose_eval<true, NEED_V> and hub_matrix — over the lanes of ONE wavefront instead of one lane (the hub block of k_clear: its
+// duration was a single lane's FP64 chain).  Four phases with a wave barrier between them; the pieces of a phase do not depend on each other:
+//   hub_lanes_pairs   lanes 0..2: the control-point pair j = lane + 1 — log, E_j and its rotation, J_r^-1, P_j; lane 3: position, velocity, control points
+//   hub_lanes_coefs   lanes 0..2: T_j = S_j P_j; lane 3: (R1 R2 R3)^T — a phase of its own keeps the matrices a lane holds, and with them the registers of k_clear, few
+//   hub_lanes_knots   lane k = 0..3: dxi[k] from T_k, T_k+1, the same code on every lane; lane 0 also q and, with NEED_V, w_body (pose_eval asks so3_eval for no dw)
+//   hub_lanes_matrix  the 144 entries of hub_matrix, entry = lane, lane + 64, lane + 128
+// The expressions are so3_eval's: T_3 = P_3 becomes a product with the identity and Xe[3] = T_3 Jri_3 a subtraction of zero — both exact, so every output has
+// the value the one-lane evaluation gives (a zero may change its sign).  tests/native/hub_lanes_host_check.cpp runs the phases as loops over lanes against pose_eval + hub_matrix.
+// ---------------------------------------------------------------------------------------------
+struct HubLanes { quat c[4], E[4]; double B[4], dB[4], Bp[4]; v3 d[4]; m3 R[4], Jri[4], P[4], T[4], dxi[4]; int ok[4]; };   // the exchange area of one hub set (indices 1..3: pairs)
+
+template <bool NEED_V>
+LVX_HD void hub_lanes_pairs(const SplineRef& sp, const KnotRef& k, int lane, HubLanes* X, PoseEval* out) {
+  if (lane < 3) {
+    const int j = lane + 1;
+    const double u = k.u, u2 = u * u, u3 = u2 * u;
+    const double B1 = 5.0 / 6.0 + u * (3.0 / 6.0) + u2 * (-3.0 / 6.0) + u3 * (1.0 / 6.0), B2 = 1.0 / 6.0 + u * (3.0 / 6.0) + u2 * (3.0 / 6.0) + u3 * (-2.0 / 6.0), B3 = u3 * (1.0 / 6.0);
+    const double Bj = j == 1 ? B1 : (j == 2 ? B2 : B3);
+    X->B[j] = Bj;
+    if (NEED_V) {
+      const double di = 1.0 / sp.dt;
+      const double U1 = di, U2 = di * (2.0 * u), U3 = di * (3.0 * u2);
+      const double dB1 = U1 * (3.0 / 6.0) + U2 * (-3.0 / 6.0) + U3 * (1.0 / 6.0), dB2 = U1 * (3.0 / 6.0) + U2 * (3.0 / 6.0) + U3 * (-2.0 / 6.0), dB3 = U3 * (1.0 / 6.0);
+      X->dB[j] = j == 1 ? dB1 : (j == 2 ? dB2 : dB3);
+    }
+    bool ok = true;
+    const v3 Om = logq_half(qmul(qconj(load_q(sp.so3 + 4 * (k.i0 + j - 1))), load_q(sp.so3 + 4 * (k.i0 + j))), &ok);
+    const v3 d = 2.0 * Om;
+    const quat E = expq_half(Bj * Om);
+    X->d[j] = d; X->E[j] = E; X->R[j] = rotmat(E); X->ok[j] = ok ? 1 : 0;
+    X->Jri[j] = so3_Jr_inv(d);
+    X->P[j] = Bj * so3_Jr(Bj * d);
+  } else if (lane == 3) {
+    out->k = k;
+    R3Basis b; r3_basis(k.u, sp.dt, &b);
+    v3 p = mk(0, 0, 0), v = mk(0, 0, 0);
+    for (int j = 0; j < 4; ++j) {
+      const v3 cj = load_v3(sp.r3 + 3 * (k.i0 + j));
+      out->Bp[j] = b.Bp[j]; X->Bp[j] = b.Bp[j]; p = p + b.Bp[j] * cj;
+      if (NEED_V) v = v + b.Bv[j] * cj;
+      X->c[j] = load_q(sp.so3 + 4 * (k.i0 + j));
+    }
+    out->p = p;
+    if (NEED_V) out->v = v;
+  }
+}
+LVX_HD bool hub_lanes_ok(const HubLanes* X) { return X->ok[1] && X->ok[2] && X->ok[3]; }
+
+// T_j = S_j P_j, the coefficient of delta d_j in xi (T_1 = R3^T R2^T P_1, T_2 = R3^T P_2, T_3 = P_3), on lane j - 1; R1 R2 R3 transposed on lane 3
+LVX_HD void hub_lanes_coefs(int lane, HubLanes* X) {
+  if (lane < 3) {
+    const int j = lane + 1;
+    const m3 R3 = X->R[3];
+    const m3 R32t = tmul(R3, transpose(X->R[2]));      // R3^T R2^T
+    X->T[j] = (j == 1 ? R32t : (j == 2 ? transpose(R3) : m3_identity())) * X->P[j];
+  } else if (lane == 3) {
+    X->T[0] = tmul(X->R[1] * (X->R[2] * X->R[3]), m3_identity());
+  }
+}
+template <bool NEED_V>
+LVX_HD void hub_lanes_knots(int lane, HubLanes* X, PoseEval* out) {
+  if (lane >= 4) return;
+  const int k = lane;
+  // d xi / d eta_k: Xe[0] = (R1 R2 R3)^T - T_1 Jri_1^T, Xe[k] = T_k Jri_k - T_k+1 Jri_k+1^T, Xe[3] = T_3 Jri_3
+  const int ja = k == 0 ? 1 : k, jb = k == 3 ? 3 : k + 1;
+  m3 first = X->T[ja] * X->Jri[ja];
+  m3 second = mul_t(X->T[jb], X->Jri[jb]);
+  if (k == 0) first = X->T[0];
+  if (k == 3) second = m3_zero();
+  const m3 Xe = first - second;
+  const m3 r = 2.0 * mul_t(Xe, rotmat(X->c[k]));   // eta_k = R(c_k)^T (2 delta_k)
+  out->so3.dxi[k] = r; X->dxi[k] = r;
+  if (lane == 0) {
+    quat q = X->c[0];
+    for (int j = 1; j < 4; ++j) q = qmul(q, X->E[j]);
+    out->so3.q = q;
+    if (NEED_V) {   // the body angular velocity (a free time offset differentiates through it); the hub takes no dw
+      const v3 w1 = X->dB[1] * X->d[1];
+      const v3 w2 = tmulv(X->R[2], w1) + X->dB[2] * X->d[2];
+      out->so3.w_body = tmulv(X->R[3], w2) + X->dB[3] * X->d[3];
+    }
+  }
+}
+
+// entry e = 24 a + c of hub_matrix
+LVX_HD double hub_lanes_entry(const HubLanes* X, int e) {
+  const int a = e / 24, c = e - 24 * a, j = c / 6, m = c - 6 * j;
+  if (a < 3) return m == a ? X->Bp[j] : 0.0;
+  return m >= 3 ? X->dxi[j].a[3 * (a - 3) + (m - 3)] : 0.0;
+}
+LVX_HD void hub_lanes_matrix(int lane, const HubLanes* X, double M[6][24]) {
+  for (int e = lane; e < 144; e += 64) M[e / 24][e % 24] = hub_lanes_entry(X, e);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Pinhole camera (sensors/pinhole_camera.h:96-238)
 // ---------------------------------------------------------------------------------------------
 LVX_HD void cam_distortion(const CamIntr& c, double x, double y, double* dx, double* dy, double D[4]) {
