@@ -132,6 +132,12 @@ int lvx_set_orientation_prior(lvx_ctx* ctx, int enable, double t, const double* 
 int lvx_set_planes(lvx_ctx* ctx, int n_planes, const double* plane_pi3);
 /* SurfelPoint list (src/lvi_exc/include/core/surfel_association.h:41-46) -> LiDARSurfelPoint blocks (trajectory_manager_lvi.cpp:571-581) */
 int lvx_set_surfel(lvx_ctx* ctx, int n, const double* pt3, const double* t, const int32_t* plane_id, double t_map, double huber, double weight);
+/* The same two calls with DEVICE pointers: the context copies what it needs on its stream at the call (the caller may reuse the buffers after lvx_synchronize);
+ * argument errors as the host forms (a plane id outside the table: LVX_E_ARG from lvx_set_surfel_d, the family stays as it was); n = 0 clears.  The family's
+ * layout (knot interval per row, stable sort, gather, row-ordered plane copy) then runs as kernels; the host reads the row count, the extremes of the plane ids and
+ * one count per knot interval, in the one host stop of lvx_set_surfel_d.  A host lvx_set_planes / lvx_set_surfel afterwards replaces the device-origin input. */
+int lvx_set_planes_d(lvx_ctx* ctx, int n_planes, const double* plane_pi3_d);
+int lvx_set_surfel_d(lvx_ctx* ctx, int n, const double* pt3_d, const double* t_d, const int32_t* plane_id_d, double t_map, double huber, double weight);
 /* sfm::Landmark table: reference observation uv and its view's t0 (kontiki/sfm/landmark.h:50-53, observation.h:35-37, view.h:34-35);
  * inverse depths live in the state vector */
 int lvx_set_landmarks(lvx_ctx* ctx, int n_landmarks, const double* uv_ref2, const double* t0_ref);
@@ -604,6 +610,11 @@ int lvx_get_surfel_map(lvx_ctx* ctx, int max_planes, lvx_surfel_plane* planes);
 /* rounds that took the one-stop chain since the context was created, and how many of those had to be repeated on the four-stop chain */
 int lvx_data_association_stats(lvx_ctx* ctx, int64_t* one_stop_rounds, int64_t* repeated_rounds);
 int lvx_get_surfel_points(lvx_ctx* ctx, int max_points, double* pt3, double* pt_map3, double* t, int32_t* plane);
+/* The surfel measurements of the evaluator from the last association without the lists leaving the device.  Equivalent to: lvx_get_surfel_map + lvx_set_planes with
+ * the records' Pi in order; lvx_get_surfel_points; the points 0, step, 2 step, ... (step <= 0: 1) with t >= t_map, in order; lvx_set_surfel(those, t_map, huber,
+ * weight).  n_used (may be NULL): how many were kept (0: the family is cleared).  LVX_E_STATE before any association on this context.  The family owns its copies:
+ * a later association or lvx_set_scans does not disturb it.  One host stop. */
+int lvx_set_surfel_from_association(lvx_ctx* ctx, int step, double t_map, double huber, double weight, int32_t* n_used);
 /* parity / debug: the de-skewed scans of the last lvx_data_association, [n_scans][H][W][4] float */
 int lvx_get_scans_in_map(lvx_ctx* ctx, float* xyzi4);
 

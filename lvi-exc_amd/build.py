@@ -16,7 +16,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-ato
 # Every csrc/*.hip is named here: "off", or DEFAULT (fast unless LVX_CONTRACT overrides it).  A source that is not listed is an error, never a silent default.
 DEFAULT = None
 CONTRACT = {"lvx_upstream.hip": "off", "lvx_render.hip": "off", "lvx_traj.hip": "off", "lvx_rotinit.hip": "off",
-            "lvx_api.hip": DEFAULT, "lvx_bcr.hip": DEFAULT, "lvx_eval.hip": DEFAULT, "lvx_solver.hip": DEFAULT, "lvx_stats.hip": DEFAULT}
+            "lvx_handoff.hip": "off", "lvx_api.hip": DEFAULT, "lvx_bcr.hip": DEFAULT, "lvx_eval.hip": DEFAULT, "lvx_solver.hip": DEFAULT, "lvx_stats.hip": DEFAULT}
 DEFAULT_CONTRACT = os.environ.get("LVX_CONTRACT", "fast")
 
 

@@ -119,6 +119,7 @@ void lvx_destroy(lvx_ctx* c) {
   if (c->d_comm.p) (void)hipFree(c->d_comm.p);
   bcr_destroy(c);
   stats_destroy(c);
+  handoff_destroy(c);
   traj_destroy(c);
   rotinit_destroy(c);
   for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv}) if (b->p) (void)hipFree(b->p);
@@ -157,13 +158,13 @@ int lvx_set_orientation_prior(lvx_ctx* c, int enable, double t, const double* q_
 }
 int lvx_set_planes(lvx_ctx* c, int n, const double* pi3) { if (c) c->cfg_version++;
   if (!c || n < 0 || (n > 0 && !pi3)) return LVX_E_ARG;
-  c->planes.assign(pi3, pi3 + 3 * (size_t)n); c->layout_dirty = true; return LVX_OK;
+  c->planes.assign(pi3, pi3 + 3 * (size_t)n); c->ho.planes_dev = c->ho.planes_stale = false; c->layout_dirty = true; return LVX_OK;
 }
 int lvx_set_surfel(lvx_ctx* c, int n, const double* pt3, const double* t, const int32_t* plane_id, double t_map, double huber, double weight) { if (c) c->cfg_version++;
   if (!c || n < 0 || (n > 0 && (!pt3 || !t || !plane_id))) return LVX_E_ARG;
   for (int i = 0; i < n; ++i) if (plane_id[i] < 0 || (size_t)plane_id[i] * 3 >= c->planes.size()) return fail(c, LVX_E_ARG, "plane id out of range (call lvx_set_planes first)");
   Family& f = c->surf; f.n = n; f.t.assign(t, t + n); f.a3.assign(pt3, pt3 + 3 * (size_t)n); f.id0.assign(plane_id, plane_id + n);
-  f.huber = huber; f.weight = weight; c->t_map = t_map; c->layout_dirty = true; return LVX_OK;
+  f.huber = huber; f.weight = weight; c->t_map = t_map; c->ho.surf_dev = false; c->layout_dirty = true; return LVX_OK;
 }
 int lvx_set_landmarks(lvx_ctx* c, int n, const double* uv_ref2, const double* t0_ref) { if (c) c->cfg_version++;
   if (!c || n < 0 || (n > 0 && (!uv_ref2 || !t0_ref))) return LVX_E_ARG;

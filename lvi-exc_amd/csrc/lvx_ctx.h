@@ -107,6 +107,19 @@ struct lvx_ctx {
   double t_map = 0;
   std::vector<double> planes, lm_uv, lm_t0;
   lvx::DevBuf d_planes, d_lm_uv, d_lm_t0;
+  // device hand-off of the surfel family (lvx_handoff.hip: lvx_set_planes_d, lvx_set_surfel_d, lvx_set_surfel_from_association).  planes_dev: the plane table came
+  // through a device pointer — d_planes_in owns the copy, `planes` above keeps its SIZE (every range check reads it) and is filled from the device only when a
+  // host-origin surfel family needs the values (planes_stale).  surf_dev: the surfel rows came through device pointers — in[sel] owns the selected rows in input order
+  // (the other set takes the next call, so a call that fails leaves the family as it was), surf.t / a3 / id0 stay empty (id0 is fetched on demand by the statistics'
+  // plane lists), id_min / id_max are the extremes of the plane ids.  hist: rows per knot interval (entry k + 1: interval k, entry 0: out of range) for the spline
+  // (hist_t0, hist_dt, hist_N), read through the pinned words `pin` ([0] rows, [1] id min, [2] id max, [4 ..] histogram) in the call's one host stop.
+  struct Handoff {
+    bool planes_dev = false, planes_stale = false, surf_dev = false, hist_valid = false;
+    int sel = 0, id_min = 0, id_max = -1, hist_N = 0; double hist_t0 = 0, hist_dt = 0;
+    lvx::DevBuf d_planes_in, in_t[2], in_pt[2], in_pl[2], d_key, d_iota, d_skey, d_work, d_tmp;
+    int* pin = nullptr; size_t pin_cap = 0;
+    std::vector<int> hist;
+  } ho;
   // layout
   bool layout_dirty = true;
   std::vector<int> ord;
@@ -194,6 +207,7 @@ struct lvx_ctx {
   // organised overload, [2] counters | scan stamps | packet offsets, [3] the records of lvx_vlp16_unpack
   lvx::DevBuf d_vlp[4]; bool vlp_tables = false;
   lvx::DevBuf d_da[8]; int da_S = 0, da_H = 0, da_W = 0, da_points = 0; std::vector<lvx_surfel_plane> da_planes;
+  bool da_valid = false;   // the last lvx_data_association / lvx_data_association_poses on this context succeeded: d_da[5] / d_da[7] hold its map and lists
   // lvx_data_association without host stops (round 5): capacities learned from the previous call (leaves, planes, association-grid list entries; 0 = none yet, the call
   // runs the synchronous path), the pinned mirror the device writes its counts into, the planes still to fetch from d_da[5] when somebody asks for them
   int da_cap_nl = 0, da_cap_P = 0, da_cap_list = 0, da_planes_pending = 0; int* da_pinned = nullptr; long long da_spec_runs = 0, da_spec_misses = 0;
@@ -251,6 +265,14 @@ int bcr_backward(lvx_ctx* c, double* Zy, double* Zx, int ldz, int nrhs);
 int bcr_gram(lvx_ctx* c, const double* Z, int ldz, int n, double* M, int row_major_nz = 0);
 void bcr_destroy(lvx_ctx* c);
 void stats_destroy(lvx_ctx* c);   // lvx_stats.hip
+int sort_pairs_u32(lvx_ctx* c, DevBuf& tmp, unsigned* k_in, unsigned* k_out, int* v_in, int* v_out, size_t n, int bits);   // lvx_upstream.hip: rocPRIM's stable radix sort of (key, value) pairs over the low `bits` key bits
+// lvx_handoff.hip: device-origin plane table / surfel family
+void handoff_destroy(lvx_ctx* c);
+int handoff_planes_from_records(lvx_ctx* c, int P, const void* records_d);   // plane table = the Pi of P lvx_surfel_plane records on the device
+int handoff_set_surfel(lvx_ctx* c, int total, int step, bool use_tmap, const double* pt3_d, const double* t_d, const int32_t* plane_d, double t_map, double huber, double weight, int32_t* n_used);   // rows 0, step, 2 step, ... of the device arrays (use_tmap: those with t >= t_map), in order
+int handoff_planes_to_device(lvx_ctx* c);   // ensure_layout: d_planes from whichever origin the table has (and the host values when a host-origin surfel family reads them)
+int handoff_layout_surfel(lvx_ctx* c, std::vector<int>& sorted_keys);   // ensure_layout: the surfel block of a device-origin family; the sorted keys come back for the chunk tables
+int handoff_fetch_ids(lvx_ctx* c);   // surf.id0 of a device-origin family, fetched once (lvx_stats.hip)
 void traj_destroy(lvx_ctx* c);    // lvx_traj.hip
 void rotinit_destroy(lvx_ctx* c); // lvx_rotinit.hip
 int traj_check_d(lvx_ctx* c);      // lvx_traj.hip: the non-unit-quaternion flag of the _d trajectory queries (lvx_synchronize)

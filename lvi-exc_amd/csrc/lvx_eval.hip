@@ -2414,7 +2414,8 @@ int ensure_layout(lvx_ctx* ctx) {
   int rc;
   {   // the plane / landmark tables may have been replaced (shrunk) after the families that index them were set
     const long long npl = (long long)ctx->planes.size() / 3;
-    for (int i = 0; i < ctx->surf.n; ++i) if (ctx->surf.id0[i] < 0 || ctx->surf.id0[i] >= npl) return fail(ctx, LVX_E_ARG, "surfel plane id out of range for the current plane table");
+    if (ctx->ho.surf_dev) { if (ctx->surf.n > 0 && (ctx->ho.id_min < 0 || ctx->ho.id_max >= npl)) return fail(ctx, LVX_E_ARG, "surfel plane id out of range for the current plane table"); }   // (device-origin rows: the extremes of their ids came with the row count)
+    else for (int i = 0; i < ctx->surf.n; ++i) if (ctx->surf.id0[i] < 0 || ctx->surf.id0[i] >= npl) return fail(ctx, LVX_E_ARG, "surfel plane id out of range for the current plane table");
     for (int i = 0; i < ctx->cs.n; ++i) {
       if (ctx->cs.id1[i] < 0 || ctx->cs.id1[i] >= npl) return fail(ctx, LVX_E_ARG, "cam-surfel plane id out of range for the current plane table");
       if (ctx->cs.id0[i] < 0 || ctx->cs.id0[i] >= L) return fail(ctx, LVX_E_ARG, "cam-surfel landmark id out of range for the current landmark table");
@@ -2438,7 +2439,14 @@ int ensure_layout(lvx_ctx* ctx) {
     if ((rc = upload_tmp(ctx, f.d_b3, a.data(), a.size() * 8))) return rc;
     if ((rc = upload_tmp(ctx, f.d_perm, perm.data(), perm.size() * 4))) return rc;
   }
-  {
+  if ((rc = handoff_planes_to_device(ctx))) return rc;   // d_planes, from the host table or the device one (the device surfel block below reads it)
+  if (ctx->ho.surf_dev && ctx->surf.n > 0) {   // device-origin rows (lvx_handoff.hip): sort, gather and plane copy as kernels; the sorted keys come back as a per-interval histogram
+    std::vector<int> sk;
+    if ((rc = handoff_layout_surfel(ctx, sk))) return rc;
+    if (ctx->sw.chunk_r) rc = upload_chunks(ctx, LVX_FAM_SURFEL, sk, pick_chunk(ctx, 8, 16, ctx->sw.chunk_r, 2, 2.2));
+    else rc = upload_chunks_rows(ctx, LVX_FAM_SURFEL, sk, 16, ctx->sw.chunk_rows > 0 ? ctx->sw.chunk_rows : 512);
+    if (rc) return rc;
+  } else {
     Family& f = ctx->surf;
     std::vector<int> key(f.n), perm(f.n);
     par_for((size_t)f.n, [&](size_t a, size_t b) { for (size_t i = a; i < b; ++i) key[i] = host_i0(ctx, f.t[i]); });
@@ -2588,7 +2596,6 @@ int ensure_layout(lvx_ctx* ctx) {
     if ((rc = upload_tmp(ctx, f.d_a3, pm.data(), pm.size() * 8))) return rc;
     if ((rc = upload_tmp(ctx, f.d_perm, perm.data(), perm.size() * 4))) return rc;
   }
-  if ((rc = upload_tmp(ctx, ctx->d_planes, ctx->planes.data(), ctx->planes.size() * 8))) return rc;
   if ((rc = upload_tmp(ctx, ctx->d_lm_uv, ctx->lm_uv.data(), ctx->lm_uv.size() * 8))) return rc;
   if ((rc = upload_tmp(ctx, ctx->d_lm_t0, ctx->lm_t0.data(), ctx->lm_t0.size() * 8))) return rc;
   // ---- hub knots (all surfel / cam-surfel residuals evaluate the trajectory at t_map: arrowhead) ----

@@ -240,6 +240,7 @@ static int run_stats(lvx_ctx* c, const double* state_d, lvx_error_stats* out) {
   const int cnt[LVX_NUM_FAM] = {c->imu.n, has_acc ? c->imu.n : 0, c->has_prior ? 1 : 0, c->surf.n, c->rep.n, c->cs.n};
   // plane -> surfel rows (input positions, input order): built on the first statistics call after the problem changed, never by lvx_set_surfel
   if (!c->st_plist_valid || c->st_plist_cfg != c->cfg_version) {
+    if ((rc = handoff_fetch_ids(c))) return rc;   // (a device-origin surfel family keeps its plane ids on the device until somebody asks)
     std::vector<int> tab((size_t)P + 1 + (size_t)std::max(c->surf.n, 1), 0);
     for (int i = 0; i < c->surf.n; ++i) tab[(size_t)c->surf.id0[i] + 1]++;
     for (int p = 0; p < P; ++p) tab[(size_t)p + 1] += tab[p];

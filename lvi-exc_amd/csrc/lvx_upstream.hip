@@ -2150,6 +2150,18 @@ static int surfel_point_arrays(lvx_ctx* c, size_t cap, bool alloc, SurfelOut* o)
   return LVX_OK;
 }
 
+// Stable sort of n (32-bit key, 32-bit value) pairs by the low `bits` bits of the key with rocPRIM — the instantiation the voxel grid's sort uses above VX_OWN_SORT_MAX
+// points — for the other translation units (lvx_handoff.hip: surfel rows by knot interval); tmp is grown to what rocPRIM asks for
+namespace lvx {
+int sort_pairs_u32(lvx_ctx* c, DevBuf& tmp, unsigned* k_in, unsigned* k_out, int* v_in, int* v_out, size_t n, int bits) {
+  size_t bytes = 0;
+  LVX_HIP(c, rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, n, 0u, (unsigned)bits, c->stream));
+  const int rc = dev_alloc(c, tmp, bytes); if (rc) return rc;
+  LVX_HIP(c, rocprim::radix_sort_pairs(tmp.p, bytes, k_in, k_out, v_in, v_out, n, 0u, (unsigned)bits, c->stream));
+  return LVX_OK;
+}
+}  // namespace lvx
+
 extern "C" {
 
 // Scan registration of a batch of sweeps: six launches (count, bucket, gather, curvature, classify, compact; grid.y = sweep).  No host round trip in between: the
@@ -2936,7 +2948,7 @@ int lvx_surfel_extract(lvx_ctx* c, double p_lambda, double dist_threshold, int m
 // ---- LIinitializer::DataAssociation, refinement branch (src/lvi_exc/test/lvi_initialize_surfel_orb.cpp:1180-1201), device-resident -------------------------------
 // new scans: the association forgets the planes and the capacities it learned on the scans before them
 static void da_reset(lvx_ctx* c, int n_scans, int H, int W) {
-  c->da_S = n_scans; c->da_H = H; c->da_W = W; c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_cap_nl = c->da_cap_P = c->da_cap_list = 0;
+  c->da_S = n_scans; c->da_H = H; c->da_W = W; c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_valid = false; c->da_cap_nl = c->da_cap_P = c->da_cap_list = 0;
 }
 int lvx_set_scans(lvx_ctx* c, int n_scans, int H, int W, const lvx_point_xyzit* raw) {
   if (!c || n_scans < 0 || H < 0 || W < 0 || W > SA_WMAX || ((size_t)n_scans * H * W > 0 && !raw)) return c ? fail(c, LVX_E_ARG, "bad lvx_set_scans arguments (W <= 4096)") : LVX_E_ARG;
@@ -3190,7 +3202,7 @@ int lvx_data_association(lvx_ctx* c, const double* state, double map_time, const
   if (npt > 2147483647ull) return fail(c, LVX_E_ARG, "too many scan points for one map cloud");
   int rc;
   ProfScope ps(c, LVX_KERNEL_UPSTREAM);
-  c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0;
+  c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_valid = false;
   if (n_planes) *n_planes = 0;
   if (n_points) *n_points = 0;
   // 1. ScanUndistortion::undistortScanInMap (scan_undistortion.h:59-74): the LiDAR pose at the map time, then EVERY point of EVERY scan moved with the pose at its own
@@ -3210,11 +3222,13 @@ int lvx_data_association(lvx_ctx* c, const double* state, double map_time, const
   if (S > 2 && c->da_cap_nl > 0 && c->da_cap_P > 0 && c->da_cap_list > 0 && !c->sw.da_sync) {
     c->da_spec_runs++;
     rc = da_speculative(c, o, S, H, W, npt, dv, n_planes, n_points);
-    if (rc <= 0) return rc;
+    if (rc <= 0) { c->da_valid = rc == LVX_OK; return rc; }
     c->da_spec_misses++;
-    c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0;
+    c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_valid = false;
   }
-  return da_sync_chain(c, o, (const float4*)c->d_da[4].p, npt, S, H, W, npt, dv, n_planes, n_points);
+  rc = da_sync_chain(c, o, (const float4*)c->d_da[4].p, npt, S, H, W, npt, dv, n_planes, n_points);
+  c->da_valid = rc == LVX_OK;
+  return rc;
 }
 // The FIRST DataAssociation of a calibration: the map comes from per-scan odometry poses (LOAM's: ReadPoseGT, lvi_initialize_surfel_orb.cpp:458-516), not from the spline —
 // the InitializationDone branch (:1175-1178): Mapping() (:1262-1300) = undistortScan() + LiDAROdometry::feedScan(t, scan, pose, update_map, using_loam = true) per scan
@@ -3264,7 +3278,7 @@ int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* sc
   if (npt > 2147483647ull) return fail(c, LVX_E_ARG, "too many scan points for one map cloud");
   int rc;
   ProfScope ps(c, LVX_KERNEL_UPSTREAM);
-  c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0;
+  c->da_planes.clear(); c->da_points = 0; c->da_planes_pending = 0; c->da_valid = false;
   if (n_planes) *n_planes = 0;
   if (n_points) *n_points = 0;
   // per-scan block on the device: [t S | q 4S | p 3S | pose 16S] doubles, then [valid S | present S | key S] ints
@@ -3302,6 +3316,7 @@ int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* sc
     LVX_HIP(c, hipGetLastError());
     LVX_HIP(c, hipStreamSynchronize(st));   // (the host vector above goes out of scope)
     lvx_surfel_map_release(c);
+    c->da_valid = true;   // (an empty map and no SurfelPoints)
     return LVX_OK;
   }
   LVX_HIP(c, hipMemcpyAsync(d_key, key.data(), key.size() * 4, hipMemcpyHostToDevice, st));
@@ -3311,7 +3326,9 @@ int lvx_data_association_poses(lvx_ctx* c, const double* state, const double* sc
   LVX_HIP(c, hipGetLastError());
   LVX_HIP(c, hipStreamSynchronize(st));   // (the host vectors above go out of scope)
   lvx_surfel_map_release(c);
-  return da_sync_chain(c, o, (const float4*)c->d_da_key.p, nmap, S, H, W, npt, nullptr, n_planes, n_points);
+  rc = da_sync_chain(c, o, (const float4*)c->d_da_key.p, nmap, S, H, W, npt, nullptr, n_planes, n_points);
+  c->da_valid = rc == LVX_OK;
+  return rc;
 }
 int lvx_data_association_stats(lvx_ctx* c, int64_t* one_stop_rounds, int64_t* repeated_rounds) {
   if (!c) return LVX_E_ARG;
@@ -3345,6 +3362,19 @@ int lvx_get_surfel_points(lvx_ctx* c, int max_points, double* pt3, double* pt_ma
   if (plane) LVX_HIP(c, hipMemcpyAsync(plane, d.plane, n * 4, hipMemcpyDeviceToHost, c->stream));
   LVX_HIP(c, hipStreamSynchronize(c->stream));
   return LVX_OK;
+}
+// The surfel family of the evaluator straight from the last association: lvx_get_surfel_map + lvx_set_planes(Pi), lvx_get_surfel_points, every step-th point with
+// t >= t_map, lvx_set_surfel — without the lists leaving the device (lvx_handoff.hip).  The family owns copies: a later association does not disturb it.
+int lvx_set_surfel_from_association(lvx_ctx* c, int step, double t_map, double huber, double weight, int32_t* n_used) { if (c) c->cfg_version++;
+  if (!c) return LVX_E_ARG;
+  if (n_used) *n_used = 0;
+  if (!c->da_valid) return fail(c, LVX_E_STATE, "lvx_set_surfel_from_association: no data association on this context (lvx_data_association / lvx_data_association_poses)");
+  LVX_HIP(c, hipSetDevice(c->device));
+  const int P = c->da_planes_pending > 0 ? c->da_planes_pending : (int)c->da_planes.size();
+  int rc = handoff_planes_from_records(c, P, c->d_da[5].p); if (rc) return rc;
+  SurfelOut d{};
+  if (c->da_points > 0) surfel_point_arrays(c, (size_t)c->da_S * c->da_H * c->da_W, false, &d);   // the lists are strided by the capacity (lvx_data_association)
+  return handoff_set_surfel(c, P > 0 ? c->da_points : 0, step, true, d.pt, d.t, d.plane, t_map, huber, weight, n_used);
 }
 int lvx_get_scans_in_map(lvx_ctx* c, float* xyzi4) {
   if (!c || !xyzi4) return LVX_E_ARG;

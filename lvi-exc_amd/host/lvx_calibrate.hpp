@@ -64,6 +64,7 @@ struct CalibrateOptions {
   double w_lidar_pos = 1;                // global_opt_pos_weight (calibration.hpp:68): the LiDAR odometry position blocks of RunLidarPoses
   bool opt_time_offset = false;
   bool keep_history = false, keep_clouds = false;   // AssociationRecord per DataAssociation round (tests, diagnostics)
+  bool device_handoff = false;           // trajInitFromSurfel / trajInitFromLVIdata take their surfel blocks with lvx_set_surfel_from_association: the SurfelPoint list stays on the device (fetched only for keep_history), the planes are fetched only for the camera-surfel stage
   bool error_statistics = false;   // printErrorStatistics("Before optimization") / ("After optimization") around every stage's solve (trajectory_manager_lvi.cpp:339-342): StageReport::stats_before / stats_after
   int verbose = 1;
 };
@@ -488,10 +489,13 @@ class Calibrator {
     fetch_association(state, np, n);
   }
   void fetch_association(const std::vector<double>& state, int32_t np, int32_t n) {
-    planes_.assign((size_t)np, lvx_surfel_plane{});
-    if (np > 0) check(lvx_get_surfel_map(ctx_, np, planes_.data()));
-    sp_pt_.assign((size_t)n * 3, 0.0); sp_map_.assign((size_t)n * 3, 0.0); sp_t_.assign((size_t)n, 0.0); sp_plane_.assign((size_t)n, 0);
-    if (n > 0) check(lvx_get_surfel_points(ctx_, n, sp_pt_.data(), sp_map_.data(), sp_t_.data(), sp_plane_.data()));
+    n_planes_ = np;
+    const bool want_planes = !opt_.device_handoff || opt_.keep_history || opt_.camera_surfel_stage, want_points = !opt_.device_handoff || opt_.keep_history;
+    planes_.assign(want_planes ? (size_t)np : 0, lvx_surfel_plane{});
+    if (want_planes && np > 0) check(lvx_get_surfel_map(ctx_, np, planes_.data()));
+    const int32_t nf = want_points ? n : 0;
+    sp_pt_.assign((size_t)nf * 3, 0.0); sp_map_.assign((size_t)nf * 3, 0.0); sp_t_.assign((size_t)nf, 0.0); sp_plane_.assign((size_t)nf, 0);
+    if (nf > 0) check(lvx_get_surfel_points(ctx_, nf, sp_pt_.data(), sp_map_.data(), sp_t_.data(), sp_plane_.data()));
     if (opt_.keep_history) {
       AssociationRecord r; r.state = state; r.planes = planes_; r.pt = sp_pt_; r.pt_map = sp_map_; r.t = sp_t_; r.plane = sp_plane_;
       if (opt_.keep_clouds) { r.scans_in_map.assign(n_scans_ * (size_t)in_.H * in_.W * 4, 0.f); check(lvx_get_scans_in_map(ctx_, r.scans_in_map.data())); }
@@ -500,6 +504,12 @@ class Calibrator {
     if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] association: %d surfels, %d surfel points (every %d-th is used)\n", np, n, opt_.downsample_step);
   }
   void set_surfels() {   // addSurfMeasurement over get_surfel_points() after averageTimeDownSmaple(step) (surfel_association.cpp:240-244)
+    if (opt_.device_handoff) {   // the same selection on the device, from the lists of the last association
+      int32_t used = 0;
+      check(lvx_set_surfel_from_association(ctx_, opt_.downsample_step, in_.map_time, 5.0, opt_.w_surfel, &used));
+      n_surfel_used_ = used;
+      return;
+    }
     std::vector<double> Pi(planes_.size() * 3);
     for (size_t k = 0; k < planes_.size(); ++k) for (int a = 0; a < 3; ++a) Pi[3 * k + a] = planes_[k].Pi[a];
     check(lvx_set_planes(ctx_, (int)planes_.size(), Pi.data()));
@@ -518,7 +528,7 @@ class Calibrator {
     check(lvx_set_locks(ctx_, StageLocks(Stage::TrajFromSurfel, opt_.opt_time_offset)));
     StageReport r{name, solve(state, 30)};
     attach_history(&r);
-    r.n_planes = (int)planes_.size(); r.n_surfel_points = n_surfel_used_;
+    r.n_planes = n_planes_; r.n_surfel_points = n_surfel_used_;
     return r;
   }
   StageReport SolveVisual(std::vector<double>* state) {   // trajInitFromVisualFrames
@@ -555,7 +565,7 @@ class Calibrator {
     }
     r.lm = solve(state, 80);
     attach_history(&r);
-    r.n_planes = (int)planes_.size(); r.n_surfel_points = n_surfel_used_;
+    r.n_planes = n_planes_; r.n_surfel_points = n_surfel_used_;
     return r;
   }
   // LiDAR pose in the camera frame from the two sensor blocks (q_XtoI, p_XinI): q_LtoC = q_CtoI^-1 q_LtoI, t_LinC = q_CtoI^-1 (p_LinI - p_CinI)
@@ -620,7 +630,7 @@ class Calibrator {
   std::vector<int32_t> key_scans_;
   LidarOdometry odom_;
   std::vector<double> sp_pt_, sp_map_, sp_t_; std::vector<int32_t> sp_plane_;
-  int n_surfel_used_ = 0;
+  int n_surfel_used_ = 0, n_planes_ = 0;
   lvx_error_stats stats_before_{}, stats_after_{};
 };
 

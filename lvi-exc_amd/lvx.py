@@ -182,6 +182,15 @@ class Context:
         pt, t, plane_id = _d(pt), _d(t), _i(plane_id)
         self._ck(self._l.lvx_set_surfel(self._h, C.c_int(len(t)), _p(pt), _p(t), _p(plane_id), C.c_double(t_map), C.c_double(huber), C.c_double(w)))
 
+    def set_planes_d(self, n_planes, pi3_d_ptr):
+        """set_planes from device memory (lvx_set_planes_d): pi3_d_ptr is the address of [n_planes][3] doubles on this context's GPU."""
+        self._ck(self._l.lvx_set_planes_d(self._h, C.c_int(n_planes), C.c_void_p(pi3_d_ptr)))
+        self._n_planes = n_planes
+
+    def set_surfel_d(self, n, pt_d_ptr, t_d_ptr, plane_id_d_ptr, t_map, huber, w):
+        """set_surfel from device memory (lvx_set_surfel_d): addresses of [n][3] doubles, [n] doubles, [n] int32; the layout of the family runs on the device."""
+        self._ck(self._l.lvx_set_surfel_d(self._h, C.c_int(n), C.c_void_p(pt_d_ptr), C.c_void_p(t_d_ptr), C.c_void_p(plane_id_d_ptr), C.c_double(t_map), C.c_double(huber), C.c_double(w)))
+
     def set_landmarks(self, uv_ref, t0_ref):
         uv_ref, t0_ref = _d(uv_ref), _d(t0_ref)
         self._ck(self._l.lvx_set_landmarks(self._h, C.c_int(len(t0_ref)), _p(uv_ref), _p(t0_ref)))
@@ -902,6 +911,14 @@ def get_surfel_points(ctx, n_points):
     pt, pm, t, pl = np.zeros((max(n_points, 1), 3)), np.zeros((max(n_points, 1), 3)), np.zeros(max(n_points, 1)), np.zeros(max(n_points, 1), np.int32)
     ctx._ck(ctx._l.lvx_get_surfel_points(ctx._h, C.c_int(n_points), _p(pt), _p(pm), _p(t), _p(pl)))
     return dict(pt=pt[:n_points], pt_map=pm[:n_points], t=t[:n_points], plane=pl[:n_points])
+
+
+def set_surfel_from_association(ctx, step, t_map, huber, w):
+    """The evaluator's planes and surfel blocks from the last association, on the device (lvx_set_surfel_from_association): every step-th SurfelPoint with
+    t >= t_map, as oracle.pipeline.select_surfels picks them; returns how many were kept."""
+    n = C.c_int32(0)
+    ctx._ck(ctx._l.lvx_set_surfel_from_association(ctx._h, C.c_int(step), C.c_double(t_map), C.c_double(huber), C.c_double(w), C.byref(n)))
+    return n.value
 
 
 def get_scans_in_map(ctx, n_scans, H, W):
