@@ -320,6 +320,31 @@ int lvx_lm_get_history(lvx_ctx* ctx, int max_n, double* cost, double* radius, in
  * (S H S + clamp(diag(S H S), 1e-6, 1e32) / radius) y = -S g, delta = S y (S = Jacobi scaling or identity); delta[n_tangent] on the host */
 int lvx_solve_step(lvx_ctx* ctx, double radius, int jacobi_scaling, double* delta, double* model_cost_change);
 
+/* Uncertainty of the calibration scalars c = tangent - 6 N (0-1 gravity, 2-4 accelerometer bias, 5-7 gyroscope bias, 8-10 / 11-13 / 14 LiDAR rotation, translation,
+ * time offset, 15-17 / 18-20 / 21 the camera's) at the state of the last LVX_EVAL_NORMAL_EQ evaluation, from the factored LM system: landmarks, band and hub knots are
+ * eliminated on the device as in lvx_solve_step and the 22 x 22 remainder is decomposed in one workgroup (k_calib_cov).  Same contract as lvx_solve_step: the
+ * evaluation's error word is read first, LVX_E_STATE without such an evaluation; the stored normal equations and the LM state are left as they were.  One host stop.
+ *   cov = [ s (s H_FF s + diag(clamp(diag(s H_FF s), 1e-6, 1e32)) / radius)^-1 s ]  restricted to the calibration scalars,
+ * F = the free tangent scalars, s = the Jacobi scale 1 / (1 + sqrt(diag H)) of THIS evaluation (or 1).  It is the covariance of the DAMPED system at the stated radius:
+ * with a free trajectory the scaled H of a short sequence has eigenvalues far below rounding (and four gauge directions that are null), so the LM diagonal acts as a
+ * prior the result depends on; where the data decide (trajectory locked) the result is independent of the radius to 1e-5 at 1e8.  info_eig shows which is the case: an
+ * eigenvalue at 1e-6 / radius is a direction no residual row touches.
+ * A context that takes part in a joint solve (a reduction callback or an RCCL communicator is installed) returns LVX_E_STATE: the covariance of the shared extrinsics
+ * over all ranks' sequences is not computed here.  LVX_E_NOTPD: a pivot or an eigenvalue was not positive, or max_sweeps Jacobi sweeps did not converge (the
+ * off-diagonal measure is in lvx_last_error); `out` is not written then. */
+typedef struct lvx_calib_cov_options { double radius; int32_t jacobi_scaling; int32_t max_sweeps; } lvx_calib_cov_options;   /* 1e8, 1, 30 */
+typedef struct lvx_calib_cov {
+  int32_t n_free; int32_t free_index[22];     /* calibration scalars c that are free under the lock mask, ascending */
+  double cov[22 * 22];                        /* row-major over c; rows / columns of constant scalars are 0 */
+  double sigma[22];                           /* sqrt(cov[c][c]) in tangent units: a rotation entry is a HALF-angle (EigenQuaternionParameterization), std in rad = 2 sigma */
+  double info_eig[22], info_vec[22 * 22];     /* eigenvalues (ascending, first n_free) and unit eigenvectors (row-major, column k over free_index) of the Jacobi-SCALED
+                                                 marginal information: dimensionless, in (0, ~1] */
+  double scale[22];                           /* the Jacobi scale of each calibration scalar (1 when jacobi_scaling = 0) */
+  double radius; int32_t sweeps; int32_t n_hub_eliminated;   /* Jacobi sweeps used; border columns (6 per hub knot) eliminated in front of the 22 */
+} lvx_calib_cov;
+int lvx_calib_cov_default_options(lvx_calib_cov_options* opt);
+int lvx_calibration_covariance(lvx_ctx* ctx, const lvx_calib_cov_options* opt, lvx_calib_cov* out);
+
 /* x (+) delta with ceres::EigenQuaternionParameterization::Plus on quaternion blocks */
 int lvx_plus(lvx_ctx* ctx, const double* state, const double* delta, double* state_out);
 

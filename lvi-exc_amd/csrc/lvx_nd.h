@@ -1135,7 +1135,11 @@ int nd_dense_start(lvx_ctx* c, const double* scale, const double* lmd, double in
   hipLaunchKernelGGL(k_nd_cbuild, dim3((unsigned)P->nden, (unsigned)((bd + 3) / 4)), dim3(256), 0, P->side, ad, (double*)P->Dc.p, (double*)P->Rc.p, bd, c->bw, 0);   // a wavefront per column
   hipLaunchKernelGGL(k_nd_cbuild, dim3((unsigned)P->nden, (unsigned)((P->nc + 3) / 4)), dim3(256), 0, st, ad, (double*)P->Dc.p, (double*)P->Rc.p, bd, c->bw, 1);
   LVX_HIP(c, hipEventRecord(P->ev_rc, st));
-  c->stream = P->side;
+  struct StreamSwap {   // the batched helpers queue on c->stream: the side stream for their duration, the caller's again on EVERY exit (LVX_HIP returns from the middle)
+    lvx_ctx* c; hipStream_t keep;
+    StreamSwap(lvx_ctx* ctx, hipStream_t to) : c(ctx), keep(ctx->stream) { c->stream = to; }
+    ~StreamSwap() { c->stream = keep; }
+  } swap(c, P->side);
   rocblas_handle h = nullptr;
   const long long sD = (long long)bd * bd, sLI = (long long)(bd / 16) * 256;
   int rc = potrf_batched(c, h, (double*)P->Dc.p, bd, sD, ad.info, P->nden, (double*)P->LIc.p, sLI);
@@ -1149,7 +1153,6 @@ int nd_dense_start(lvx_ctx* c, const double* scale, const double* lmd, double in
     else if (zt == 4) hipLaunchKernelGGL(k_nd_cgram<4>, dim3((unsigned)P->nden), dim3(64 * 8), 0, P->side, ad, (const double*)P->Rc.p, bd);
     else hipLaunchKernelGGL(k_nd_cgram<5>, dim3((unsigned)P->nden), dim3(64 * 9), 0, P->side, ad, (const double*)P->Rc.p, bd);
   }
-  c->stream = st;
   if (rc) return rc;
   LVX_HIP(c, hipEventRecord(P->ev_join, P->side));
   return LVX_OK;

@@ -24,6 +24,7 @@
 #include <rccl/rccl.h>   // types only: the entry points are resolved with dlsym (rccl_api)
 
 #include "lvx_ctx.h"
+#include "lvx_symeig.h"
 
 namespace lvx {
 // dense border of a single sequence on 16 x 16 tiles (lvx_nd.h, in lvx_bcr.hip's translation unit)
@@ -707,6 +708,69 @@ __global__ __launch_bounds__(256) void k_pre_solve(const double* gb, double* gbs
   if (blockIdx.x == 0 && threadIdx.x < 64) sums[threadIdx.x] = 0.0;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Marginal covariance of the calibration scalars (lvx_calibration_covariance).  One workgroup, everything in LDS (n <= 128 as k_dense_partial).
+// S: the reduced border system (lower triangle), hub knots first, the 22 calibration slots last.  The nh hub columns are eliminated right-looking (L D L^T: no
+// right-hand side, nothing is kept of the factor), which leaves the scaled marginal information T of the calibration slots in the trailing block.  A locked slot is an
+// inert lmd / radius diagonal: only the free slots are compacted into M.  M = V diag(w) V^T by cyclic Jacobi (lvx_symeig.h; the pairs of a round over the lanes), then
+// cov = D V diag(1 / w) V^T D with D = the Jacobi scale.
+// out (LVX_CCOV_N doubles): cov [22][22] | sigma [22] | w ascending [22] | V [22][22] (column k <-> w[k]) | scale [22] | off, sweeps, status, band pivot code,
+// first hub pivot (1-based, 0 = none), its value.  status: 0 ok, 1 the sweep cap was reached, 2 an eigenvalue is not positive.
+// ---------------------------------------------------------------------------------------------------------
+#define LVX_NCAL 22
+#define LVX_CCOV_N (2 * LVX_NCAL * LVX_NCAL + 3 * LVX_NCAL + 6)
+#define CCOV_NT 256
+struct SymeigBlockSync { __device__ void operator()() const { __syncthreads(); } };
+__global__ __launch_bounds__(CCOV_NT) void k_calib_cov(const double* __restrict__ S, int n, int nh, const double* __restrict__ scale_c, uint32_t free_mask, int max_sweeps, const int* info, double* out) {
+  extern __shared__ double ds[];           // T [n][n + 1]
+  __shared__ double M[LVX_NCAL * (LVX_NCAL + 1)], V[LVX_NCAL * (LVX_NCAL + 1)], cs[LVX_SYMEIG_CS], piv[2];
+  __shared__ int order[LVX_NCAL], fr[LVX_NCAL], slot[LVX_NCAL];
+  const int tid = threadIdx.x, ld = n + 1, ldm = LVX_NCAL + 1;
+  double* T = ds;
+  for (int r = tid >> 6; r < n; r += CCOV_NT / 64) for (int cc = tid & 63; cc <= r; cc += 64) T[r * ld + cc] = S[(size_t)r * n + cc];
+  if (tid == 0) {
+    piv[0] = 0.0; piv[1] = 0.0;
+    int nf0 = 0;
+    for (int c = 0; c < LVX_NCAL; ++c) { slot[c] = -1; if (free_mask >> c & 1u) { slot[c] = nf0; fr[nf0++] = c; } }
+  }
+  __syncthreads();
+  int nf = 0;
+  for (int c = 0; c < LVX_NCAL; ++c) nf += (int)(free_mask >> c & 1u);
+  for (int k = 0; k < nh; ++k) {
+    if (tid == 0) { const double d = T[k * ld + k]; if (!(d > 0.0)) { if (piv[0] == 0.0) { piv[0] = (double)(k + 1); piv[1] = d; } T[k * ld + k] = 1.0; } }
+    __syncthreads();
+    const double inv = 1.0 / T[k * ld + k];
+    for (int c0 = k + 1; c0 < n; c0 += 64) {   // lane = column, wavefront = row (as k_dense_partial); column k is read, never written, in this step
+      const int cc = c0 + (tid & 63);
+      const double lc = cc < n ? T[cc * ld + k] * inv : 0.0;
+      for (int rr = k + 1 + (tid >> 6); rr < n; rr += CCOV_NT / 64) if (cc < n && rr >= cc) T[rr * ld + cc] -= T[rr * ld + k] * lc;
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < nf * nf; e += CCOV_NT) {
+    const int i = e / nf, j = e % nf, a = nh + fr[i > j ? i : j], b = nh + fr[i > j ? j : i];
+    M[i * ldm + j] = T[a * ld + b];
+  }
+  __syncthreads();
+  int sweeps = 0; double off = 0.0;
+  const int capped = symeig_jacobi(M, ldm, nf, V, ldm, cs, max_sweeps, tid, CCOV_NT, SymeigBlockSync(), &sweeps, &off);
+  if (tid == 0) symeig_order(M, ldm + 1, nf, order);
+  __syncthreads();
+  int status = capped ? 1 : 0;
+  for (int k = 0; k < nf; ++k) if (!status && !(M[k * (ldm + 1)] > 0.0)) status = 2;
+  double* o_cov = out, *o_sig = out + LVX_NCAL * LVX_NCAL, *o_w = o_sig + LVX_NCAL, *o_v = o_w + LVX_NCAL, *o_sc = o_v + LVX_NCAL * LVX_NCAL, *o_tail = o_sc + LVX_NCAL;
+  for (int e = tid; e < LVX_NCAL * LVX_NCAL; e += CCOV_NT) {
+    const int ci = e / LVX_NCAL, cj = e % LVX_NCAL, i = slot[ci], j = slot[cj];
+    double s = 0.0;
+    if (i >= 0 && j >= 0 && status == 0) { for (int k = 0; k < nf; ++k) { const int q = order[k]; s += V[i * ldm + q] * V[j * ldm + q] / M[q * (ldm + 1)]; } s *= scale_c[ci] * scale_c[cj]; }
+    o_cov[e] = s;
+    if (ci == cj) o_sig[ci] = sqrt(s);
+    o_v[e] = (ci < nf && cj < nf) ? V[ci * ldm + order[cj]] : 0.0;
+  }
+  if (tid < LVX_NCAL) { o_w[tid] = tid < nf ? M[order[tid] * (ldm + 1)] : 0.0; o_sc[tid] = scale_c[tid]; }
+  if (tid == 0) { o_tail[0] = off; o_tail[1] = (double)sweeps; o_tail[2] = (double)status; o_tail[3] = (double)info[0]; o_tail[4] = piv[0]; o_tail[5] = piv[1]; }
+}
+
 }  // namespace lvx
 
 using namespace lvx;
@@ -847,9 +911,10 @@ struct StageTimer {   // LVX_SOLVER_TIMING=1: host wall time per stage (enqueue 
   void lap(const char* what) { if (!on) return; const auto n = std::chrono::steady_clock::now(); fprintf(stderr, "[lvx solver] %-28s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(n - t).count()); t = n; }
 };
 
-static int solve_local(lvx_ctx* c, SolveWork& w, double radius, bool force_seq, bool* bcr_used, bool defer_check = false) {   // defer_check: the caller reads the pivot codes with the step's sums
+// First half of solve_local, and all that lvx_calibration_covariance needs of it: landmarks and band are eliminated (on whichever route the plan and force_seq select) and
+// w.S (lower triangle) / w.rhs hold the reduced border system, unfactored.  Everything is queued; the band's pivot code is in w.info[0].
+static int reduce_to_border(lvx_ctx* c, SolveWork& w, double radius, bool force_seq, bool* bcr_used, StageTimer& tm) {
   hipStream_t st = c->stream;
-  StageTimer tm(c);
   const int nb = c->nb, bw = c->bw, nbd = c->nbd;
   const double ir = 1.0 / radius;
   bool sums_cleared = false;   // (k_pre_solve clears them with its copies; otherwise the fill below)
@@ -916,6 +981,14 @@ static int solve_local(lvx_ctx* c, SolveWork& w, double radius, bool force_seq, 
     hipLaunchKernelGGL(k_schur, dim3(nbd), dim3(256), 0, st, (const double*)Zf, w.Cs, w.gcs, (const double*)w.scale,
                        nb > 0 ? nb : 0, nbd, c->nbd_ext, ldz, (const double*)w.lmd, ir, w.S, w.rhs);
   }
+  return LVX_OK;
+}
+
+static int solve_local(lvx_ctx* c, SolveWork& w, double radius, bool force_seq, bool* bcr_used, bool defer_check = false) {   // defer_check: the caller reads the pivot codes with the step's sums
+  hipStream_t st = c->stream;
+  StageTimer tm(c);
+  const int nbd = c->nbd;
+  { const int rcb = reduce_to_border(c, w, radius, force_seq, bcr_used, tm); if (rcb) return rcb; }
   if (dense_tiles_ok(c, nbd)) { const int rcd = dense_tiles_factor(c, w.S, w.rhs, nbd, w.info); if (rcd) return rcd; }   // single sequence: one wavefront on 16 x 16 tiles (10 us against 50)
   else {
   const size_t lds_dense = ((size_t)nbd * (nbd + 1) + nbd) * 8;
@@ -1298,6 +1371,66 @@ int lvx_solve_step_shared(lvx_ctx* c, double radius, int jacobi_scaling, lvx_all
 }
 int lvx_solve_step(lvx_ctx* c, double radius, int jacobi_scaling, double* delta, double* model_cost_change) {
   return lvx_solve_step_shared(c, radius, jacobi_scaling, nullptr, nullptr, delta, model_cost_change);
+}
+
+int lvx_calib_cov_default_options(lvx_calib_cov_options* o) {
+  if (!o) return LVX_E_ARG;
+  o->radius = 1e8; o->jacobi_scaling = 1; o->max_sweeps = 30;
+  return LVX_OK;
+}
+// lvx_solve_step's front half (diagonal, scale, damping, elimination down to the border system — from copies, so the stored normal equations stay), then k_calib_cov
+// in place of the border factorisation.  The record and every pivot code come back in ONE copy: the only host stop.
+int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx_calib_cov* out) {
+  if (!c || !opt || !out || !(opt->radius > 0) || opt->max_sweeps < 1) return LVX_E_ARG;
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ)) return fail(c, LVX_E_STATE, "lvx_calibration_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_calibration_covariance: the context takes part in a joint solve (the covariance of the shared extrinsics over the ranks is not computed)");
+  LVX_HIP(c, hipSetDevice(c->device));
+  int rc = check_last_eval(c); if (rc) return rc;
+  SolveWork w;
+  if ((rc = solver_alloc(c, w))) return rc;
+  const int nb = c->nb, nbd = c->nbd, nh = nbd - LVX_NCAL;
+  if (nh < 0 || nbd > 128) return fail(c, LVX_E_ARG, "lvx_calibration_covariance: border of " + std::to_string(nbd) + " scalars (22 .. 128 fit the one-workgroup kernel)");
+  if ((rc = dev_alloc(c, c->d_ccov, (size_t)LVX_CCOV_N * 8))) return rc;
+  hipStream_t st = c->stream;
+  EvalLocal e; bool gconv = false;
+  if ((rc = local_after_eval(c, w, &e, false))) return rc;   // the diagonal of THIS evaluation (queued; nothing of *e is used)
+  if ((rc = apply_diag(c, w, true, opt->jacobi_scaling, 1e-6, 1e32, e, nullptr, 0.0, &gconv))) return rc;
+  uint32_t free_mask = 0;
+  for (int k = 0; k < LVX_NCAL; ++k) if (c->ord[6 * (size_t)c->N + k] != LVX_DEAD) free_mask |= 1u << k;
+  std::vector<double> h(LVX_CCOV_N);
+  StageTimer tm(c);
+  const size_t lds = (size_t)nbd * (nbd + 1) * 8;
+  LVX_HIP(c, hipFuncSetAttribute((const void*)k_calib_cov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  auto run = [&](bool force_seq, bool* bcr_used) -> int {
+    w.lm_done = false;
+    const int r = reduce_to_border(c, w, opt->radius, force_seq, bcr_used, tm); if (r) return r;
+    hipLaunchKernelGGL(k_calib_cov, dim3(1), dim3(CCOV_NT), lds, st, (const double*)w.S, nbd, nh, (const double*)(w.scale + (nb + nh)), free_mask, (int)opt->max_sweeps, (const int*)w.info, (double*)c->d_ccov.p);
+    LVX_HIP(c, hipGetLastError());
+    LVX_HIP(c, hipMemcpyAsync(h.data(), c->d_ccov.p, (size_t)LVX_CCOV_N * 8, hipMemcpyDeviceToHost, st));
+    LVX_HIP(c, hipStreamSynchronize(st));
+    return LVX_OK;
+  };
+  bool bcr_used = false;
+  if ((rc = run(false, &bcr_used))) return rc;
+  const double* tail = h.data() + LVX_CCOV_N - 6;
+  // a pivot lost in the reduction's elimination order: once more with the sequential band Cholesky, as lvx_solve_step does (switch TEST_BAD_PIVOT: the tests' way in)
+  if (bcr_used && (tail[3] != 0.0 || tail[4] != 0.0 || tail[2] == 2.0 || c->sw.test_bad_pivot)) {
+    ++c->solver_fallbacks;
+    if ((rc = run(true, &bcr_used))) return rc;
+  }
+  if (tail[3] != 0.0 || tail[4] != 0.0) return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string((int)tail[3]) + ", first hub pivot " + std::to_string((int)tail[4]) + " value " + std::to_string(tail[5]) + ")");
+  if (tail[2] == 2.0) return fail(c, LVX_E_NOTPD, "marginal information of the calibration scalars has a non-positive eigenvalue " + std::to_string(h[LVX_NCAL * LVX_NCAL + LVX_NCAL]));
+  if (tail[2] != 0.0) { char buf[160]; snprintf(buf, sizeof buf, "Jacobi eigen-decomposition not converged after %d sweeps: max |t_pq| / sqrt(t_pp t_qq) = %.3e", (int)tail[1], tail[0]); return fail(c, LVX_E_NOTPD, buf); }
+  std::memset(out, 0, sizeof *out);
+  for (int k = 0; k < LVX_NCAL; ++k) if (free_mask >> k & 1u) out->free_index[out->n_free++] = k;
+  const double* p = h.data();
+  std::memcpy(out->cov, p, sizeof out->cov); p += LVX_NCAL * LVX_NCAL;
+  std::memcpy(out->sigma, p, sizeof out->sigma); p += LVX_NCAL;
+  std::memcpy(out->info_eig, p, sizeof out->info_eig); p += LVX_NCAL;
+  std::memcpy(out->info_vec, p, sizeof out->info_vec); p += LVX_NCAL * LVX_NCAL;
+  std::memcpy(out->scale, p, sizeof out->scale);
+  out->radius = opt->radius; out->sweeps = (int32_t)tail[1]; out->n_hub_eliminated = nh;
+  return LVX_OK;
 }
 
 // Collectives of the joint loop: one after the first evaluation, then exactly TWO per iteration —

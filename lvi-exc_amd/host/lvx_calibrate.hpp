@@ -66,6 +66,8 @@ struct CalibrateOptions {
   bool keep_history = false, keep_clouds = false;   // AssociationRecord per DataAssociation round (tests, diagnostics)
   bool device_handoff = false;           // trajInitFromSurfel / trajInitFromLVIdata take their surfel blocks with lvx_set_surfel_from_association: the SurfelPoint list stays on the device (fetched only for keep_history), the planes are fetched only for the camera-surfel stage
   bool error_statistics = false;   // printErrorStatistics("Before optimization") / ("After optimization") around every stage's solve (trajectory_manager_lvi.cpp:339-342): StageReport::stats_before / stats_after
+  bool covariance = false;         // lvx_calibration_covariance at every stage's final state (one more LVX_EVAL_NORMAL_EQ evaluation per stage): StageReport::covariance
+  double covariance_radius = 1e8;  // the radius of the damped system the covariance belongs to (what it means)
   int verbose = 1;
 };
 struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_surfel_points = 0, n_cam_surfel = 0;
@@ -73,6 +75,7 @@ struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_su
                      std::vector<double> state_in;   // the state the stage's solve started from (CalibrateOptions::keep_history)
                      bool has_stats = false; lvx_error_stats stats_before{}, stats_after{};   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
                      int init_prefix = -1; lvx_rotinit_result init{};   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
+                     bool has_covariance = false; lvx_calib_cov covariance{};   // CalibrateOptions::covariance: the record at the state the stage's solve ended at (false: the option is off, or the call reported LVX_E_NOTPD)
                      int n_lidar_poses = 0; lvx_family_stats lidar_pos_before{}, lidar_pos_after{}; };   // trajInitFromLidarPose: blocks attached; with error_statistics, lvx_lidar_pose_statistics around the solve
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
@@ -80,6 +83,40 @@ struct AssociationRecord { std::vector<double> state; std::vector<lvx_surfel_pla
 
 // LIinitializer::ReprojectPointCloudToImage's image choice (lvi_initialize_surfel_orb.cpp:1319-1327): per scan the FIRST image with img_t > scan_t and |img_t - scan_t| < 0.05,
 // or -1
+// The calibration scalars c = tangent - 6 N of lvx_calib_cov, by name
+inline const char* CalibScalarName(int c) {
+  static const char* const names[22] = {"gravity.x", "gravity.y", "acc_bias.x", "acc_bias.y", "acc_bias.z", "gyro_bias.x", "gyro_bias.y", "gyro_bias.z",
+                                        "lidar_rot.x", "lidar_rot.y", "lidar_rot.z", "lidar_pos.x", "lidar_pos.y", "lidar_pos.z", "lidar_tau",
+                                        "cam_rot.x", "cam_rot.y", "cam_rot.z", "cam_pos.x", "cam_pos.y", "cam_pos.z", "cam_tau"};
+  return c >= 0 && c < 22 ? names[c] : "?";
+}
+// What a user reads off a lvx_calib_cov, one line per sensor whose extrinsics are (partly) free and one for the spectrum:
+//   [LiDAR]  rotation std (deg): a b c; translation std (m): x y z            (rotation: 2 sigma 180 / pi — the tangent of a quaternion block is a half-angle; a constant scalar prints 0)
+//   [Camera] ...
+//   [Spectrum] smallest scaled eigenvalue: v (radius r); dominant scalar: name (c = k)
+// The covariance is that of the damped system at the record's radius; an eigenvalue at 1e-6 / radius is a direction no residual row touches.
+inline std::string FormatCalibrationUncertainty(const lvx_calib_cov& r) {
+  std::string out;
+  char buf[256];
+  const double deg = 2.0 * 180.0 / 3.14159265358979323846;
+  const struct { const char* tag; int c0; } sensors[2] = {{"[LiDAR] ", 8}, {"[Camera]", 15}};
+  for (const auto& sn : sensors) {
+    bool any = false;
+    for (int k = 0; k < r.n_free; ++k) any = any || (r.free_index[k] >= sn.c0 && r.free_index[k] < sn.c0 + 6);
+    if (!any) continue;
+    const double* s = r.sigma + sn.c0;
+    std::snprintf(buf, sizeof buf, "%s rotation std (deg): %.6e %.6e %.6e; translation std (m): %.6e %.6e %.6e\n", sn.tag, deg * s[0], deg * s[1], deg * s[2], s[3], s[4], s[5]);
+    out += buf;
+  }
+  if (r.n_free > 0) {
+    int dom = 0;
+    for (int i = 1; i < r.n_free; ++i) if (std::fabs(r.info_vec[i * 22]) > std::fabs(r.info_vec[dom * 22])) dom = i;
+    std::snprintf(buf, sizeof buf, "[Spectrum] smallest scaled eigenvalue: %.6e (radius %.6e); dominant scalar: %s (c = %d)\n", r.info_eig[0], r.radius, CalibScalarName(r.free_index[dom]), (int)r.free_index[dom]);
+    out += buf;
+  }
+  return out;
+}
+
 inline std::vector<int32_t> MatchScanImages(const std::vector<double>& scan_t, const std::vector<double>& image_t) {
   std::vector<int32_t> idx(scan_t.size(), -1);
   for (size_t j = 0; j < scan_t.size(); ++j)
@@ -589,6 +626,15 @@ class Calibrator {
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_before_));
     check(lvx_lm_solve(ctx_, state->data(), &o, &s));
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_after_));
+    has_cov_ = false;
+    if (opt_.covariance) {   // the normal equations at the final state (the loop's last ones may belong to a rejected candidate), then the call
+      double cost = 0.0;
+      check(lvx_evaluate(ctx_, state->data(), LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cost, nullptr));
+      lvx_calib_cov_options co; lvx_calib_cov_default_options(&co); co.radius = opt_.covariance_radius;
+      const int rc = lvx_calibration_covariance(ctx_, &co, &cov_);
+      if (rc == LVX_E_NOTPD) { if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] covariance: %s\n", lvx_last_error(ctx_)); }   // no record for this stage; the calibration goes on
+      else { check(rc); has_cov_ = true; if (opt_.verbose) std::fputs(FormatCalibrationUncertainty(cov_).c_str(), stderr); }
+    }
     const int cap = 4 * max_it + 8;
     hist_cost_.assign((size_t)cap, 0.0); hist_radius_.assign((size_t)cap, 0.0); hist_acc_.assign((size_t)cap, 0);
     const int k = lvx_lm_get_history(ctx_, cap, hist_cost_.data(), hist_radius_.data(), hist_acc_.data());
@@ -599,6 +645,7 @@ class Calibrator {
   void attach_history(StageReport* r) const {
     r->cost_history = hist_cost_; r->radius_history = hist_radius_; r->accepted = hist_acc_; r->state_in = stage_state_in_;
     r->has_stats = opt_.error_statistics; r->stats_before = stats_before_; r->stats_after = stats_after_;
+    r->has_covariance = has_cov_; r->covariance = cov_;
   }
   void check(int rc) {
     if (rc == LVX_OK) return;
@@ -632,6 +679,7 @@ class Calibrator {
   std::vector<double> sp_pt_, sp_map_, sp_t_; std::vector<int32_t> sp_plane_;
   int n_surfel_used_ = 0, n_planes_ = 0;
   lvx_error_stats stats_before_{}, stats_after_{};
+  bool has_cov_ = false; lvx_calib_cov cov_{};
 };
 
 }  // namespace lvx_host

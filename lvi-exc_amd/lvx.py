@@ -87,6 +87,19 @@ class LmSummary(C.Structure):
                 ("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_radius", C.c_double)]
 
 
+class CalibCovOptions(C.Structure):
+    _fields_ = [("radius", C.c_double), ("jacobi_scaling", C.c_int32), ("max_sweeps", C.c_int32)]
+
+
+N_CALIB = 22   # calibration scalars c = tangent - 6 N: gravity 0-1, acc bias 2-4, gyro bias 5-7, LiDAR q 8-10 / p 11-13 / tau 14, camera q 15-17 / p 18-20 / tau 21
+
+
+class CalibCov(C.Structure):
+    _fields_ = [("n_free", C.c_int32), ("free_index", C.c_int32 * N_CALIB), ("cov", C.c_double * (N_CALIB * N_CALIB)), ("sigma", C.c_double * N_CALIB),
+                ("info_eig", C.c_double * N_CALIB), ("info_vec", C.c_double * (N_CALIB * N_CALIB)), ("scale", C.c_double * N_CALIB),
+                ("radius", C.c_double), ("sweeps", C.c_int32), ("n_hub_eliminated", C.c_int32)]
+
+
 LM_TERMINATION = ["no_convergence", "function_tolerance", "parameter_tolerance", "gradient_tolerance", "max_iterations", "failure", "min_trust_region_radius"]
 
 
@@ -406,6 +419,22 @@ class Context:
         mcc = C.c_double(0)
         self._ck(self._l.lvx_solve_step(self._h, C.c_double(radius), C.c_int(1 if jacobi_scaling else 0), _p(delta), C.byref(mcc)))
         return delta, mcc.value
+
+    def calibration_covariance(self, radius=1e8, jacobi_scaling=True, max_sweeps=None):
+        """Covariance of the calibration scalars in the DAMPED system of the last evaluate(normal_eq=True) at `radius`, and the spectrum of their scaled marginal
+        information (lvx_calibration_covariance).  Returns a dict: free_index [n_free], cov [22, 22], sigma [22] (tangent units: a rotation entry is a half-angle),
+        info_eig [n_free] ascending, info_vec [n_free, n_free] (column k belongs to info_eig[k], rows over free_index), scale [22], radius, sweeps, n_hub_eliminated."""
+        opt = CalibCovOptions()
+        self._l.lvx_calib_cov_default_options(C.byref(opt))
+        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
+        if max_sweeps is not None:
+            opt.max_sweeps = int(max_sweeps)
+        r = CalibCov()
+        self._ck(self._l.lvx_calibration_covariance(self._h, C.byref(opt), C.byref(r)))
+        nf = r.n_free
+        return dict(free_index=np.array(r.free_index[:nf], dtype=np.int64), cov=np.array(r.cov).reshape(N_CALIB, N_CALIB), sigma=np.array(r.sigma),
+                    info_eig=np.array(r.info_eig[:nf]), info_vec=np.array(r.info_vec).reshape(N_CALIB, N_CALIB)[:nf, :nf].copy(), scale=np.array(r.scale),
+                    radius=r.radius, sweeps=r.sweeps, n_hub_eliminated=r.n_hub_eliminated)
 
     def lm_solve(self, state, max_iterations=50, **kw):
         """TrajectoryEstimator::Solve(max_iterations) equivalent.  Returns (state, summary dict with per-iteration history)."""
