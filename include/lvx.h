@@ -330,7 +330,7 @@ int lvx_solve_step(lvx_ctx* ctx, double radius, int jacobi_scaling, double* delt
  * prior the result depends on; where the data decide (trajectory locked) the result is independent of the radius to 1e-5 at 1e8.  info_eig shows which is the case: an
  * eigenvalue at 1e-6 / radius is a direction no residual row touches.
  * A context that takes part in a joint solve (a reduction callback or an RCCL communicator is installed) returns LVX_E_STATE: the covariance of the shared extrinsics
- * over all ranks' sequences is not computed here.  LVX_E_NOTPD: a pivot or an eigenvalue was not positive, or max_sweeps Jacobi sweeps did not converge (the
+ * over all ranks' sequences is not computed here (lvx_calibration_covariance_shared, below, is the call for it).  LVX_E_NOTPD: a pivot or an eigenvalue was not positive, or max_sweeps Jacobi sweeps did not converge (the
  * off-diagonal measure is in lvx_last_error); `out` is not written then. */
 typedef struct lvx_calib_cov_options { double radius; int32_t jacobi_scaling; int32_t max_sweeps; } lvx_calib_cov_options;   /* 1e8, 1, 30 */
 typedef struct lvx_calib_cov {
@@ -458,7 +458,7 @@ int lvx_surfel_map_release(lvx_ctx* ctx);
  * variables on its GPU, ONE all-reduce of the 14 x 14 reduced system (+ rhs + flags, 211 doubles), every rank solves it and back-substitutes;
  * plus tiny reductions of the cost, the model cost change and the step / gradient norms so that all ranks take the same accept / reject and
  * termination decisions.  The library does not link a communication library: the host supplies the reduction over HOST buffers (RCCL via
- * torch.distributed, MPI, ...); messages are <= 211 doubles and latency-bound.  All ranks must use the same lock mask and options. */
+ * torch.distributed, MPI, ...); messages are <= 278 doubles (the largest: lvx_calibration_covariance_shared) and latency-bound.  All ranks must use the same lock mask and options. */
 #define LVX_N_SHARED 14
 #define LVX_REDUCE_SUM 0
 #define LVX_REDUCE_MAX 1
@@ -466,6 +466,33 @@ typedef int (*lvx_allreduce_fn)(void* user, double* buf, int n, int op);   /* in
 /* lvx_solve_step / lvx_lm_solve of the joint problem; fn == NULL degenerates to the single-sequence calls */
 int lvx_solve_step_shared(lvx_ctx* ctx, double radius, int jacobi_scaling, lvx_allreduce_fn fn, void* user, double* delta, double* model_cost_change);
 int lvx_lm_solve_shared(lvx_ctx* ctx, double* state, const lvx_lm_options* opt, lvx_allreduce_fn fn, void* user, lvx_lm_summary* summary);
+
+/* lvx_calibration_covariance of the JOINT problem: how well all the sequences together determine the shared extrinsics, and how much each one contributed.  Every rank
+ * calls it after its own LVX_EVAL_NORMAL_EQ evaluation with the same options and the same locks on the shared scalars; the transport is chosen as in
+ * lvx_solve_step_shared (fn: host callback; fn == NULL with an RCCL communicator: the device path; fn == NULL without one: a joint problem of one rank).
+ * Definition: H = the joint normal matrix over [every rank's private scalars | the 14 shared scalars once], F its free scalars,
+ *   s = 1 / (1 + sqrt(diag H_FF)) (or 1): the shared entries come from the diagonal SUMMED over the ranks,
+ *   A_R = s H_FF s + diag(clamp(diag(s H_FF s), 1e-6, 1e32)) / radius,    cov = s A_R^-1 s  restricted to this rank's 8 private calibration scalars and the 14 shared,
+ * the system lvx_solve_step_shared factors at that radius (what the radius means: INTEGRATION.md 4d-2).  The spectrum is that of M, the Schur complement of A_R onto the
+ * free shared scalars, and own_info is this rank's term of it, T_r = s_sh (C_r - B_r^T A_r^-1 B_r) s_sh with the rank's private damping inside A_r and no shared damping:
+ *   sum_r own_info_r + diag(lmd_shared) / radius = M = V diag(info_eig) V^T,   lmd_shared = clamp(diag(s H s), 1e-6, 1e32) at the shared scalars.
+ * own_info[k][k] / M[k][k] is the fraction of the joint information about scalar k that this sequence supplied.  The shared part of the record (cov rows / columns
+ * 8 .. 21, info_eig, info_vec) is bit-identical on all ranks.  Exactly two collectives: the joint diagonal, and one sum of 278 doubles (T_r, per-slot free
+ * indicators, rank count, votes, sweep cap); with RCCL one host stop behind the first.  The stored normal equations and the LM state are left as they were.
+ * Errors are voted, every rank returns together and no rank writes `out`: LVX_E_NOTPD (a pivot or an eigenvalue not positive on any rank, or the sweep cap — the
+ * SMALLEST max_sweeps over the ranks applies everywhere, values above 64 count as 64); LVX_E_STATE (a rank has no preceding evaluation); LVX_E_ARG (a shared scalar
+ * is locked on some ranks and free on others); any other local failure returns its code on the failing rank and LVX_E_COMM on the others.  A pivot lost on the
+ * block-reduction route of any rank makes every rank repeat the elimination sequentially, with a third collective. */
+typedef struct lvx_joint_calib_cov {
+  int32_t n_free; int32_t free_index[22];      /* as lvx_calib_cov, under this rank's lock mask */
+  double  cov[22 * 22], sigma[22];             /* c 0..7 (gravity, biases): THIS rank's private scalars; c 8..21: the shared extrinsics; cross terms included */
+  int32_t n_shared_free; int32_t shared_free_slot[14];   /* canonical slots 0..13 (c - 8) that are free, ascending */
+  double  info_eig[14], info_vec[14 * 14];     /* spectrum of the JOINT Jacobi-scaled marginal information of the free shared scalars (ascending; column k over shared_free_slot) */
+  double  own_info[14 * 14];                   /* this rank's own contribution T_r to that matrix: canonical slots, joint scale, WITHOUT the shared damping; 0 in locked rows / columns */
+  double  scale[22];                           /* c 0..7 from this rank's diagonal, c 8..21 from the JOINT diagonal */
+  double  radius; int32_t sweeps, n_hub_eliminated, world;   /* world = number of ranks that took part (counted in the collective) */
+} lvx_joint_calib_cov;
+int lvx_calibration_covariance_shared(lvx_ctx* ctx, const lvx_calib_cov_options* opt, lvx_allreduce_fn fn, void* user, lvx_joint_calib_cov* out);
 
 /* RCCL transport: with a communicator installed the reductions of lvx_solve_step_shared / lvx_lm_solve_shared (fn = NULL) run as ncclAllReduce on the
  * context's stream — the per-step [S | rhs | votes] block is packed, reduced and solved on the device with no host round trip.  librccl is loaded with

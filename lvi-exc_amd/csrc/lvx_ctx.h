@@ -158,7 +158,7 @@ struct lvx_ctx {
   // block cyclic reduction (lvx_bcr.hip): diagonal blocks, per-level coupling blocks, pivot info; rocBLAS handle
   int solver_fallbacks = 0;   // lvx_layout::solver_fallbacks
   int lm_elim_kernel = 0;     // lvx_layout::lm_elim_kernel: which landmark elimination the last solve launched
-  lvx::DevBuf d_ccov;         // lvx_calibration_covariance: the record k_calib_cov writes (LVX_CCOV_N doubles)
+  lvx::DevBuf d_ccov;         // lvx_calibration_covariance: the record k_calib_cov writes (LVX_CCOV_N doubles); ..._shared: record, kept factor and message of k_joint_cov_*
   lvx::DevBuf d_bcrD, d_bcrG, d_bcrInfo, d_Y2, d_gram, d_bcrLinv; bool bcr_linv = false;   // d_bcrLinv: inverses of the factors' 16 x 16 diagonal triangles (k_potrf_batched -> k_trsm_reg)
   void* blas = nullptr;
   int bcr_b = 0, bcr_nblk = 0, bcr_nreal = 0;

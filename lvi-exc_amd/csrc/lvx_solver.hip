@@ -721,6 +721,22 @@ __global__ __launch_bounds__(256) void k_pre_solve(const double* gb, double* gbs
 #define LVX_CCOV_N (2 * LVX_NCAL * LVX_NCAL + 3 * LVX_NCAL + 6)
 #define CCOV_NT 256
 struct SymeigBlockSync { __device__ void operator()() const { __syncthreads(); } };
+// Columns 0 .. ne - 1 of T (lower triangle, [n][ld] in LDS) eliminated in place by the CCOV_NT threads of the workgroup: afterwards T[k][k] = d_k and, below it, column k
+// holds l_ik d_k of the L D L^T factor; the trailing block is the Schur complement.  A pivot that is not positive is replaced by 1 and the first one is noted in piv
+// (1-based column, value).  The caller has a barrier behind its loads; the last step's barrier is the exit.
+__device__ __forceinline__ void border_eliminate(double* T, int ld, int n, int ne, double* piv, int tid) {
+  for (int k = 0; k < ne; ++k) {
+    if (tid == 0) { const double d = T[k * ld + k]; if (!(d > 0.0)) { if (piv[0] == 0.0) { piv[0] = (double)(k + 1); piv[1] = d; } T[k * ld + k] = 1.0; } }
+    __syncthreads();
+    const double inv = 1.0 / T[k * ld + k];
+    for (int c0 = k + 1; c0 < n; c0 += 64) {   // lane = column, wavefront = row (as k_dense_partial); column k is read, never written, in this step
+      const int cc = c0 + (tid & 63);
+      const double lc = cc < n ? T[cc * ld + k] * inv : 0.0;
+      for (int rr = k + 1 + (tid >> 6); rr < n; rr += CCOV_NT / 64) if (cc < n && rr >= cc) T[rr * ld + cc] -= T[rr * ld + k] * lc;
+    }
+    __syncthreads();
+  }
+}
 __global__ __launch_bounds__(CCOV_NT) void k_calib_cov(const double* __restrict__ S, int n, int nh, const double* __restrict__ scale_c, uint32_t free_mask, int max_sweeps, const int* info, double* out) {
   extern __shared__ double ds[];           // T [n][n + 1]
   __shared__ double M[LVX_NCAL * (LVX_NCAL + 1)], V[LVX_NCAL * (LVX_NCAL + 1)], cs[LVX_SYMEIG_CS], piv[2];
@@ -736,17 +752,7 @@ __global__ __launch_bounds__(CCOV_NT) void k_calib_cov(const double* __restrict_
   __syncthreads();
   int nf = 0;
   for (int c = 0; c < LVX_NCAL; ++c) nf += (int)(free_mask >> c & 1u);
-  for (int k = 0; k < nh; ++k) {
-    if (tid == 0) { const double d = T[k * ld + k]; if (!(d > 0.0)) { if (piv[0] == 0.0) { piv[0] = (double)(k + 1); piv[1] = d; } T[k * ld + k] = 1.0; } }
-    __syncthreads();
-    const double inv = 1.0 / T[k * ld + k];
-    for (int c0 = k + 1; c0 < n; c0 += 64) {   // lane = column, wavefront = row (as k_dense_partial); column k is read, never written, in this step
-      const int cc = c0 + (tid & 63);
-      const double lc = cc < n ? T[cc * ld + k] * inv : 0.0;
-      for (int rr = k + 1 + (tid >> 6); rr < n; rr += CCOV_NT / 64) if (cc < n && rr >= cc) T[rr * ld + cc] -= T[rr * ld + k] * lc;
-    }
-    __syncthreads();
-  }
+  border_eliminate(T, ld, n, nh, piv, tid);
   for (int e = tid; e < nf * nf; e += CCOV_NT) {
     const int i = e / nf, j = e % nf, a = nh + fr[i > j ? i : j], b = nh + fr[i > j ? j : i];
     M[i * ldm + j] = T[a * ld + b];
@@ -769,6 +775,166 @@ __global__ __launch_bounds__(CCOV_NT) void k_calib_cov(const double* __restrict_
   }
   if (tid < LVX_NCAL) { o_w[tid] = tid < nf ? M[order[tid] * (ldm + 1)] : 0.0; o_sc[tid] = scale_c[tid]; }
   if (tid == 0) { o_tail[0] = off; o_tail[1] = (double)sweeps; o_tail[2] = (double)status; o_tail[3] = (double)info[0]; o_tail[4] = piv[0]; o_tail[5] = piv[1]; }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// lvx_calibration_covariance_shared: the calibration covariance of the JOINT problem (private scalars per rank, the 14 extrinsic scalars shared).  Two one-workgroup
+// kernels around ONE sum over the ranks.  Border order: [nh hub | 8 private calibration slots | 14 shared slots]; the shared damping is not in S (apply_diag).
+//   k_joint_cov_local   eliminates hub and private columns (a locked slot is an inert lmd / R diagonal), keeps P^-1 (8 x 8, P the private block behind the hub
+//                       elimination) and G = P^-1 X (8 x 14, X the coupling) from the L D L^T factor, and packs this rank's term T_r of the shared block.
+//   k_joint_cov_shared  the same instructions on the same reduced message on every rank: M = sum_r T_r + lmd_shared / R over the free shared slots, M = V w V^T,
+//                       cov_ss = D M^-1 D, cov_pp = D_p (P^-1 + G M^-1 G^T) D_p, cov_ps = -D_p G M^-1 D_s.
+// Message (LVX_JC_N doubles, summed): T_r [14][14] canonical slots | slot free (14) | 1 (ranks) | not-PD votes | error votes | ranks whose elimination ran on the
+// reduction route (a sequential redo can help) | one-hot of min(max_sweeps, 64): the smallest cap over the ranks applies on all of them.
+// Record (LVX_JREC_N): cov [22][22] | sigma [22] | w [14] | V [14][14] | own T_r [14][14] | scale [22] | off, sweeps, status, band pivot code, first pivot, its value,
+// ranks, not-PD votes, error votes, redo votes.  status: 0 ok, 1 sweep cap, 2 eigenvalue not positive, 3 a shared slot is free on some ranks only, 4 / 5 votes.
+// ---------------------------------------------------------------------------------------------------------
+#define LVX_NPRIV (LVX_NCAL - LVX_N_SHARED)
+#define LVX_JC_FREE (LVX_N_SHARED * LVX_N_SHARED)
+#define LVX_JC_WORLD (LVX_JC_FREE + LVX_N_SHARED)
+#define LVX_JC_NOTPD (LVX_JC_WORLD + 1)
+#define LVX_JC_ERR (LVX_JC_WORLD + 2)
+#define LVX_JC_REDO (LVX_JC_WORLD + 3)
+#define LVX_JC_SWEEPS (LVX_JC_WORLD + 4)
+#define LVX_JC_SWEEP_SLOTS 64
+#define LVX_JC_N (LVX_JC_SWEEPS + LVX_JC_SWEEP_SLOTS)
+#define LVX_JKEEP_N (LVX_NPRIV * LVX_NPRIV + LVX_NPRIV * LVX_N_SHARED)
+#define LVX_JREC_COV 0
+#define LVX_JREC_SIG (LVX_NCAL * LVX_NCAL)
+#define LVX_JREC_W (LVX_JREC_SIG + LVX_NCAL)
+#define LVX_JREC_V (LVX_JREC_W + LVX_N_SHARED)
+#define LVX_JREC_OWN (LVX_JREC_V + LVX_N_SHARED * LVX_N_SHARED)
+#define LVX_JREC_SCALE (LVX_JREC_OWN + LVX_N_SHARED * LVX_N_SHARED)
+#define LVX_JREC_TAIL (LVX_JREC_SCALE + LVX_NCAL)
+#define LVX_JREC_N (LVX_JREC_TAIL + 10)
+// S == nullptr: this rank failed before its border system existed — the message carries its votes only
+__global__ __launch_bounds__(CCOV_NT) void k_joint_cov_local(const double* __restrict__ S, int n, int nh, uint32_t free_mask, int sweep_slot, double err, double force_notpd, double redo,
+                                                            const int* info, double* msg, double* keep, double* rec) {
+  extern __shared__ double ds[];           // T [n][n + 1]
+  __shared__ double piv[2], d[LVX_NPRIV], Li[LVX_NPRIV * LVX_NPRIV], W[LVX_N_SHARED * LVX_NPRIV];
+  const int tid = threadIdx.x, ld = n + 1, np = nh + LVX_NPRIV;
+  double* T = ds;
+  for (int e = tid; e < LVX_JC_N; e += CCOV_NT) msg[e] = 0.0;
+  if (tid == 0) { piv[0] = 0.0; piv[1] = 0.0; }
+  __syncthreads();
+  if (S != nullptr) {
+    for (int r = tid >> 6; r < n; r += CCOV_NT / 64) for (int cc = tid & 63; cc <= r; cc += 64) T[r * ld + cc] = S[(size_t)r * n + cc];
+    __syncthreads();
+    border_eliminate(T, ld, n, np, piv, tid);
+    if (tid < LVX_NPRIV) d[tid] = T[(nh + tid) * ld + nh + tid];
+    __syncthreads();
+    for (int e = tid; e < LVX_N_SHARED * LVX_NPRIV; e += CCOV_NT) W[e] = T[(np + e / LVX_NPRIV) * ld + nh + e % LVX_NPRIV] / d[e % LVX_NPRIV];   // W = X^T L^-T D^-1
+    if (tid < LVX_NPRIV) {   // column tid of L^-1 (unit lower triangular): L x = e_tid
+      for (int i = 0; i < LVX_NPRIV; ++i) {
+        double t = i == tid ? 1.0 : 0.0;
+        for (int k = tid; k < i; ++k) t -= T[(nh + i) * ld + nh + k] / d[k] * Li[k * LVX_NPRIV + tid];
+        Li[i * LVX_NPRIV + tid] = i < tid ? 0.0 : t;
+      }
+    }
+    __syncthreads();
+    for (int e = tid; e < LVX_NPRIV * LVX_NPRIV; e += CCOV_NT) {   // P^-1 = L^-T D^-1 L^-1
+      const int i = e / LVX_NPRIV, j = e % LVX_NPRIV;
+      double s = 0.0;
+      for (int k = i > j ? i : j; k < LVX_NPRIV; ++k) s += Li[k * LVX_NPRIV + i] * Li[k * LVX_NPRIV + j] / d[k];
+      keep[e] = s;
+    }
+    for (int e = tid; e < LVX_NPRIV * LVX_N_SHARED; e += CCOV_NT) {   // G = L^-T W^T
+      const int i = e / LVX_N_SHARED, a = e % LVX_N_SHARED;
+      double g = 0.0;
+      for (int k = i; k < LVX_NPRIV; ++k) g += Li[k * LVX_NPRIV + i] * W[a * LVX_NPRIV + k];
+      keep[LVX_NPRIV * LVX_NPRIV + e] = g;
+    }
+    for (int e = tid; e < LVX_N_SHARED * LVX_N_SHARED; e += CCOV_NT) {
+      const int a = e / LVX_N_SHARED, b = e % LVX_N_SHARED, hi = a > b ? a : b, lo = a > b ? b : a;
+      const bool fr = (free_mask >> (LVX_NPRIV + a) & 1u) && (free_mask >> (LVX_NPRIV + b) & 1u);
+      const double v = fr ? T[(np + hi) * ld + np + lo] : 0.0;
+      msg[e] = v; rec[LVX_JREC_OWN + e] = v;
+    }
+    if (tid < LVX_N_SHARED) msg[LVX_JC_FREE + tid] = (free_mask >> (LVX_NPRIV + tid) & 1u) ? 1.0 : 0.0;
+  }
+  if (tid == 0) {
+    const int code = (S != nullptr && info != nullptr) ? info[0] : 0;
+    msg[LVX_JC_WORLD] = 1.0;
+    msg[LVX_JC_NOTPD] = (piv[0] != 0.0 || code != 0 || force_notpd != 0.0) ? 1.0 : 0.0;
+    msg[LVX_JC_ERR] = err; msg[LVX_JC_REDO] = redo;
+    msg[LVX_JC_SWEEPS + sweep_slot] = 1.0;
+    rec[LVX_JREC_TAIL + 3] = (double)code; rec[LVX_JREC_TAIL + 4] = piv[0]; rec[LVX_JREC_TAIL + 5] = piv[1];
+  }
+}
+struct JointLmd { double v[LVX_N_SHARED]; };
+__global__ __launch_bounds__(CCOV_NT) void k_joint_cov_shared(const double* __restrict__ msg, const double* __restrict__ keep, JointLmd lmd, double inv_radius, const double* __restrict__ scale_c,
+                                                             uint32_t free_mask, double* rec) {
+  __shared__ double M[LVX_N_SHARED * (LVX_N_SHARED + 1)], V[LVX_N_SHARED * (LVX_N_SHARED + 1)], Mi[LVX_N_SHARED * LVX_N_SHARED], GM[LVX_NPRIV * LVX_N_SHARED], cs[LVX_SYMEIG_CS];
+  __shared__ int order[LVX_N_SHARED], fr[LVX_N_SHARED], slot[LVX_N_SHARED], hdr[3];   // hdr: free shared slots, status, sweep cap
+  const int tid = threadIdx.x, ldm = LVX_N_SHARED + 1;
+  const double* Pi = keep, *G = keep + LVX_NPRIV * LVX_NPRIV;
+  if (tid == 0) {
+    const double world = msg[LVX_JC_WORLD];
+    int st = msg[LVX_JC_ERR] > 0.0 ? 5 : msg[LVX_JC_NOTPD] > 0.0 ? 4 : 0, nf0 = 0, cap = LVX_JC_SWEEP_SLOTS;
+    for (int a = 0; a < LVX_N_SHARED; ++a) {
+      const double f = msg[LVX_JC_FREE + a];
+      slot[a] = -1;
+      if (f == world) { slot[a] = nf0; fr[nf0++] = a; }
+      else if (f != 0.0 && st == 0) st = 3;
+    }
+    for (int k = LVX_JC_SWEEP_SLOTS - 1; k >= 0; --k) if (msg[LVX_JC_SWEEPS + k] > 0.0) cap = k + 1;
+    hdr[0] = nf0; hdr[1] = st; hdr[2] = cap;
+  }
+  __syncthreads();
+  const int nf = hdr[0];
+  int status = hdr[1], sweeps = 0;
+  double off = 0.0;
+  if (status == 0) {
+    for (int e = tid; e < nf * nf; e += CCOV_NT) {
+      const int i = e / nf, j = e % nf;
+      M[i * ldm + j] = msg[fr[i] * LVX_N_SHARED + fr[j]] + (i == j ? lmd.v[fr[i]] * inv_radius : 0.0);
+    }
+    __syncthreads();
+    if (symeig_jacobi(M, ldm, nf, V, ldm, cs, hdr[2], tid, CCOV_NT, SymeigBlockSync(), &sweeps, &off)) status = 1;
+    if (tid == 0) symeig_order(M, ldm + 1, nf, order);
+    __syncthreads();
+    for (int k = 0; k < nf; ++k) if (!status && !(M[k * (ldm + 1)] > 0.0)) status = 2;
+  }
+  if (status == 0) {
+    for (int e = tid; e < nf * nf; e += CCOV_NT) {   // M^-1 over the free shared slots
+      const int i = e / nf, j = e % nf;
+      double s = 0.0;
+      for (int k = 0; k < nf; ++k) { const int q = order[k]; s += V[i * ldm + q] * V[j * ldm + q] / M[q * (ldm + 1)]; }
+      Mi[i * LVX_N_SHARED + j] = s;
+    }
+    __syncthreads();
+    for (int e = tid; e < LVX_NPRIV * nf; e += CCOV_NT) {   // G M^-1
+      const int p = e / nf, j = e % nf;
+      double s = 0.0;
+      for (int i = 0; i < nf; ++i) s += G[p * LVX_N_SHARED + fr[i]] * Mi[i * LVX_N_SHARED + j];
+      GM[p * LVX_N_SHARED + j] = s;
+    }
+    __syncthreads();
+  }
+  for (int e = tid; e < LVX_NCAL * LVX_NCAL; e += CCOV_NT) {
+    const int ci = e / LVX_NCAL, cj = e % LVX_NCAL, a = ci > cj ? ci : cj, b = ci > cj ? cj : ci;   // one expression per unordered pair: the record is symmetric to the bit
+    const int sa = a >= LVX_NPRIV ? slot[a - LVX_NPRIV] : -1, sb = b >= LVX_NPRIV ? slot[b - LVX_NPRIV] : -1;
+    const bool fa = a >= LVX_NPRIV ? sa >= 0 : (free_mask >> a & 1u) != 0, fb = b >= LVX_NPRIV ? sb >= 0 : (free_mask >> b & 1u) != 0;
+    double s = 0.0;
+    if (status == 0 && fa && fb) {
+      if (b >= LVX_NPRIV) s = Mi[sa * LVX_N_SHARED + sb];
+      else if (a >= LVX_NPRIV) s = -GM[b * LVX_N_SHARED + sa];
+      else { s = Pi[a * LVX_NPRIV + b]; for (int j = 0; j < nf; ++j) s += GM[a * LVX_N_SHARED + j] * G[b * LVX_N_SHARED + fr[j]]; }
+      s *= scale_c[a] * scale_c[b];
+    }
+    rec[LVX_JREC_COV + e] = s;
+    if (ci == cj) rec[LVX_JREC_SIG + ci] = sqrt(s);
+  }
+  for (int e = tid; e < LVX_N_SHARED * LVX_N_SHARED; e += CCOV_NT) {
+    const int i = e / LVX_N_SHARED, j = e % LVX_N_SHARED;
+    rec[LVX_JREC_V + e] = (hdr[1] == 0 && i < nf && j < nf) ? V[i * ldm + order[j]] : 0.0;   // (hdr[1] == 0: the decomposition ran, V and order exist)
+  }
+  if (tid < LVX_N_SHARED) rec[LVX_JREC_W + tid] = (hdr[1] == 0 && tid < nf) ? M[order[tid] * (ldm + 1)] : 0.0;
+  if (tid < LVX_NCAL) rec[LVX_JREC_SCALE + tid] = scale_c[tid];
+  if (tid == 0) {
+    double* t = rec + LVX_JREC_TAIL;
+    t[0] = off; t[1] = (double)sweeps; t[2] = (double)status; t[6] = msg[LVX_JC_WORLD]; t[7] = msg[LVX_JC_NOTPD]; t[8] = msg[LVX_JC_ERR]; t[9] = msg[LVX_JC_REDO];
+  }
 }
 
 }  // namespace lvx
@@ -813,7 +979,7 @@ static RcclApi* rccl_api(lvx_ctx* c) {
   api.lib = lib;
   return &api;
 }
-#define LVX_COMM_BUF 512   // doubles of the device staging buffer of the reductions (the largest message is 212)
+#define LVX_COMM_BUF 512   // doubles of the device staging buffer of the reductions (the largest message is LVX_JC_N = 278)
 static bool is_joint(const lvx_ctx* c) { return c->ar_fn != nullptr || c->rccl_comm != nullptr; }
 // in place over all ranks on the DEVICE buffer d_comm[0..n), queued on the context's stream
 static int reduce_device(lvx_ctx* c, int n, int op) {
@@ -1430,6 +1596,85 @@ int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx
   std::memcpy(out->info_vec, p, sizeof out->info_vec); p += LVX_NCAL * LVX_NCAL;
   std::memcpy(out->scale, p, sizeof out->scale);
   out->radius = opt->radius; out->sweeps = (int32_t)tail[1]; out->n_hub_eliminated = nh;
+  return LVX_OK;
+}
+
+// The covariance of the JOINT problem: lvx_solve_step_shared's front half (the diagonal collective puts the joint diagonal at the shared slots and withholds their
+// damping), the elimination down to the border system from copies, then k_joint_cov_local -> ONE sum over the ranks -> k_joint_cov_shared.  Two collectives per call;
+// every failure is voted in the collective that follows it, so all ranks leave together.  With RCCL everything behind the diagonal collective is queued on the stream
+// and the record comes back in one copy: one host stop.  A pivot lost on the reduction route of ANY rank: every rank repeats the second half sequentially (a third
+// collective, as rare as the fallback of lvx_solve_step).
+static int identity_allreduce(void*, double*, int, int) { return 0; }
+int lvx_calibration_covariance_shared(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx_allreduce_fn fn, void* user, lvx_joint_calib_cov* out) {
+  if (!c || !opt || !out || !(opt->radius > 0) || opt->max_sweeps < 1) return LVX_E_ARG;
+  LVX_HIP(c, hipSetDevice(c->device));
+  HookScope hook(c, (fn || c->rccl_comm) ? fn : identity_allreduce, user);   // no transport: a joint problem of one rank
+  int lerr = LVX_OK;
+  double no_eval = 0.0;
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ)) { lerr = fail(c, LVX_E_STATE, "lvx_calibration_covariance_shared needs a preceding LVX_EVAL_NORMAL_EQ evaluation"); no_eval = 1.0; }
+  if (!lerr) lerr = check_last_eval(c);
+  SolveWork w;
+  if (!lerr) lerr = solver_alloc(c, w);
+  const int nb = c->nb, nbd = c->nbd, nh = nbd - LVX_NCAL;
+  if (!lerr && (nh < 0 || nbd > 128)) lerr = fail(c, LVX_E_ARG, "lvx_calibration_covariance_shared: border of " + std::to_string(nbd) + " scalars (22 .. 128 fit the one-workgroup kernel)");
+  if (!lerr) lerr = dev_alloc(c, c->d_ccov, (size_t)(LVX_JREC_N + LVX_JKEEP_N + LVX_JC_N) * 8);
+  double cost = 0.0; bool gconv = false;
+  int rc = post_eval(c, w, true, opt->jacobi_scaling, 1e-6, 1e32, &cost, 0.0, &gconv, lerr, &no_eval);
+  if (no_eval > 0.0) return lerr == LVX_E_STATE ? lerr : fail(c, LVX_E_STATE, "lvx_calibration_covariance_shared: a rank of the joint problem has no preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  uint32_t free_mask = 0;
+  for (int k = 0; k < LVX_NCAL; ++k) if (c->ord[6 * (size_t)c->N + k] != LVX_DEAD) free_mask |= 1u << k;
+  double* rec = (double*)c->d_ccov.p, *keep = rec + LVX_JREC_N;
+  double* msg = c->rccl_comm ? (double*)c->d_comm.p : keep + LVX_JKEEP_N;   // RCCL reduces in its staging buffer; the callback's message is staged through the host
+  JointLmd lmd{};
+  for (int a = 0; a < LVX_N_SHARED; ++a) lmd.v[a] = c->sh_lmd[a];
+  const int sweep_slot = std::min((int)opt->max_sweeps, LVX_JC_SWEEP_SLOTS) - 1;
+  std::vector<double> h(LVX_JREC_N), hm(LVX_JC_N);
+  StageTimer tm(c);
+  const size_t lds = (size_t)nbd * (nbd + 1) * 8;
+  LVX_HIP(c, hipFuncSetAttribute((const void*)k_joint_cov_local, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const double* tail = h.data() + LVX_JREC_TAIL;
+  auto run = [&](bool force_seq, bool* bcr_used) -> int {
+    w.lm_done = false;
+    const int lrc = reduce_to_border(c, w, opt->radius, force_seq, bcr_used, tm);   // a local failure is voted: nobody waits in the sum
+    if (lrc) hipLaunchKernelGGL(k_joint_cov_local, dim3(1), dim3(CCOV_NT), 0, st, (const double*)nullptr, nbd, nh, free_mask, sweep_slot, 1.0, 0.0, 0.0, (const int*)nullptr, msg, keep, rec);
+    else hipLaunchKernelGGL(k_joint_cov_local, dim3(1), dim3(CCOV_NT), lds, st, (const double*)w.S, nbd, nh, free_mask, sweep_slot, 0.0, (*bcr_used && c->sw.test_bad_pivot) ? 1.0 : 0.0,
+                            *bcr_used ? 1.0 : 0.0, (const int*)w.info, msg, keep, rec);
+    int r2;
+    if (c->rccl_comm) { if ((r2 = reduce_device(c, LVX_JC_N, LVX_REDUCE_SUM))) return r2; }
+    else {
+      LVX_HIP(c, hipMemcpyAsync(hm.data(), msg, (size_t)LVX_JC_N * 8, hipMemcpyDeviceToHost, st));
+      LVX_HIP(c, hipStreamSynchronize(st));
+      if ((r2 = reduce(c, hm.data(), LVX_JC_N, LVX_REDUCE_SUM))) return r2;
+      LVX_HIP(c, hipMemcpyAsync(msg, hm.data(), (size_t)LVX_JC_N * 8, hipMemcpyHostToDevice, st));
+    }
+    hipLaunchKernelGGL(k_joint_cov_shared, dim3(1), dim3(CCOV_NT), 0, st, (const double*)msg, (const double*)keep, lmd, 1.0 / opt->radius, (const double*)(w.scale + (nb + nh)), free_mask, rec);
+    LVX_HIP(c, hipGetLastError());
+    LVX_HIP(c, hipMemcpyAsync(h.data(), rec, (size_t)LVX_JREC_N * 8, hipMemcpyDeviceToHost, st));
+    LVX_HIP(c, hipStreamSynchronize(st));
+    return leave_together(c, tail[8], lrc);
+  };
+  bool bcr_used = false;
+  if ((rc = run(false, &bcr_used))) return rc;
+  if (tail[9] > 0.0 && (tail[7] > 0.0 || tail[2] == 2.0)) {   // decided on reduced words: every rank repeats, the ones that were sequential already included
+    if (bcr_used) ++c->solver_fallbacks;
+    if ((rc = run(true, &bcr_used))) return rc;
+  }
+  if (tail[2] == 3.0) return fail(c, LVX_E_ARG, "lvx_calibration_covariance_shared: a shared extrinsic scalar is locked on some ranks and free on others");
+  if (tail[7] > 0.0) return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string((int)tail[3]) + ", first hub pivot " + std::to_string((int)tail[4]) + " value " + std::to_string(tail[5]) + ")");
+  if (tail[2] == 2.0) return fail(c, LVX_E_NOTPD, "marginal information of the calibration scalars has a non-positive eigenvalue " + std::to_string(h[LVX_JREC_W]));
+  if (tail[2] != 0.0) { char buf[160]; snprintf(buf, sizeof buf, "Jacobi eigen-decomposition not converged after %d sweeps: max |t_pq| / sqrt(t_pp t_qq) = %.3e", (int)tail[1], tail[0]); return fail(c, LVX_E_NOTPD, buf); }
+  std::memset(out, 0, sizeof *out);
+  for (int k = 0; k < LVX_NCAL; ++k) if (free_mask >> k & 1u) out->free_index[out->n_free++] = k;
+  for (int a = 0; a < LVX_N_SHARED; ++a) if (free_mask >> (LVX_NPRIV + a) & 1u) out->shared_free_slot[out->n_shared_free++] = a;
+  std::memcpy(out->cov, h.data() + LVX_JREC_COV, sizeof out->cov);
+  std::memcpy(out->sigma, h.data() + LVX_JREC_SIG, sizeof out->sigma);
+  std::memcpy(out->info_eig, h.data() + LVX_JREC_W, sizeof out->info_eig);
+  std::memcpy(out->info_vec, h.data() + LVX_JREC_V, sizeof out->info_vec);
+  std::memcpy(out->own_info, h.data() + LVX_JREC_OWN, sizeof out->own_info);
+  std::memcpy(out->scale, h.data() + LVX_JREC_SCALE, sizeof out->scale);
+  out->radius = opt->radius; out->sweeps = (int32_t)tail[1]; out->n_hub_eliminated = nh; out->world = (int32_t)tail[6];
   return LVX_OK;
 }
 

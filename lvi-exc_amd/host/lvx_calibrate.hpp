@@ -117,6 +117,43 @@ inline std::string FormatCalibrationUncertainty(const lvx_calib_cov& r) {
   return out;
 }
 
+// The same for a lvx_joint_calib_cov (lvx_calibration_covariance_shared: several sequences, shared extrinsics): the [LiDAR] / [Camera] / [Spectrum] lines of the JOINT
+// problem, and per sensor this sequence's fraction of the diagonal of the joint information of the shared scalars, own_info_kk / (sum_q w_q V_kq^2):
+//   [Share] LiDAR  rotation: a b c; translation: x y z                        (in [0, 1]; the fractions of all sequences and the LM prior add up to 1; a constant scalar prints 0)
+inline std::string FormatJointCalibrationUncertainty(const lvx_joint_calib_cov& r) {
+  std::string out;
+  char buf[256];
+  const double deg = 2.0 * 180.0 / 3.14159265358979323846;
+  const struct { const char* tag; const char* name; int c0; } sensors[2] = {{"[LiDAR] ", "LiDAR ", 8}, {"[Camera]", "Camera", 15}};
+  const int ns = r.n_shared_free;
+  for (const auto& sn : sensors) {
+    bool any = false;
+    for (int k = 0; k < r.n_free; ++k) any = any || (r.free_index[k] >= sn.c0 && r.free_index[k] < sn.c0 + 6);
+    if (!any) continue;
+    const double* s = r.sigma + sn.c0;
+    std::snprintf(buf, sizeof buf, "%s rotation std (deg): %.6e %.6e %.6e; translation std (m): %.6e %.6e %.6e\n", sn.tag, deg * s[0], deg * s[1], deg * s[2], s[3], s[4], s[5]);
+    out += buf;
+    double share[6] = {0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < ns; ++i) {
+      const int slot = r.shared_free_slot[i], j = slot - (sn.c0 - 8);
+      if (j < 0 || j >= 6) continue;
+      double m = 0.0;
+      for (int q = 0; q < ns; ++q) m += r.info_eig[q] * r.info_vec[i * 14 + q] * r.info_vec[i * 14 + q];
+      share[j] = r.own_info[slot * 14 + slot] / m;
+    }
+    std::snprintf(buf, sizeof buf, "[Share] %s rotation: %.6e %.6e %.6e; translation: %.6e %.6e %.6e\n", sn.name, share[0], share[1], share[2], share[3], share[4], share[5]);
+    out += buf;
+  }
+  if (ns > 0) {
+    int dom = 0;
+    for (int i = 1; i < ns; ++i) if (std::fabs(r.info_vec[i * 14]) > std::fabs(r.info_vec[dom * 14])) dom = i;
+    const int c = 8 + r.shared_free_slot[dom];
+    std::snprintf(buf, sizeof buf, "[Spectrum] smallest scaled eigenvalue: %.6e (radius %.6e); dominant scalar: %s (c = %d)\n", r.info_eig[0], r.radius, CalibScalarName(c), c);
+    out += buf;
+  }
+  return out;
+}
+
 inline std::vector<int32_t> MatchScanImages(const std::vector<double>& scan_t, const std::vector<double>& image_t) {
   std::vector<int32_t> idx(scan_t.size(), -1);
   for (size_t j = 0; j < scan_t.size(); ++j)

@@ -100,6 +100,16 @@ class CalibCov(C.Structure):
                 ("radius", C.c_double), ("sweeps", C.c_int32), ("n_hub_eliminated", C.c_int32)]
 
 
+N_SHARED = 14   # the shared extrinsic scalars of a joint solve: canonical slot k = c - 8
+
+
+class JointCalibCov(C.Structure):
+    _fields_ = [("n_free", C.c_int32), ("free_index", C.c_int32 * N_CALIB), ("cov", C.c_double * (N_CALIB * N_CALIB)), ("sigma", C.c_double * N_CALIB),
+                ("n_shared_free", C.c_int32), ("shared_free_slot", C.c_int32 * N_SHARED), ("info_eig", C.c_double * N_SHARED), ("info_vec", C.c_double * (N_SHARED * N_SHARED)),
+                ("own_info", C.c_double * (N_SHARED * N_SHARED)), ("scale", C.c_double * N_CALIB),
+                ("radius", C.c_double), ("sweeps", C.c_int32), ("n_hub_eliminated", C.c_int32), ("world", C.c_int32)]
+
+
 LM_TERMINATION = ["no_convergence", "function_tolerance", "parameter_tolerance", "gradient_tolerance", "max_iterations", "failure", "min_trust_region_radius"]
 
 
@@ -494,6 +504,26 @@ class Context:
         out["termination"] = LM_TERMINATION[sm.termination]
         out.update(cost_history=cost[:k], radius_history=rad[:k], accepted=acc[:k])
         return x, out
+
+    def calibration_covariance_shared(self, allreduce, radius=1e8, jacobi_scaling=True, max_sweeps=None):
+        """calibration_covariance of the JOINT problem (lvx_calibration_covariance_shared); every rank calls it after its own evaluate(normal_eq=True) with the same
+        options.  allreduce as in solve_step_shared; None: the RCCL communicator installed with rccl_init, or a joint problem of one rank.  Returns a dict: free_index,
+        cov [22, 22] (c 0..7 this rank's private scalars, c 8..21 the shared extrinsics), sigma [22], shared_free_slot [n_shared_free] (slot = c - 8), info_eig
+        [n_shared_free] ascending and info_vec [n_shared_free, n_shared_free] (rows over shared_free_slot) of the joint scaled marginal information of the shared scalars,
+        own_info [14, 14] (this rank's term of that matrix, without the shared damping), scale [22], radius, sweeps, n_hub_eliminated, world."""
+        opt = CalibCovOptions()
+        self._l.lvx_calib_cov_default_options(C.byref(opt))
+        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
+        if max_sweeps is not None:
+            opt.max_sweeps = int(max_sweeps)
+        r = JointCalibCov()
+        cb = self._hook(allreduce) if allreduce is not None else None
+        self._ck(self._l.lvx_calibration_covariance_shared(self._h, C.byref(opt), cb, None, C.byref(r)))
+        nf, ns = r.n_free, r.n_shared_free
+        return dict(free_index=np.array(r.free_index[:nf], dtype=np.int64), cov=np.array(r.cov).reshape(N_CALIB, N_CALIB), sigma=np.array(r.sigma),
+                    shared_free_slot=np.array(r.shared_free_slot[:ns], dtype=np.int64), info_eig=np.array(r.info_eig[:ns]),
+                    info_vec=np.array(r.info_vec).reshape(N_SHARED, N_SHARED)[:ns, :ns].copy(), own_info=np.array(r.own_info).reshape(N_SHARED, N_SHARED),
+                    scale=np.array(r.scale), radius=r.radius, sweeps=r.sweeps, n_hub_eliminated=r.n_hub_eliminated, world=r.world)
 
     # ---- RCCL transport of the joint solve (the reductions run as ncclAllReduce on the context's stream) ----
     def rccl_unique_id(self):
