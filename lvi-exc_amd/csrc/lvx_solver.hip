@@ -24,6 +24,7 @@
 #include <rccl/rccl.h>   // types only: the entry points are resolved with dlsym (rccl_api)
 
 #include "lvx_ctx.h"
+#include "lvx_lm_policy.h"
 #include "lvx_symeig.h"
 
 namespace lvx {
@@ -1337,8 +1338,10 @@ static int solve_step_device(lvx_ctx* c, SolveWork& w, double radius, double m[3
   return LVX_OK;
 }
 
-// max |g| over this rank's private free scalars (band, private border, landmarks) -> *g; the shared entries of g_c -> gsh[ns]
-static int local_gmax(lvx_ctx* c, SolveWork& w, double* g, double* gsh) {   // (with the diagonal of J^T J, which the same launch fetches: k_post_eval)
+// What a LVX_EVAL_NORMAL_EQ evaluation leaves on the host (local_after_eval): this rank's private gradient max norm, the shared entries of diagonal / gradient
+struct EvalLocal { double gm = 0.0; double hd[LVX_N_SHARED] = {0}, hg[LVX_N_SHARED] = {0}; double tau[2] = {0, 0}; bool have_tau = false; };   // tau: the (shared) sensor time offsets of a constrained joint solve
+// max |g| over this rank's private free scalars (band, private border, landmarks) and the shared entries of g_c, queued into the pinned words
+static int local_gmax(lvx_ctx* c, SolveWork& w) {   // (with the diagonal of J^T J, which the same launch fetches: k_post_eval)
   hipStream_t st = c->stream;
   LVX_HIP(c, hipMemsetAsync(w.sums + 4, 0, 8, st));
   // box constraints of a single sequence (w.constrained): the gradient norm is the projected one, at the state of the last evaluation
@@ -1356,8 +1359,7 @@ static int local_gmax(lvx_ctx* c, SolveWork& w, double* g, double* gsh) {   // (
   q.nbd_g = c->nbd - c->ns; q.tb = tb;
   const int tot = c->nb + c->nbd + q.nl;
   hipLaunchKernelGGL(k_post_eval, dim3((unsigned)std::min(RED_BLOCKS, (tot + 255) / 256)), dim3(256), 0, st, q);
-  // into the pinned words (lvx_ctx::pin); local_collect moves them to *g / gsh after the host stop
-  (void)g; (void)gsh;
+  // into the pinned words (lvx_ctx::pin); local_collect moves them to EvalLocal::gm / hg after the host stop
   if (!c->pin) { LVX_HIP(c, hipHostMalloc((void**)&c->pin, 128 * 8, hipHostMallocDefault)); std::memset(c->pin, 0, 128 * 8); }
   LVX_HIP(c, hipMemcpyAsync(c->pin + 24, w.sums + 4, 8, hipMemcpyDeviceToHost, st));
   if (c->ns > 0) LVX_HIP(c, hipMemcpyAsync(c->pin + 25, (const double*)c->d_gc.p + (c->nbd - c->ns), (size_t)c->ns * 8, hipMemcpyDeviceToHost, st));
@@ -1366,7 +1368,6 @@ static int local_gmax(lvx_ctx* c, SolveWork& w, double* g, double* gsh) {   // (
 // What follows a LVX_EVAL_NORMAL_EQ evaluation, in two halves so that the loop can put ONE collective between them.
 // local_after_eval: the diagonal of J^T J into w.diag (the LM damping in w.lmd — what the solver reads — is untouched until apply_diag), this rank's private
 // gradient max norm, and the shared entries of diagonal / gradient on the host.
-struct EvalLocal { double gm = 0.0; double hd[LVX_N_SHARED] = {0}, hg[LVX_N_SHARED] = {0}; double tau[2] = {0, 0}; bool have_tau = false; };   // tau: the (shared) sensor time offsets of a constrained joint solve
 // after the host stop behind local_after_eval's copies: the pinned words into *e
 static void local_collect(const lvx_ctx* c, EvalLocal* e) {
   e->gm = c->pin[24];
@@ -1376,9 +1377,7 @@ static void local_collect(const lvx_ctx* c, EvalLocal* e) {
 static int local_after_eval(lvx_ctx* c, SolveWork& w, EvalLocal* e, bool sync = true) {   // sync = false: queued only (the caller's next host stop completes the copies into *e)
   const int n = c->nb + c->nbd, ns = c->ns;
   hipStream_t st = c->stream;
-  const int nl = w.lm ? c->L : 0;   // landmark diagonal behind the band / border entries
-  (void)nl;
-  int rc = local_gmax(c, w, &e->gm, e->hg); if (rc) return rc;   // k_post_eval: the diagonal (band, border, landmarks behind them) and the gradient norm in one launch
+  int rc = local_gmax(c, w); if (rc) return rc;   // k_post_eval: the diagonal (band, border, landmarks behind them) and the gradient norm in one launch
   if (is_joint(c) && ns > 0) LVX_HIP(c, hipMemcpyAsync(c->pin + 50, w.diag + (n - ns), (size_t)ns * 8, hipMemcpyDeviceToHost, st));
   // (keyed on the LOCKS, which every rank shares — a rank whose own sequence has no block that makes it constrained must project the summed shared gradient
   // exactly as its peers do, or they disagree on gradient_tolerance convergence and part ways before the next collective)
@@ -1452,42 +1451,6 @@ static int post_eval(lvx_ctx* c, SolveWork& w, bool compute_scale, int use_scali
   return apply_diag(c, w, compute_scale, use_scaling, mn, mx, e, nullptr, grad_tol, grad_converged);
 }
 
-// ---- projected Armijo line search of a constrained problem (TrustRegionMinimizer::DoLineSearch; restated from Ceres' public sources, see oracle/lm.py) ----
-struct LsSample { double x, f, df; bool has_df; };
-// coefficients (highest power first) of the lowest-degree polynomial through the samples: Gaussian elimination with partial pivoting, the same operations as
-// oracle/lm.py::interpolating_polynomial
-static std::vector<double> poly_fit(const std::vector<LsSample>& sm) {
-  int n = 0; for (const auto& q : sm) n += 1 + (q.has_df ? 1 : 0);
-  std::vector<double> A((size_t)n * n, 0.0), b(n, 0.0);
-  int r = 0;
-  for (const auto& q : sm) {
-    for (int k = 0; k < n; ++k) A[(size_t)r * n + k] = std::pow(q.x, n - 1 - k);
-    b[r++] = q.f;
-    if (q.has_df) { for (int k = 0; k < n; ++k) A[(size_t)r * n + k] = (n - 1 - k > 0) ? (n - 1 - k) * std::pow(q.x, n - 2 - k) : 0.0; b[r++] = q.df; }
-  }
-  for (int k = 0; k < n; ++k) {
-    int piv = k; for (int i = k + 1; i < n; ++i) if (std::fabs(A[(size_t)i * n + k]) > std::fabs(A[(size_t)piv * n + k])) piv = i;
-    if (piv != k) { for (int j = 0; j < n; ++j) std::swap(A[(size_t)k * n + j], A[(size_t)piv * n + j]); std::swap(b[k], b[piv]); }
-    for (int i = k + 1; i < n; ++i) { const double m = A[(size_t)i * n + k] / A[(size_t)k * n + k]; for (int j = k; j < n; ++j) A[(size_t)i * n + j] -= m * A[(size_t)k * n + j]; b[i] -= m * b[k]; }
-  }
-  std::vector<double> c(n, 0.0);
-  for (int k = n - 1; k >= 0; --k) { double t = b[k]; for (int j = k + 1; j < n; ++j) t -= A[(size_t)k * n + j] * c[j]; c[k] = t / A[(size_t)k * n + k]; }
-  return c;
-}
-// argmin on [lo, hi]: 2001 uniform samples, then 60 golden-section steps on the best bracket (oracle/lm.py::minimize_polynomial)
-static double poly_argmin(const std::vector<double>& c, double lo, double hi) {
-  auto val = [&](double x) { double v = 0.0; for (double a : c) v = v * x + a; return v; };
-  const int n = 2000; double best = 0.0; int bi = 0;
-  for (int i = 0; i <= n; ++i) { const double v = val(lo + (hi - lo) * i / n); if (i == 0 || v < best) { best = v; bi = i; } }
-  double a = lo + (hi - lo) * std::max(bi - 1, 0) / n, b = lo + (hi - lo) * std::min(bi + 1, n) / n;
-  const double g = 0.6180339887498949;
-  double x1 = b - g * (b - a), x2 = a + g * (b - a), f1 = val(x1), f2 = val(x2);
-  for (int it = 0; it < 60; ++it) {
-    if (f1 <= f2) { b = x2; x2 = x1; f2 = f1; x1 = b - g * (b - a); f1 = val(x1); }
-    else { a = x1; x1 = x2; f1 = f2; x2 = a + g * (b - a); f2 = val(x2); }
-  }
-  return 0.5 * (a + b);
-}
 // g . delta with the gradient the accumulators hold now
 static int grad_dot(lvx_ctx* c, SolveWork& w, double* out) {
   hipStream_t st = c->stream;
@@ -1505,6 +1468,167 @@ struct HookScope {   // installs the all-reduce hook for the duration of one API
   HookScope(lvx_ctx* ctx, lvx_allreduce_fn fn, void* user) : c(ctx) { c->ar_fn = fn; c->ar_user = user; }
   ~HookScope() { c->ar_fn = nullptr; c->ar_user = nullptr; c->ns = 0; }
 };
+
+// ---- shared by lvx_calibration_covariance and lvx_calibration_covariance_shared ----
+// bit k: calibration scalar k is free
+static uint32_t calib_free_mask(const lvx_ctx* c) {
+  uint32_t m = 0;
+  for (int k = 0; k < LVX_NCAL; ++k) if (c->ord[6 * (size_t)c->N + k] != LVX_DEAD) m |= 1u << k;
+  return m;
+}
+template <class Rec> static void cov_free_index(uint32_t free_mask, Rec* out) {
+  for (int k = 0; k < LVX_NCAL; ++k) if (free_mask >> k & 1u) out->free_index[out->n_free++] = k;
+}
+// the record's tail words as a status: tail[0] the Jacobi off-diagonal ratio, [1] sweeps, [2] the eigen-solver's code, [3] band pivot code, [4] first hub pivot, [5] its
+// value; pivot_lost and min_eig are read where each call's record keeps them
+static int cov_status(lvx_ctx* c, const double* tail, bool pivot_lost, double min_eig) {
+  if (pivot_lost) return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string((int)tail[3]) + ", first hub pivot " + std::to_string((int)tail[4]) + " value " + std::to_string(tail[5]) + ")");
+  if (tail[2] == 2.0) return fail(c, LVX_E_NOTPD, "marginal information of the calibration scalars has a non-positive eigenvalue " + std::to_string(min_eig));
+  if (tail[2] != 0.0) { char buf[160]; snprintf(buf, sizeof buf, "Jacobi eigen-decomposition not converged after %d sweeps: max |t_pq| / sqrt(t_pp t_qq) = %.3e", (int)tail[1], tail[0]); return fail(c, LVX_E_NOTPD, buf); }
+  return LVX_OK;
+}
+
+// ---- the Levenberg-Marquardt driver: what lvx_lm_solve_shared's loop carries out.  Every decision that needs no device is lvx_lm_policy.h's ----
+struct LmRun {
+  lvx_ctx* c; SolveWork& w; const lvx_lm_options& o;
+  const bool joint;
+  bool ls_on = false;     // the joint problem (or this single sequence) is constrained: every rank runs the line-search protocol
+  double* x; double* xt;  // the iterate and the candidate (device)
+  hipStream_t st; const int N, L;
+  TrustRegion tr;
+  double cost = 0;
+  int it = 0;
+  int pending = LVX_OK;   // a local failure (restoring the normal equations of x) that has not met a collective yet: voted in the next R1
+  bool acc_is_x = true;   // the accumulators hold the normal equations of x (not of a candidate that was not accepted)
+  bool restored = false;  // a restore ran since the last collective: if the loop ends now, its outcome has not been voted on yet
+  lvx_lm_summary s{};
+  LmRun(lvx_ctx* c_, SolveWork& w_, const lvx_lm_options& o_)
+      : c(c_), w(w_), o(o_), joint(is_joint(c_)), x((double*)c_->d_state.p), xt((double*)c_->d_state_try.p), st(c_->stream), N(c_->N), L(c_->L), tr(o_) { s.termination = LVX_LM_NO_CONVERGENCE; }
+  // one entry of the history lvx_lm_get_history returns: accepted (1) / rejected or not applied (0) / invalid (-1)
+  void record(int flag) { c->lm_cost.push_back(cost); c->lm_radius.push_back(tr.radius); c->lm_accept.push_back(flag); }
+  // the accumulators hold the candidate's normal equations: put those of x back (no reduction: every rank takes this branch together)
+  void restore_x() { double cx = 0; const int re = lvx_evaluate_d(c, x, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cx); if (re && !pending) pending = re; acc_is_x = re == 0; restored = true; }
+};
+// a sum over the ranks whose last slot v[n - 1] carries the error vote: when a rank failed, all leave together.  Single sequence: nothing to sum, the error itself
+static int vote_sum(LmRun& r, double* v, int n, int err) {
+  if (!r.joint) return err;
+  v[n - 1] = err ? 1.0 : 0.0;
+  int rc = reduce(r.c, v, n, LVX_REDUCE_SUM); if (rc) return rc;
+  return leave_together(r.c, v[n - 1], err);
+}
+// x (+) w.delta -> dst, evaluated with cost (*f) AND normal equations: they replace those of x in the accumulators.  pre: an error the caller holds already (nothing is
+// queued then).  Inside the joint protocol a local error must meet a collective, so every failure is RETURNED for the caller to vote, never acted on here.
+//   h            the six sums k_plus leaves, cleared before and fetched after: step norm^2, x norm^2 over the free blocks, [4], [5] the shared blocks' halves of a joint
+//                solve; fetched for a point that cannot be evaluated too (the parameter-tolerance test reads the candidate's norms whatever its cost).  Null: neither
+//                cleared nor fetched (the start point's projection onto the box, whose norms nobody reads)
+//   unevaluable  set when the point cannot be evaluated (*f = INFINITY: a rejected step, not an error); null: that is an error like any other
+//   ev           the single sequence's hooked variant: what the loop wants on the host after the pass — its cost and error words, the sums, the candidate's diagonal and
+//                gradient norm (local_after_eval: used if the step is accepted) — arrives with ONE host stop: the copies and the small kernels are queued from inside the
+//                evaluation call, right before it waits (lvx_ctx::before_eval_sync).  *ev_done: they were.  The joint solve keeps its stops (its collectives sit between them)
+static int try_step(LmRun& r, double* dst, int pre, double* f, double* h, bool* unevaluable = nullptr, EvalLocal* ev = nullptr, bool* ev_done = nullptr) {
+  lvx_ctx* c = r.c; SolveWork& w = r.w;
+  if (pre) return pre;
+  if (h) LVX_HIP(c, hipMemsetAsync(w.sums + 2, 0, 48, r.st));
+  hipLaunchKernelGGL(k_plus, dim3((unsigned)((r.N + 1 + r.L + 255) / 256)), dim3(256), 0, r.st, (const double*)r.x, (const double*)w.delta, r.N, r.L, c->locks, dst, w.sums, (h && r.joint) ? 1 : 0,
+                     c->sensor_mto, w.tk ? w.tk + 7 : nullptr);
+  bool hooked = false; int hook_rc = LVX_OK;
+  if (ev) c->before_eval_sync = [&]() {
+    hooked = true; hook_rc = LVX_OK;
+    if (hipMemcpyAsync(c->pin + 16, w.sums + 2, 48, hipMemcpyDeviceToHost, r.st) != hipSuccess) hook_rc = LVX_E_HIP;
+    if (!hook_rc) hook_rc = local_after_eval(c, w, ev, false);
+  };
+  int le = lvx_evaluate_d(c, dst, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, f);
+  c->before_eval_sync = nullptr;
+  if (unevaluable) { *unevaluable = le == LVX_E_RANGE || le == LVX_E_NONUNIT_QUAT; if (*unevaluable) { *f = INFINITY; le = LVX_OK; } }
+  if (!le && hooked && hook_rc) le = hook_rc;
+  if (hooked && !hook_rc) { for (int q = 0; q < 6; ++q) h[q] = c->pin[16 + q]; local_collect(c, ev); }
+  if (h && !le && !hooked && hipMemcpy(h, w.sums + 2, 48, hipMemcpyDeviceToHost) != hipSuccess) le = LVX_E_HIP;
+  if (ev_done) *ev_done = hooked && !hook_rc;
+  return le;
+}
+static int ls_hip(lvx_ctx* c, hipError_t e) { return e == hipSuccess ? LVX_OK : fail(c, LVX_E_HIP, std::string("line search: ") + hipGetErrorString(e)); }
+// g . (the unscaled step dh) at the trial the accumulators hold: w.delta <- dh for the product, then back to the trial's scaled step dt
+static int grad_dot_unscaled(LmRun& r, const std::vector<double>& dh, const std::vector<double>& dt, double* ga) {
+  int le = ls_hip(r.c, hipMemcpyAsync(r.w.delta, dh.data(), dh.size() * 8, hipMemcpyHostToDevice, r.st));
+  if (!le) le = grad_dot(r.c, r.w, ga);
+  if (!le) le = ls_hip(r.c, hipMemcpyAsync(r.w.delta, dt.data(), dt.size() * 8, hipMemcpyHostToDevice, r.st));
+  return le;
+}
+// Projected Armijo line search along the trust-region step of a constrained problem (ArmijoSearch decides, this evaluates).  In: the candidate of the full step — its
+// cost *cand, its sums h, lerr its error so far — and g_delta = g . delta, the linear prediction.  Out: when a shorter step satisfies Armijo, w.delta (device) is that
+// step, xt, the accumulators, *cand and h belong to it; otherwise the full step stays (Ceres leaves delta alone) and its candidate is put back.  *searched: a pass ran
+// here, so what the candidate's own pass queued for local_after_eval is stale.
+// Joint solve: every quantity the search decides on is the SUM over the ranks (costs, directional derivatives), so every rank contracts by the same factor; payloads
+// {4, 2, 4 per trial, 1}, the last slot of each the error vote.  Inside the protocol a local HIP error is never returned: the peers would wait in the next reduction
+// for ever.  It is kept, voted in the next collective, and every rank leaves together.  Returns non-zero when the solve ends here.
+static int line_search(LmRun& r, double g_delta, int lerr, double* cand, double* h, bool* searched) {
+  lvx_ctx* c = r.c; SolveWork& w = r.w;
+  int rc;
+  double cand_g = *cand, m0_g = g_delta;
+  if (r.joint) {   // decide together: the candidate's JOINT cost against the joint linear prediction
+    double b4[4] = {std::isfinite(*cand) ? *cand : 0.0, g_delta, std::isfinite(*cand) ? 0.0 : 1.0, 0.0};
+    if (lerr) { b4[0] = b4[1] = b4[2] = 0.0; }
+    if ((rc = vote_sum(r, b4, 4, lerr))) return rc;
+    cand_g = b4[2] > 0.0 ? INFINITY : b4[0]; m0_g = b4[1];
+  } else if (lerr) return LVX_OK;   // (the caller returns it)
+  if (!ArmijoSearch::needed(r.cost, cand_g, m0_g)) return LVX_OK;
+  *searched = true;
+  double g1 = 0.0;
+  { int le = grad_dot(c, w, &g1); double b2[2] = {le ? 0.0 : g1, 0.0}; if ((rc = vote_sum(r, b2, 2, le))) return rc; g1 = b2[0]; }
+  const int ntg = lvx_tangent_size(c);
+  std::vector<double> dh((size_t)ntg), dt((size_t)ntg);   // the full step, the trial's step
+  int hip_ls = ls_hip(c, hipMemcpyAsync(dh.data(), w.delta, (size_t)ntg * 8, hipMemcpyDeviceToHost, r.st));
+  if (!hip_ls) hip_ls = ls_hip(c, hipStreamSynchronize(r.st));
+  // ArmijoLineSearch measures the step against ||direction||_inf; joint: the norm of the JOINT step (max over the ranks; the second slot carries the vote of a rank that failed)
+  double dinf = 0.0;
+  for (int i = 0; i < ntg; ++i) dinf = std::max(dinf, std::fabs(dh[i]));
+  if (r.joint) {
+    double dv[2] = {dinf, hip_ls ? 1.0 : 0.0};
+    if ((rc = reduce(c, dv, 2, LVX_REDUCE_MAX))) return rc;
+    if ((rc = leave_together(c, dv[1], hip_ls))) return rc;
+    dinf = dv[0];
+  } else if (hip_ls) return hip_ls;
+  ArmijoSearch ls(r.cost, m0_g, cand_g, g1, dinf);
+  bool found = false;
+  for (double a = 1.0;;) {
+    const int fitted = ls.trial;
+    const bool go = ls.next(&a);
+    if (r.o.verbose && ls.trial != fitted) fprintf(stderr, "[lvx lm] it %3d line search trial %d: f0 %.12e g0 %.12e | last step %.6e f %.12e df %.12e -> step %.12e\n", r.it, ls.trial, ls.f0, ls.g0, ls.cur.x, ls.cur.f, ls.cur.df, a);
+    if (!go) break;
+    for (int i = 0; i < ntg; ++i) dt[i] = a * dh[i];
+    double f = 0, ga = 0.0, htr[6] = {0, 0, 0, 0, 0, 0};
+    bool bad = false;   // a trial that cannot be evaluated: contract again without a new sample
+    int le = try_step(r, r.xt, ls_hip(c, hipMemcpyAsync(w.delta, dt.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, r.st)), &f, htr, &bad);
+    // the directional derivative along the UNSCALED step is needed only when the trial fails Armijo.  Joint: taken with every trial, its sum rides on the trial's one
+    // reduction; single sequence: taken AFTER the test, by the trials that fail it — two copies of the step, a k_gdot launch and a stream sync less per accepted trial
+    if (r.joint && !le && !bad) le = grad_dot_unscaled(r, dh, dt, &ga);
+    double b4[4] = {(le || bad) ? 0.0 : f, (le || bad) ? 0.0 : ga, bad ? 1.0 : 0.0, 0.0};
+    if ((rc = vote_sum(r, b4, 4, le))) return rc;
+    if (r.joint) bad = b4[2] > 0.0;
+    if (!r.joint && !bad && !ls.armijo(b4[0]) && (rc = grad_dot_unscaled(r, dh, dt, &b4[1]))) return rc;
+    if (ls.report(b4[0], b4[1], bad)) { *cand = f; for (int q = 0; q < 6; ++q) h[q] = htr[q]; found = true; break; }
+  }
+  if (!found) {   // no step satisfies Armijo: the full step stays — put its candidate back
+    const int re = try_step(r, r.xt, ls_hip(c, hipMemcpyAsync(w.delta, dh.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, r.st)), cand, h);
+    double b1[1] = {0.0};
+    if ((rc = vote_sum(r, b1, 1, re))) return rc;
+  }
+  return LVX_OK;
+}
+// R2, the joint solve's one reduction behind the candidate: the private blocks' terms summed over the ranks, the shared blocks' norms (identical on every rank: h[4],
+// h[5]) added once.  r2: [g.delta, delta^T H delta, y^T D^2 y, candidate cost, step norm^2, x norm^2, error votes | the candidate's joint block].  Single sequence: nothing
+// to reduce, the error itself
+static int reduce_candidate(LmRun& r, int lerr, const EvalLocal& ev, const double* h, double* r2) {
+  if (!r.joint) return lerr;
+  int rc;
+  r2[6] = lerr ? 1.0 : 0.0;
+  if (lerr) { r2[0] = r2[1] = r2[2] = r2[3] = r2[4] = r2[5] = 0.0; for (int i = 0; i < LVX_JB_N; ++i) r2[7 + i] = 0.0; }
+  else joint_block_pack(r.c, ev, r.o.gradient_tolerance, r2 + 7);
+  if ((rc = reduce(r.c, r2, 7 + LVX_JB_N, LVX_REDUCE_SUM))) return rc;
+  if ((rc = leave_together(r.c, r2[6], lerr))) return rc;
+  r2[4] += h[4]; r2[5] += h[5];
+  return LVX_OK;
+}
 
 extern "C" {
 
@@ -1561,8 +1685,7 @@ int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx
   EvalLocal e; bool gconv = false;
   if ((rc = local_after_eval(c, w, &e, false))) return rc;   // the diagonal of THIS evaluation (queued; nothing of *e is used)
   if ((rc = apply_diag(c, w, true, opt->jacobi_scaling, 1e-6, 1e32, e, nullptr, 0.0, &gconv))) return rc;
-  uint32_t free_mask = 0;
-  for (int k = 0; k < LVX_NCAL; ++k) if (c->ord[6 * (size_t)c->N + k] != LVX_DEAD) free_mask |= 1u << k;
+  const uint32_t free_mask = calib_free_mask(c);
   std::vector<double> h(LVX_CCOV_N);
   StageTimer tm(c);
   const size_t lds = (size_t)nbd * (nbd + 1) * 8;
@@ -1584,11 +1707,9 @@ int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx
     ++c->solver_fallbacks;
     if ((rc = run(true, &bcr_used))) return rc;
   }
-  if (tail[3] != 0.0 || tail[4] != 0.0) return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string((int)tail[3]) + ", first hub pivot " + std::to_string((int)tail[4]) + " value " + std::to_string(tail[5]) + ")");
-  if (tail[2] == 2.0) return fail(c, LVX_E_NOTPD, "marginal information of the calibration scalars has a non-positive eigenvalue " + std::to_string(h[LVX_NCAL * LVX_NCAL + LVX_NCAL]));
-  if (tail[2] != 0.0) { char buf[160]; snprintf(buf, sizeof buf, "Jacobi eigen-decomposition not converged after %d sweeps: max |t_pq| / sqrt(t_pp t_qq) = %.3e", (int)tail[1], tail[0]); return fail(c, LVX_E_NOTPD, buf); }
+  if ((rc = cov_status(c, tail, tail[3] != 0.0 || tail[4] != 0.0, h[LVX_NCAL * LVX_NCAL + LVX_NCAL]))) return rc;
   std::memset(out, 0, sizeof *out);
-  for (int k = 0; k < LVX_NCAL; ++k) if (free_mask >> k & 1u) out->free_index[out->n_free++] = k;
+  cov_free_index(free_mask, out);
   const double* p = h.data();
   std::memcpy(out->cov, p, sizeof out->cov); p += LVX_NCAL * LVX_NCAL;
   std::memcpy(out->sigma, p, sizeof out->sigma); p += LVX_NCAL;
@@ -1623,8 +1744,7 @@ int lvx_calibration_covariance_shared(lvx_ctx* c, const lvx_calib_cov_options* o
   if (no_eval > 0.0) return lerr == LVX_E_STATE ? lerr : fail(c, LVX_E_STATE, "lvx_calibration_covariance_shared: a rank of the joint problem has no preceding LVX_EVAL_NORMAL_EQ evaluation");
   if (rc) return rc;
   hipStream_t st = c->stream;
-  uint32_t free_mask = 0;
-  for (int k = 0; k < LVX_NCAL; ++k) if (c->ord[6 * (size_t)c->N + k] != LVX_DEAD) free_mask |= 1u << k;
+  const uint32_t free_mask = calib_free_mask(c);
   double* rec = (double*)c->d_ccov.p, *keep = rec + LVX_JREC_N;
   double* msg = c->rccl_comm ? (double*)c->d_comm.p : keep + LVX_JKEEP_N;   // RCCL reduces in its staging buffer; the callback's message is staged through the host
   JointLmd lmd{};
@@ -1662,11 +1782,9 @@ int lvx_calibration_covariance_shared(lvx_ctx* c, const lvx_calib_cov_options* o
     if ((rc = run(true, &bcr_used))) return rc;
   }
   if (tail[2] == 3.0) return fail(c, LVX_E_ARG, "lvx_calibration_covariance_shared: a shared extrinsic scalar is locked on some ranks and free on others");
-  if (tail[7] > 0.0) return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string((int)tail[3]) + ", first hub pivot " + std::to_string((int)tail[4]) + " value " + std::to_string(tail[5]) + ")");
-  if (tail[2] == 2.0) return fail(c, LVX_E_NOTPD, "marginal information of the calibration scalars has a non-positive eigenvalue " + std::to_string(h[LVX_JREC_W]));
-  if (tail[2] != 0.0) { char buf[160]; snprintf(buf, sizeof buf, "Jacobi eigen-decomposition not converged after %d sweeps: max |t_pq| / sqrt(t_pp t_qq) = %.3e", (int)tail[1], tail[0]); return fail(c, LVX_E_NOTPD, buf); }
+  if ((rc = cov_status(c, tail, tail[7] > 0.0, h[LVX_JREC_W]))) return rc;
   std::memset(out, 0, sizeof *out);
-  for (int k = 0; k < LVX_NCAL; ++k) if (free_mask >> k & 1u) out->free_index[out->n_free++] = k;
+  cov_free_index(free_mask, out);
   for (int a = 0; a < LVX_N_SHARED; ++a) if (free_mask >> (LVX_NPRIV + a) & 1u) out->shared_free_slot[out->n_shared_free++] = a;
   std::memcpy(out->cov, h.data() + LVX_JREC_COV, sizeof out->cov);
   std::memcpy(out->sigma, h.data() + LVX_JREC_SIG, sizeof out->sigma);
@@ -1704,222 +1822,87 @@ int lvx_lm_solve_shared(lvx_ctx* c, double* state, const lvx_lm_options* opt_in,
   w.constrained = !lerr && (free_rho || free_tau);   // this rank's own view: its start point and its private gradient entries are projected
   double cons_votes = w.constrained ? 1.0 : 0.0;
   if (!lerr && !joint && w.lm && c->nb > 0) { w.inplace = true; w.Hs = (const double*)c->d_Hb.p; w.Bs = (const double*)c->d_Bd.p; c->p_Hs = w.Hs; }
-  hipStream_t st = c->stream;
   const size_t sbytes = (size_t)lvx_state_size(c) * 8;
-  double* x = (double*)c->d_state.p;
-  double* xt = (double*)c->d_state_try.p;
   c->lm_cost.clear(); c->lm_radius.clear(); c->lm_accept.clear();
-  lvx_lm_summary s{}; s.termination = LVX_LM_NO_CONVERGENCE;
-  double cost = 0; bool gconv = false;
+  LmRun r(c, w, o);
+  lvx_lm_summary& s = r.s;
+  bool gconv = false;
   if (!lerr) {
-    LVX_HIP(c, hipMemcpyAsync(x, state, sbytes, hipMemcpyHostToDevice, st));
+    LVX_HIP(c, hipMemcpyAsync(r.x, state, sbytes, hipMemcpyHostToDevice, r.st));
     if (w.constrained) {   // TrustRegionMinimizer::IterationZero: x <- Plus(x, 0), the start point projected onto the box
-      LVX_HIP(c, hipMemsetAsync(w.delta, 0, (size_t)lvx_tangent_size(c) * 8, st));
-      hipLaunchKernelGGL(k_plus, dim3((unsigned)((c->N + 1 + c->L + 255) / 256)), dim3(256), 0, st, (const double*)x, (const double*)w.delta, c->N, c->L, c->locks, x, w.sums, 0, c->sensor_mto, w.tk ? w.tk + 7 : nullptr);
-    }
-    lerr = lvx_evaluate_d(c, x, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cost);
+      LVX_HIP(c, hipMemsetAsync(w.delta, 0, (size_t)lvx_tangent_size(c) * 8, r.st));
+      lerr = try_step(r, r.x, LVX_OK, &r.cost, nullptr);
+    } else lerr = lvx_evaluate_d(c, r.x, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &r.cost);
   }
-  if ((rc = post_eval(c, w, true, o.jacobi_scaling, o.min_lm_diagonal, o.max_lm_diagonal, &cost, o.gradient_tolerance, &gconv, lerr, &cons_votes))) return rc;
-  const bool ls_on = cons_votes > 0.0;   // the joint problem (or this single sequence) is constrained: every rank runs the line-search protocol
-  s.initial_cost = cost;
-  double radius = o.initial_radius, decrease_factor = 2.0;
-  int invalid = 0;
-  const int N = c->N, L = c->L;
+  if ((rc = post_eval(c, w, true, o.jacobi_scaling, o.min_lm_diagonal, o.max_lm_diagonal, &r.cost, o.gradient_tolerance, &gconv, lerr, &cons_votes))) return rc;
+  r.ls_on = cons_votes > 0.0;
+  s.initial_cost = r.cost;
   if (gconv) { s.termination = LVX_LM_GRADIENT_TOLERANCE; }
-  int it = 0;
-  int pending = LVX_OK;   // a local failure (restoring the normal equations of x) that has not met a collective yet: voted in the next R1
-  bool acc_is_x = true;   // the accumulators hold the normal equations of x (not of a candidate that was not accepted)
-  // the accumulators hold the candidate's normal equations: put those of x back (no reduction: every rank takes this branch together)
-  bool restored = false;  // a restore ran since the last collective: if the loop ends now, its outcome has not been voted on yet
-  auto restore_x = [&]() { double cx = 0; const int re = lvx_evaluate_d(c, x, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cx); if (re && !pending) pending = re; acc_is_x = re == 0; restored = true; };
+  // oracle/lm.py::lm_solve, line for line: solve, try the step, search if constrained, reduce, classify, act
   while (s.termination == LVX_LM_NO_CONVERGENCE) {
-    if (it >= o.max_iterations) { s.termination = LVX_LM_MAX_ITERATIONS; break; }
-    ++it;
+    if (r.it >= o.max_iterations) { s.termination = LVX_LM_MAX_ITERATIONS; break; }
+    ++r.it;
     double m[3]; bool notpd = false;
-    if ((rc = solve_step_device(c, w, radius, m, &notpd, pending))) return rc;
-    pending = LVX_OK; restored = false;
-    if (w.inplace) acc_is_x = false;   // the landmark elimination ran on the band / border rows themselves
+    if ((rc = solve_step_device(c, w, r.tr.radius, m, &notpd, r.pending))) return rc;
+    r.pending = LVX_OK; r.restored = false;
+    if (w.inplace) r.acc_is_x = false;   // the landmark elimination ran on the band / border rows themselves
     // candidate x (+) delta: cost AND normal equations (they replace those of x in the accumulators; the model terms of x were taken by solve_step_device)
     double r2[7 + LVX_JB_N] = {m[0], m[1], m[2], 0, 0, 0, 0}, h[6] = {0, 0, 0, 0, 0, 0};
     lerr = LVX_OK;
     bool cand_ne = false;
     EvalLocal ev;
     if (!notpd) {
-      LVX_HIP(c, hipMemsetAsync(w.sums + 2, 0, 48, st));
-      hipLaunchKernelGGL(k_plus, dim3((unsigned)((N + 1 + L + 255) / 256)), dim3(256), 0, st, (const double*)x, (const double*)w.delta, N, L, c->locks, xt, w.sums, joint ? 1 : 0, c->sensor_mto, w.tk ? w.tk + 7 : nullptr);
       double cand = 0;
-      // Single sequence: what the loop wants on the host after the candidate's pass — its cost and error words, the step norms k_plus left in w.sums, the candidate's
-      // diagonal and gradient norm (local_after_eval: used if the step is accepted) — arrives with ONE host stop: the copies and the small kernels are queued from inside
-      // the evaluation call, right before it waits (lvx_ctx::before_eval_sync).  The joint solve keeps its stops (its collectives sit between them).
-      bool hooked = false; int hook_rc = LVX_OK;
-      if (!joint) c->before_eval_sync = [&]() {
-        hooked = true; hook_rc = LVX_OK;
-        if (hipMemcpyAsync(c->pin + 16, w.sums + 2, 48, hipMemcpyDeviceToHost, st) != hipSuccess) hook_rc = LVX_E_HIP;
-        if (!hook_rc) hook_rc = local_after_eval(c, w, &ev, false);
-      };
-      const int re = lvx_evaluate_d(c, xt, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cand);
-      c->before_eval_sync = nullptr;
-      cand_ne = true; acc_is_x = false;
-      if (re == LVX_E_RANGE || re == LVX_E_NONUNIT_QUAT) cand = INFINITY; else if (re) lerr = re;   // a candidate that cannot be evaluated is a rejected step, anything else an error
-      if (!lerr && hooked && hook_rc) lerr = hook_rc;
-      if (hooked && !hook_rc) { for (int q = 0; q < 6; ++q) h[q] = c->pin[16 + q]; local_collect(c, &ev); }
-      if (!lerr && !hooked && hipMemcpy(h, w.sums + 2, 48, hipMemcpyDeviceToHost) != hipSuccess) lerr = LVX_E_HIP;
-      bool ev_done = hooked && !hook_rc;   // (a line search below evaluates again: its last pass is what local_after_eval must see)
-      // projected Armijo line search (constrained problem): the full step stays when it decreases the cost by 1e-4 of the linear prediction — the rule.  Joint solve:
-      // every quantity the search decides on is the SUM over the ranks (costs, directional derivatives); a rank that fails votes and all leave together.
-      auto jsum = [&](double* v, int n, int err) -> int {   // v[n - 1] is the vote slot
-        if (!joint) return err;
-        v[n - 1] = err ? 1.0 : 0.0;
-        int r_ = reduce(c, v, n, LVX_REDUCE_SUM); if (r_) return r_;
-        return leave_together(c, v[n - 1], err);
-      };
-      double cand_g = cand, m0_g = m[0];
-      if (ls_on && joint) {   // decide together: the candidate's JOINT cost against the joint linear prediction
-        double b4[4] = {std::isfinite(cand) ? cand : 0.0, m[0], std::isfinite(cand) ? 0.0 : 1.0, 0.0};
-        if (lerr) { b4[0] = b4[1] = b4[2] = 0.0; }
-        if ((rc = jsum(b4, 4, lerr))) return rc;
-        cand_g = b4[2] > 0.0 ? INFINITY : b4[0]; m0_g = b4[1];
-      }
-      if (!lerr && ls_on && std::isfinite(cand_g) && m0_g < 0.0 && cand_g > cost + 1e-4 * m0_g) {
-        ev_done = false;   // the search evaluates again: the diagonal / gradient norm queued with the full step's pass are not the accepted point's
-        const double f0 = cost, g0 = m0_g;
-        double g1 = 0.0;
-        { int le = grad_dot(c, w, &g1); double b2[2] = {le ? 0.0 : g1, 0.0}; if ((rc = jsum(b2, 2, le))) return rc; g1 = b2[0]; }
-        LsSample prev{0, 0, 0, false}, cur{1.0, cand_g, g1, true};
-        bool have_prev = false, found = false;
-        double alpha = 1.0, fa = cand, ha[6] = {h[0], h[1], 0, 0, h[4], h[5]};
-        const int ntg = lvx_tangent_size(c);
-        std::vector<double> dh((size_t)ntg);
-        //  inside the joint protocol a local HIP error must not `return`: the peers would wait in the next reduction for ever.  It is kept (hip_ls), voted in
-        // the next collective, and every rank leaves together.
-        int hip_ls = LVX_OK;
-        auto hip_keep = [&](hipError_t e) { if (e != hipSuccess && !hip_ls) hip_ls = fail(c, LVX_E_HIP, std::string("line search: ") + hipGetErrorString(e)); };
-        hip_keep(hipMemcpyAsync(dh.data(), w.delta, (size_t)ntg * 8, hipMemcpyDeviceToHost, st));
-        hip_keep(hipStreamSynchronize(st));
-        std::vector<double> dt((size_t)ntg);
-        // ArmijoLineSearch gives up when step * ||direction||_inf < min_line_search_step_size (1e-9); joint: the norm of the JOINT step (max over the ranks; the second
-        // slot carries the vote of a rank that failed)
-        double dinf = 0.0;
-        for (int i = 0; i < ntg; ++i) dinf = std::max(dinf, std::fabs(dh[i]));
-        if (joint) {
-          double dv[2] = {dinf, hip_ls ? 1.0 : 0.0};
-          if ((rc = reduce(c, dv, 2, LVX_REDUCE_MAX))) return rc;
-          if ((rc = leave_together(c, dv[1], hip_ls))) return rc;
-          dinf = dv[0];
-        } else if (hip_ls) return hip_ls;
-        for (int trial = 1; trial <= 20 && !found; ++trial) {
-          std::vector<LsSample> sm{{0.0, f0, g0, true}};
-          if (have_prev) sm.push_back(prev);
-          sm.push_back(cur);
-          const double a = poly_argmin(poly_fit(sm), 1e-3 * cur.x, 0.6 * cur.x);
-          if (o.verbose) fprintf(stderr, "[lvx lm] it %3d line search trial %d: f0 %.12e g0 %.12e | last step %.6e f %.12e df %.12e -> step %.12e\n", it, trial, f0, g0, cur.x, cur.f, cur.df, a);
-          if (a * dinf < 1e-9) break;
-          for (int i = 0; i < ntg; ++i) dt[i] = a * dh[i];
-          int le = LVX_OK;
-          hip_ls = LVX_OK;
-          hip_keep(hipMemcpyAsync(w.delta, dt.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, st));
-          hip_keep(hipMemsetAsync(w.sums + 2, 0, 48, st));
-          le = hip_ls;
-          if (!le) hipLaunchKernelGGL(k_plus, dim3((unsigned)((N + 1 + L + 255) / 256)), dim3(256), 0, st, (const double*)x, (const double*)w.delta, N, L, c->locks, xt, w.sums, joint ? 1 : 0, c->sensor_mto, w.tk ? w.tk + 7 : nullptr);
-          double f = 0, ga = 0.0, htr[6] = {0, 0, 0, 0, 0, 0};
-          if (!le) le = lvx_evaluate_d(c, xt, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &f);
-          bool bad = le == LVX_E_RANGE || le == LVX_E_NONUNIT_QUAT;   // a trial that cannot be evaluated: contract again without a new sample
-          if (bad) le = LVX_OK;
-          if (!le && !bad && hipMemcpy(htr, w.sums + 2, 48, hipMemcpyDeviceToHost) != hipSuccess) le = LVX_E_HIP;
-          // the directional derivative along the UNSCALED step is needed only when the trial fails Armijo.  Joint: taken with every trial, its sum rides on the trial's one
-          // reduction; single sequence: taken AFTER the test, by the trials that fail it — two copies of the step, a k_gdot launch and a stream sync less per
-          // accepted trial
-          auto take_ga = [&]() {
-            hip_ls = LVX_OK;
-            hip_keep(hipMemcpyAsync(w.delta, dh.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, st));
-            if (!hip_ls) le = grad_dot(c, w, &ga); else le = hip_ls;
-            if (!le) { hip_keep(hipMemcpyAsync(w.delta, dt.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, st)); le = hip_ls; }   // delta (device) stays the scaled step of this trial
-          };
-          if (joint && !le && !bad) take_ga();
-          double f_g = f, ga_g = ga;
-          if (joint) {
-            double b4[4] = {(le || bad) ? 0.0 : f, (le || bad) ? 0.0 : ga, bad ? 1.0 : 0.0, 0.0};
-            if ((rc = jsum(b4, 4, le))) return rc;
-            f_g = b4[0]; ga_g = b4[1]; bad = b4[2] > 0.0;
-          } else if (le) return le;
-          if (bad) { cur.x = a; continue; }
-          if (f_g <= f0 + 1e-4 * a * g0) {
-            for (int q = 0; q < 6; ++q) ha[q] = htr[q];
-            alpha = a; fa = f; found = true; break;
-          }
-          if (!joint) { take_ga(); if (le) return le; ga_g = ga; }
-          prev = cur; have_prev = true; cur = LsSample{a, f_g, ga_g, true};
-        }
-        if (found) { cand = fa; for (int q = 0; q < 6; ++q) h[q] = ha[q]; }   // delta (device) = alpha x the trust-region step, xt and the accumulators belong to it
-        else {   // no step satisfies Armijo: the full step stays (Ceres leaves delta alone) — put its candidate back
-          hip_ls = LVX_OK;
-          hip_keep(hipMemcpyAsync(w.delta, dh.data(), (size_t)ntg * 8, hipMemcpyHostToDevice, st));
-          hip_keep(hipMemsetAsync(w.sums + 2, 0, 48, st));
-          if (!hip_ls) hipLaunchKernelGGL(k_plus, dim3((unsigned)((N + 1 + L + 255) / 256)), dim3(256), 0, st, (const double*)x, (const double*)w.delta, N, L, c->locks, xt, w.sums, joint ? 1 : 0, c->sensor_mto, w.tk ? w.tk + 7 : nullptr);
-          int re3 = hip_ls ? hip_ls : lvx_evaluate_d(c, xt, LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cand);
-          if (!re3 && hipMemcpy(h, w.sums + 2, 48, hipMemcpyDeviceToHost) != hipSuccess) re3 = LVX_E_HIP;
-          if (joint) { double b1[1] = {0.0}; if ((rc = jsum(b1, 1, re3))) return rc; } else if (re3) return re3;
-        }
-        (void)alpha;
-      }
-      if (!lerr && std::isfinite(cand) && !ev_done) lerr = local_after_eval(c, w, &ev);   // the candidate's diagonal / gradient: used if the step is accepted (w.lmd, the damping of x, stays)
+      bool unevaluable = false, ev_done = false, searched = false;   // (unevaluable: cand = INFINITY, a rejected step)
+      lerr = try_step(r, r.xt, LVX_OK, &cand, h, &unevaluable, joint ? nullptr : &ev, &ev_done);
+      cand_ne = true; r.acc_is_x = false;
+      if (r.ls_on && (rc = line_search(r, m[0], lerr, &cand, h, &searched))) return rc;
+      if (!lerr && std::isfinite(cand) && (searched || !ev_done)) lerr = local_after_eval(c, w, &ev);   // the candidate's diagonal / gradient: used if the step is accepted (w.lmd, the damping of x, stays)
       r2[3] = cand; r2[4] = h[0]; r2[5] = h[1];
     }
-    if (joint) {   // private blocks summed over the ranks; the shared blocks (identical on every rank) are counted once below
-      r2[6] = lerr ? 1.0 : 0.0;
-      if (lerr) { r2[0] = r2[1] = r2[2] = r2[3] = r2[4] = r2[5] = 0.0; for (int i = 0; i < LVX_JB_N; ++i) r2[7 + i] = 0.0; }
-      else joint_block_pack(c, ev, o.gradient_tolerance, r2 + 7);
-      if ((rc = reduce(c, r2, 7 + LVX_JB_N, LVX_REDUCE_SUM))) return rc;
-      if ((rc = leave_together(c, r2[6], lerr))) return rc;
-      r2[4] += h[4]; r2[5] += h[5];
-    } else if (lerr) return lerr;
+    if ((rc = reduce_candidate(r, lerr, ev, h, r2))) return rc;
     const double model = -r2[0] - 0.5 * r2[1], cand = r2[3];
-    const bool step_valid = !notpd && std::isfinite(model) && model > 0.0;
-    if (!step_valid && o.verbose) fprintf(stderr, "[lvx lm] it %3d invalid step: %s model_cost_change %.6e g.delta %.6e\n", it, notpd ? "not positive definite" : "model", model, r2[0]);
-    if (!step_valid) {   // TrustRegionMinimizer::HandleInvalidStep + LevenbergMarquardtStrategy::StepIsInvalid
-      if (++invalid >= 5) { s.termination = LVX_LM_FAILURE; break; }   // max_num_consecutive_invalid_steps = 5
-      radius *= 0.5;
-      c->lm_cost.push_back(cost); c->lm_radius.push_back(radius); c->lm_accept.push_back(-1);
-      if (cand_ne || w.inplace) restore_x();
+    if (!TrustRegion::step_valid(notpd, model)) {   // TrustRegionMinimizer::HandleInvalidStep + LevenbergMarquardtStrategy::StepIsInvalid
+      if (o.verbose) fprintf(stderr, "[lvx lm] it %3d invalid step: %s model_cost_change %.6e g.delta %.6e\n", r.it, notpd ? "not positive definite" : "model", model, r2[0]);
+      if (!r.tr.StepIsInvalid()) { s.termination = LVX_LM_FAILURE; break; }
+      r.record(-1);
+      if (cand_ne || w.inplace) r.restore_x();
       continue;
     }
-    invalid = 0;
-    const double step_norm = std::sqrt(r2[4]), x_norm = std::sqrt(r2[5]);
-    if (step_norm <= o.parameter_tolerance * (x_norm + o.parameter_tolerance)) { s.termination = LVX_LM_PARAMETER_TOLERANCE; c->lm_cost.push_back(cost); c->lm_radius.push_back(radius); c->lm_accept.push_back(0); break; }
-    const double cost_change = cost - cand;
-    if (std::fabs(cost_change) <= o.function_tolerance * cost) {
-      // FunctionToleranceReached is tested before the step is accepted or rejected and returns without applying it (trust_region_minimizer.cc)
-      s.termination = LVX_LM_FUNCTION_TOLERANCE; c->lm_cost.push_back(cost); c->lm_radius.push_back(radius); c->lm_accept.push_back(0); break;
+    double rho;
+    const StepVerdict verdict = r.tr.classify(r.cost, cand, model, std::sqrt(r2[4]), std::sqrt(r2[5]), &rho);
+    if (verdict == STEP_PARAMETER_TOLERANCE || verdict == STEP_FUNCTION_TOLERANCE) {   // tested before the step is accepted or rejected: the solve returns without applying it (trust_region_minimizer.cc)
+      s.termination = verdict == STEP_PARAMETER_TOLERANCE ? LVX_LM_PARAMETER_TOLERANCE : LVX_LM_FUNCTION_TOLERANCE;
+      r.record(0);
+      break;
     }
-    const double rho = cost_change / model;
-    if (rho > o.min_relative_decrease) {
-      std::swap(c->d_state.p, c->d_state_try.p); x = (double*)c->d_state.p; xt = (double*)c->d_state_try.p;
-      cost = cand; s.successful_steps++; acc_is_x = true;
+    if (verdict == STEP_ACCEPT) {
+      std::swap(c->d_state.p, c->d_state_try.p); r.x = (double*)c->d_state.p; r.xt = (double*)c->d_state_try.p;
+      r.cost = cand; s.successful_steps++; r.acc_is_x = true;
       bool gc = false;
       if ((rc = apply_diag(c, w, false, o.jacobi_scaling, o.min_lm_diagonal, o.max_lm_diagonal, ev, joint ? r2 + 7 : nullptr, o.gradient_tolerance, &gc))) return rc;
-      radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rho - 1.0, 3));   // LevenbergMarquardtStrategy::StepAccepted
-      radius = std::min(o.max_radius, radius); decrease_factor = 2.0;
-      c->lm_cost.push_back(cost); c->lm_radius.push_back(radius); c->lm_accept.push_back(1);
+      r.tr.StepAccepted(rho);
+      r.record(1);
       if (gc) { s.termination = LVX_LM_GRADIENT_TOLERANCE; break; }
     } else {
-      radius = radius / decrease_factor; decrease_factor *= 2.0;      // StepRejected (the LM diagonal of x is reused)
-      c->lm_cost.push_back(cost); c->lm_radius.push_back(radius); c->lm_accept.push_back(0);
-      if (radius < o.min_radius) { s.termination = LVX_LM_MIN_RADIUS; break; }   // Ceres: CONVERGENCE, "minimum trust region radius reached"
-      restore_x();
+      const bool above_min = r.tr.StepRejected();   // (the LM diagonal of x is reused)
+      r.record(0);
+      if (!above_min) { s.termination = LVX_LM_MIN_RADIUS; break; }
+      r.restore_x();
     }
-    if (o.verbose) fprintf(stderr, "[lvx lm] it %3d cost %.9e radius %.3e rho %.3f\n", it, cost, radius, rho);
+    if (o.verbose) fprintf(stderr, "[lvx lm] it %3d cost %.9e radius %.3e rho %.3f\n", r.it, r.cost, r.tr.radius, rho);
   }
-  s.iterations = it; s.final_cost = cost; s.final_radius = radius;
-  if (joint && restored) {   // the loop ended (iteration cap) right behind a rejected step: every rank is here (same decisions), the restore's outcome is voted so that all return together
-    double v = pending ? 1.0 : 0.0;
+  s.iterations = r.it; s.final_cost = r.cost; s.final_radius = r.tr.radius;
+  if (joint && r.restored) {   // the loop ended (iteration cap) right behind a rejected step: every rank is here (same decisions), the restore's outcome is voted so that all return together
+    double v = r.pending ? 1.0 : 0.0;
     if ((rc = reduce(c, &v, 1, LVX_REDUCE_SUM))) return rc;
-    if ((rc = leave_together(c, v, pending))) return rc;
+    if ((rc = leave_together(c, v, r.pending))) return rc;
   }
-  if (!acc_is_x) c->last_what &= ~LVX_EVAL_NORMAL_EQ;   // a tolerance test ended the loop on a candidate that was not applied: its normal equations are not those of the returned state
-  LVX_HIP(c, hipMemcpyAsync(state, x, sbytes, hipMemcpyDeviceToHost, st));
-  LVX_HIP(c, hipStreamSynchronize(st));
+  if (!r.acc_is_x) c->last_what &= ~LVX_EVAL_NORMAL_EQ;   // a tolerance test ended the loop on a candidate that was not applied: its normal equations are not those of the returned state
+  LVX_HIP(c, hipMemcpyAsync(state, r.x, sbytes, hipMemcpyDeviceToHost, r.st));
+  LVX_HIP(c, hipStreamSynchronize(r.st));
   if (sum) *sum = s;
-  return pending ? pending : LVX_OK;
+  return r.pending ? r.pending : LVX_OK;
 }
 int lvx_lm_solve(lvx_ctx* c, double* state, const lvx_lm_options* opt_in, lvx_lm_summary* sum) {
   return lvx_lm_solve_shared(c, state, opt_in, nullptr, nullptr, sum);

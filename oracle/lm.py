@@ -27,7 +27,7 @@ def interpolating_polynomial(samples):
         if df is not None:
             rows.append([(n - 1 - k) * x ** (n - 2 - k) if n - 1 - k > 0 else 0.0 for k in range(n)]); rhs.append(df)
     A, b = np.array(rows, dtype=np.float64), np.array(rhs, dtype=np.float64)
-    # Gaussian elimination with partial pivoting (the same sequence of operations as lvx_solver.hip::poly_fit)
+    # Gaussian elimination with partial pivoting (the same sequence of operations as lvx_lm_policy.h::poly_fit)
     for k in range(n):
         piv = k + int(np.argmax(np.abs(A[k:, k])))
         if piv != k:
