@@ -345,6 +345,37 @@ typedef struct lvx_calib_cov {
 int lvx_calib_cov_default_options(lvx_calib_cov_options* opt);
 int lvx_calibration_covariance(lvx_ctx* ctx, const lvx_calib_cov_options* opt, lvx_calib_cov* out);
 
+/* Uncertainty of trajectory POSES in the same damped system: Sigma = s (s H_FF s + diag(lmd) / radius)^-1 s as above (free landmarks marginalised), restricted to the
+ * at most 31 tangent scalars the pose at t[i] in `frame` (LVX_FRAME_TRAJECTORY / _LIDAR / _CAMERA, below) depends on and carried to the pose.  Contract of
+ * lvx_calibration_covariance throughout: the normal equations of the last LVX_EVAL_NORMAL_EQ evaluation at the state of that evaluation, its error word read first,
+ * LVX_E_STATE without one or on a context of a joint solve, copies only (the stored normal equations and a following lvx_solve_step see nothing), one host stop;
+ * LVX_E_NOTPD (a band or border pivot <= 0) writes nothing.  The elimination always takes the sequential band Cholesky, whatever plan the solver would choose: the
+ * entries of the inverse on the factor's pattern (band within max(bw, 23), band x border, border x border) come from the Takahashi recurrence over that factor
+ * (k_border_inv, k_band_selinv), and the sweep stops at the lowest band position a query needs.
+ *   window_idx[i][0..23]: tangent index 6 k .. 6 k + 5 of knots k = i0 .. i0 + 3; [24..30]: the sensor's theta (3), p (3), tau (1), -1 for LVX_FRAME_TRAJECTORY; a
+ *     constant (locked) scalar is -1.  window_cov[i] = Sigma over those scalars, zero rows / columns at -1.
+ *   cov[i] = J window_cov[i] J^T with J (6 x 31) the derivative of the pose error (dp = p' - p in the world frame; dphi the WORLD-frame rotation vector in radians,
+ *     R' = Exp(dphi) R) by the tangent scalars: it carries the half-angle factor of EigenQuaternionParameterization, so sigma is metres and radians.  Sensor frame:
+ *     q_S = q(tt) q_rel, p_S = p(tt) + q(tt) p_rel at tt = t + tau, tau column (v + omega x (q p_rel), omega).
+ * Validity of a sample as lvx_sample_trajectory (an invalid one: valid = 0, zeros, window_idx -1); a window with a non-unit control quaternion is invalid and the call returns
+ * LVX_E_NONUNIT_QUAT with the rest filled.  All sums in a fixed order: two calls return the same bits.  Any output array but `valid` may be NULL.
+ * LVX_E_ARG: NULL context / options / t / out / valid, n <= 0, radius <= 0, unknown frame; a border of more than 96 scalars or a half-bandwidth beyond ~380 (the
+ * one-workgroup kernels' LDS). */
+typedef struct lvx_traj_cov_options { double radius; int32_t jacobi_scaling; int32_t reserved; } lvx_traj_cov_options;   /* 1e8, 1, 0 */
+typedef struct lvx_traj_cov {
+  double*  cov;        /* [n][36] row-major over (dp_x, dp_y, dp_z, dphi_x, dphi_y, dphi_z); may be NULL */
+  double*  sigma;      /* [n][6]: sqrt of the diagonal, metres and RADIANS; may be NULL */
+  double*  window_cov; /* [n][31 * 31]; may be NULL */
+  int32_t* window_idx; /* [n][31] tangent index of each row of window_cov, -1 = constant or absent; may be NULL */
+  uint8_t* valid;      /* [n] */
+} lvx_traj_cov;
+#define LVX_TRAJ_COV_W 31
+int lvx_traj_cov_default_options(lvx_traj_cov_options* opt);
+int lvx_trajectory_covariance(lvx_ctx* ctx, const lvx_traj_cov_options* opt, int frame, int n, const double* t, lvx_traj_cov* out);
+/* t_d and the arrays of out_d are DEVICE addresses; only enqueues on the context's stream (after the evaluation's error word, which is read as above); a lost pivot
+ * (nothing written) or a non-unit quaternion is reported by the next lvx_synchronize, as lvx_sample_trajectory_d's errors are. */
+int lvx_trajectory_covariance_d(lvx_ctx* ctx, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov* out_d);
+
 /* x (+) delta with ceres::EigenQuaternionParameterization::Plus on quaternion blocks */
 int lvx_plus(lvx_ctx* ctx, const double* state, const double* delta, double* state_out);
 

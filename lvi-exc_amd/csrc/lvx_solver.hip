@@ -26,6 +26,7 @@
 #include "lvx_ctx.h"
 #include "lvx_lm_policy.h"
 #include "lvx_symeig.h"
+#include "lvx_selinv.h"
 
 namespace lvx {
 // dense border of a single sequence on 16 x 16 tiles (lvx_nd.h, in lvx_bcr.hip's translation unit)
@@ -1717,6 +1718,108 @@ int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx
   std::memcpy(out->info_vec, p, sizeof out->info_vec); p += LVX_NCAL * LVX_NCAL;
   std::memcpy(out->scale, p, sizeof out->scale);
   out->radius = opt->radius; out->sweeps = (int32_t)tail[1]; out->n_hub_eliminated = nh;
+  return LVX_OK;
+}
+
+int lvx_traj_cov_default_options(lvx_traj_cov_options* o) {
+  if (!o) return LVX_E_ARG;
+  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
+  return LVX_OK;
+}
+// lvx_calibration_covariance's front half with the sequential band Cholesky forced, then the selected inverse of that factor (lvx_selinv.h) and one wavefront per
+// query.  Everything is queued: t_d and the arrays of o are device addresses; flags[0] takes RES_NONUNIT, flags[1] a lost pivot (nothing written then).
+static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov& o, int* flags) {
+  int rc;
+  SolveWork w;
+  if ((rc = solver_alloc(c, w))) return rc;
+  const int nb = c->nb, bw = c->bw, nbd = c->nbd;
+  if (nbd > 96) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: border of " + std::to_string(nbd) + " scalars (up to 96 fit the one-workgroup inverse)");
+  const int TB = si_tb(bw), R = TB + 16, mT = TB + si_up16(nbd), M = R + si_up16(nbd);
+  const size_t lds_si = ((size_t)(16 + mT) * 17 + (size_t)32 * (mT + 1) + 3 * 16 * 17) * 8;
+  if (nb > 0 && lds_si > 160 * 1024) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: half-bandwidth " + std::to_string(bw) + " too wide for the panel of the selected inverse");
+  const size_t nb1 = (size_t)std::max(nb, 1);
+  if ((rc = dev_alloc(c, c->d_tcov, (8 + nb1 * SI_BD + (size_t)M * M) * 8))) return rc;
+  int* head = (int*)c->d_tcov.p; double* SigB = (double*)c->d_tcov.p + 8; double* D = SigB + nb1 * SI_BD;
+  hipStream_t st = c->stream;
+  EvalLocal e; bool gconv = false;
+  if ((rc = local_after_eval(c, w, &e, false))) return rc;   // the diagonal of THIS evaluation (queued; nothing of *e is used)
+  if ((rc = apply_diag(c, w, true, opt->jacobi_scaling, 1e-6, 1e32, e, nullptr, 0.0, &gconv))) return rc;
+  StageTimer tm(c);
+  bool bcr_used = false;
+  w.lm_done = false;
+  if ((rc = reduce_to_border(c, w, opt->radius, true, &bcr_used, tm))) return rc;
+  const size_t lds_b = (size_t)2 * nbd * (nbd + 1) * 8;
+  LVX_HIP(c, hipFuncSetAttribute((const void*)k_border_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
+  hipLaunchKernelGGL(k_border_inv, dim3(1), dim3(SI_NT), lds_b, st, w.S, nbd, w.info);
+  LVX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)head, nb, 1, st));
+  const double* state_d = c->last_state_d;
+  if (nb > 0) {
+    hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, head);
+    LVX_HIP(c, hipMemsetAsync(D, 0, (size_t)M * M * 8, st));
+    SelInv g{(const double*)w.L, nb, bw, w.Z, w.ldz, nbd, (const double*)w.S, D, M, SigB, (const int*)head, (const int*)w.info};
+    LVX_HIP(c, hipFuncSetAttribute((const void*)k_band_selinv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_si));
+    hipLaunchKernelGGL(k_band_selinv, dim3(1), dim3(SI_NT), lds_si, st, g);
+  }
+  PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, (const double*)SigB, (const double*)w.Z, w.ldz, nb, nbd, (const double*)w.S, (const double*)w.scale,
+            (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.cov, o.sigma, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
+  hipLaunchKernelGGL(k_pose_cov, dim3((unsigned)n), dim3(64), 0, st, p);
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+static int traj_cov_args(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t, const lvx_traj_cov* out) {
+  if (!c) return LVX_E_ARG;
+  if (!opt || !t || !out || !out->valid || n <= 0 || !(opt->radius > 0)) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: n <= 0, radius <= 0 or a required pointer is NULL");
+  if (frame != LVX_FRAME_TRAJECTORY && frame != LVX_FRAME_LIDAR && frame != LVX_FRAME_CAMERA) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: unknown frame");
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_trajectory_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_trajectory_covariance: the context takes part in a joint solve");
+  LVX_HIP(c, hipSetDevice(c->device));
+  return check_last_eval(c);
+}
+int lvx_trajectory_covariance_d(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov* out_d) {
+  int rc = traj_cov_args(c, opt, frame, n, t_d, out_d);
+  if (rc) return rc;
+  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
+    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
+    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
+  }
+  c->tcov_d_unchecked = true;
+  return traj_cov_enqueue(c, opt, frame, n, t_d, *out_d, (int*)c->d_tj[3].p + 1);
+}
+int lvx_trajectory_covariance(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t, lvx_traj_cov* out) {
+  int rc = traj_cov_args(c, opt, frame, n, t, out);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  // device and pinned images: [t | cov | sigma | window_cov | window_idx | valid | flags (2 ints)]; an array the caller does not ask for is not computed
+  const size_t nn = (size_t)n, W2 = (size_t)LVX_TRAJ_COV_W * LVX_TRAJ_COV_W;
+  size_t off[7]; size_t cur = 0;
+  const size_t bytes[6] = {nn * 8, out->cov ? nn * 36 * 8 : 0, out->sigma ? nn * 6 * 8 : 0, out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_TRAJ_COV_W * 4 : 0, nn};
+  for (int k = 0; k < 6; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
+  off[6] = cur; cur += 16;
+  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
+  if (c->h_tcov_cap < cur) {
+    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
+    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
+    c->h_tcov_cap = cur;
+  }
+  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
+  std::memcpy(h, t, nn * 8);
+  LVX_HIP(c, hipMemcpyAsync(d, h, nn * 8, hipMemcpyHostToDevice, st));
+  LVX_HIP(c, hipMemsetAsync(d + off[6], 0, 16, st));
+  lvx_traj_cov od;
+  od.cov = out->cov ? (double*)(d + off[1]) : nullptr; od.sigma = out->sigma ? (double*)(d + off[2]) : nullptr; od.window_cov = out->window_cov ? (double*)(d + off[3]) : nullptr;
+  od.window_idx = out->window_idx ? (int32_t*)(d + off[4]) : nullptr; od.valid = (uint8_t*)(d + off[5]);
+  if ((rc = traj_cov_enqueue(c, opt, frame, n, (const double*)d, od, (int*)(d + off[6])))) return rc;
+  LVX_HIP(c, hipMemcpyAsync(h + off[1], d + off[1], cur - off[1], hipMemcpyDeviceToHost, st));
+  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
+  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
+  int fl[2]; std::memcpy(fl, h + off[6], 8);
+  if (fl[1]) {
+    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
+    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
+  }
+  void* dst[6] = {nullptr, out->cov, out->sigma, out->window_cov, out->window_idx, out->valid};
+  for (int k = 1; k < 6; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
+  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
   return LVX_OK;
 }
 

@@ -68,14 +68,19 @@ struct CalibrateOptions {
   bool error_statistics = false;   // printErrorStatistics("Before optimization") / ("After optimization") around every stage's solve (trajectory_manager_lvi.cpp:339-342): StageReport::stats_before / stats_after
   bool covariance = false;         // lvx_calibration_covariance at every stage's final state (one more LVX_EVAL_NORMAL_EQ evaluation per stage): StageReport::covariance
   double covariance_radius = 1e8;  // the radius of the damped system the covariance belongs to (what it means)
+  double trajectory_covariance_step = 0;   // seconds, 0 = off: lvx_trajectory_covariance of the pose at every stage's final state, sampled with SampleTimes over the IMU span (the same evaluation as `covariance`, the same radius): StageReport::trajectory_sigma
+  int trajectory_covariance_frame = LVX_FRAME_LIDAR;   // the frame of those poses.  A stage that locks the trajectory and a sensor's extrinsics (the camera-surfel stage: LiDAR) reports exact zeros for that sensor's frame
   int verbose = 1;
 };
+// lvx_trajectory_covariance over a list of times: cov [n][36], sigma [n][6] (metres, RADIANS), valid [n]
+struct TrajectoryUncertainty { int frame = 0; double radius = 0; std::vector<double> t, cov, sigma; std::vector<uint8_t> valid; };
 struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_surfel_points = 0, n_cam_surfel = 0;
                      std::vector<double> cost_history, radius_history; std::vector<int32_t> accepted;   // per-iteration trace of the stage's solve (lvx_lm_get_history)
                      std::vector<double> state_in;   // the state the stage's solve started from (CalibrateOptions::keep_history)
                      bool has_stats = false; lvx_error_stats stats_before{}, stats_after{};   // CalibrateOptions::error_statistics: lvx_error_statistics at the state the solve started from / ended at
                      int init_prefix = -1; lvx_rotinit_result init{};   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
                      bool has_covariance = false; lvx_calib_cov covariance{};   // CalibrateOptions::covariance: the record at the state the stage's solve ended at (false: the option is off, or the call reported LVX_E_NOTPD)
+                     bool has_trajectory_sigma = false; TrajectoryUncertainty trajectory_sigma;   // CalibrateOptions::trajectory_covariance_step: pose sigmas (trajectory_covariance_frame) along the spline at the stage's final state (false: off, or LVX_E_NOTPD)
                      int n_lidar_poses = 0; lvx_family_stats lidar_pos_before{}, lidar_pos_after{}; };   // trajInitFromLidarPose: blocks attached; with error_statistics, lvx_lidar_pose_statistics around the solve
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
@@ -209,6 +214,38 @@ inline TrajectorySamples SampleTrajectory(lvx_ctx* ctx, const std::vector<double
   lvx_traj_samples o{r.position.data(), r.velocity.data(), r.acceleration.empty() ? nullptr : r.acceleration.data(), r.orientation_xyzw.data(), r.angular_velocity.data(), r.valid.data()};
   ThrowOnError(ctx, lvx_sample_trajectory(ctx, state.data(), frame, (int)n, times.data(), &o));
   return r;
+}
+// lvx_trajectory_covariance at the normal equations (and the state) of the context's last LVX_EVAL_NORMAL_EQ evaluation; opts = nullptr: the defaults
+inline TrajectoryUncertainty TrajectoryCovariance(lvx_ctx* ctx, int frame, const std::vector<double>& times, const lvx_traj_cov_options* opts = nullptr) {
+  TrajectoryUncertainty r; r.frame = frame; r.t = times;
+  lvx_traj_cov_options o; lvx_traj_cov_default_options(&o);
+  if (opts) o = *opts;
+  r.radius = o.radius;
+  const size_t n = times.size();
+  if (n == 0) return r;
+  r.cov.assign(36 * n, 0.0); r.sigma.assign(6 * n, 0.0); r.valid.assign(n, 0);
+  lvx_traj_cov out{r.cov.data(), r.sigma.data(), nullptr, nullptr, r.valid.data()};
+  ThrowOnError(ctx, lvx_trajectory_covariance(ctx, &o, frame, (int)n, times.data(), &out));
+  return r;
+}
+// What a user reads off it, two lines: the worst and the median position / rotation sigma (norm of the three standard deviations) over the valid samples and the
+// time of the worst.  The sigmas belong to the damped system at the record's radius, as those of FormatCalibrationUncertainty.
+//   [Trajectory] position std (m): worst a at t = ..., median b (n valid samples, radius r)
+//   [Trajectory] rotation std (deg): worst a at t = ..., median b
+inline std::string FormatTrajectoryUncertainty(const TrajectoryUncertainty& r) {
+  std::vector<double> sp, sr; std::vector<size_t> at;
+  for (size_t i = 0; i < r.valid.size(); ++i) if (r.valid[i]) {
+    const double* s = r.sigma.data() + 6 * i;
+    sp.push_back(std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2])); sr.push_back(std::sqrt(s[3] * s[3] + s[4] * s[4] + s[5] * s[5])); at.push_back(i);
+  }
+  if (sp.empty()) return "[Trajectory] no valid sample\n";
+  const size_t wp = (size_t)(std::max_element(sp.begin(), sp.end()) - sp.begin()), wr = (size_t)(std::max_element(sr.begin(), sr.end()) - sr.begin());
+  auto median = [](std::vector<double> v) { std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end()); return v[v.size() / 2]; };
+  const double deg = 180.0 / 3.14159265358979323846;
+  char buf[512];
+  std::snprintf(buf, sizeof buf, "[Trajectory] position std (m): worst %.6e at t = %.6f, median %.6e (%d valid samples, radius %.6e)\n[Trajectory] rotation std (deg): worst %.6e at t = %.6f, median %.6e\n",
+                sp[wp], r.t[at[wp]], median(sp), (int)sp.size(), r.radius, deg * sr[wr], r.t[at[wr]], deg * median(sr));
+  return buf;
 }
 struct PoseComparison { lvx_pose_errors errors{}; std::vector<double> abs_trans, abs_rot; };
 // reference poses as ReadPoseGT returns them (stamp_ns, p, q w x y z): the stamps become stamp_ns * 1e-9 seconds
@@ -663,10 +700,23 @@ class Calibrator {
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_before_));
     check(lvx_lm_solve(ctx_, state->data(), &o, &s));
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_after_));
-    has_cov_ = false;
-    if (opt_.covariance) {   // the normal equations at the final state (the loop's last ones may belong to a rejected candidate), then the call
+    has_cov_ = false; has_tsig_ = false;
+    const bool want_tsig = opt_.trajectory_covariance_step > 0 && !in_.imu_t.empty();
+    if (opt_.covariance || want_tsig) {   // the normal equations at the final state (the loop's last ones may belong to a rejected candidate), then the calls
       double cost = 0.0;
       check(lvx_evaluate(ctx_, state->data(), LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cost, nullptr));
+    }
+    if (want_tsig) {
+      lvx_traj_cov_options to; lvx_traj_cov_default_options(&to); to.radius = opt_.covariance_radius;
+      const std::vector<double> times = SampleTimes(in_.imu_t.front(), in_.imu_t.back(), opt_.trajectory_covariance_step);
+      tsig_ = TrajectoryUncertainty{}; tsig_.frame = opt_.trajectory_covariance_frame; tsig_.radius = to.radius; tsig_.t = times;
+      tsig_.cov.assign(36 * times.size(), 0.0); tsig_.sigma.assign(6 * times.size(), 0.0); tsig_.valid.assign(times.size(), 0);
+      lvx_traj_cov out{tsig_.cov.data(), tsig_.sigma.data(), nullptr, nullptr, tsig_.valid.data()};
+      const int rc = times.empty() ? LVX_OK : lvx_trajectory_covariance(ctx_, &to, opt_.trajectory_covariance_frame, (int)times.size(), times.data(), &out);
+      if (rc == LVX_E_NOTPD) { if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] trajectory covariance: %s\n", lvx_last_error(ctx_)); }   // no record for this stage; the calibration goes on
+      else { check(rc); has_tsig_ = true; if (opt_.verbose) std::fputs(FormatTrajectoryUncertainty(tsig_).c_str(), stderr); }
+    }
+    if (opt_.covariance) {
       lvx_calib_cov_options co; lvx_calib_cov_default_options(&co); co.radius = opt_.covariance_radius;
       const int rc = lvx_calibration_covariance(ctx_, &co, &cov_);
       if (rc == LVX_E_NOTPD) { if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] covariance: %s\n", lvx_last_error(ctx_)); }   // no record for this stage; the calibration goes on
@@ -683,6 +733,7 @@ class Calibrator {
     r->cost_history = hist_cost_; r->radius_history = hist_radius_; r->accepted = hist_acc_; r->state_in = stage_state_in_;
     r->has_stats = opt_.error_statistics; r->stats_before = stats_before_; r->stats_after = stats_after_;
     r->has_covariance = has_cov_; r->covariance = cov_;
+    r->has_trajectory_sigma = has_tsig_; r->trajectory_sigma = tsig_;
   }
   void check(int rc) {
     if (rc == LVX_OK) return;
@@ -717,6 +768,7 @@ class Calibrator {
   int n_surfel_used_ = 0, n_planes_ = 0;
   lvx_error_stats stats_before_{}, stats_after_{};
   bool has_cov_ = false; lvx_calib_cov cov_{};
+  bool has_tsig_ = false; TrajectoryUncertainty tsig_;
 };
 
 }  // namespace lvx_host

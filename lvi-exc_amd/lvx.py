@@ -100,6 +100,18 @@ class CalibCov(C.Structure):
                 ("radius", C.c_double), ("sweeps", C.c_int32), ("n_hub_eliminated", C.c_int32)]
 
 
+TRAJ_COV_W = 31   # tangent scalars a pose depends on: 24 of the four knots, the sensor's theta (3), p (3), tau (1)
+
+
+class TrajCovOptions(C.Structure):
+    _fields_ = [("radius", C.c_double), ("jacobi_scaling", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TrajCov(C.Structure):
+    """lvx_traj_cov: host or device addresses; a NULL member (but valid) is not computed."""
+    _fields_ = [("cov", C.c_void_p), ("sigma", C.c_void_p), ("window_cov", C.c_void_p), ("window_idx", C.c_void_p), ("valid", C.c_void_p)]
+
+
 N_SHARED = 14   # the shared extrinsic scalars of a joint solve: canonical slot k = c - 8
 
 
@@ -445,6 +457,43 @@ class Context:
         return dict(free_index=np.array(r.free_index[:nf], dtype=np.int64), cov=np.array(r.cov).reshape(N_CALIB, N_CALIB), sigma=np.array(r.sigma),
                     info_eig=np.array(r.info_eig[:nf]), info_vec=np.array(r.info_vec).reshape(N_CALIB, N_CALIB)[:nf, :nf].copy(), scale=np.array(r.scale),
                     radius=r.radius, sweeps=r.sweeps, n_hub_eliminated=r.n_hub_eliminated)
+
+    def _traj_cov_options(self, radius, jacobi_scaling):
+        opt = TrajCovOptions()
+        self._l.lvx_traj_cov_default_options(C.byref(opt))
+        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
+        return opt
+
+    def trajectory_covariance(self, t, frame=0, radius=1e8, jacobi_scaling=True, window=False):
+        """Covariance of the pose at times t in `frame` (FRAME_TRAJECTORY / FRAME_LIDAR / FRAME_CAMERA) in the DAMPED system of the last evaluate(normal_eq=True), at the
+        state of that evaluation (lvx_trajectory_covariance).  Returns a dict: cov [n, 6, 6] over (dp world, dphi world), sigma [n, 6] (metres, radians), valid [n] bool;
+        with window=True also window_cov [n, 31, 31] and window_idx [n, 31] (tangent index, -1 constant or absent).  An invalid sample holds zeros.  A non-unit control
+        quaternion raises LvxError(E_NONUNIT_QUAT) whose `partial` attribute is that dict."""
+        t = _d(np.atleast_1d(t))
+        n = len(t)
+        out = dict(cov=np.zeros((n, 6, 6)), sigma=np.zeros((n, 6)))
+        if window:
+            out["window_cov"] = np.zeros((n, TRAJ_COV_W, TRAJ_COV_W))
+            out["window_idx"] = np.full((n, TRAJ_COV_W), -1, np.int32)
+        valid = np.zeros(n, np.uint8)
+        r = TrajCov(out["cov"].ctypes.data, out["sigma"].ctypes.data, out["window_cov"].ctypes.data if window else None, out["window_idx"].ctypes.data if window else None,
+                    valid.ctypes.data)
+        opt = self._traj_cov_options(radius, jacobi_scaling)
+        rc = self._l.lvx_trajectory_covariance(self._h, C.byref(opt), C.c_int(frame), C.c_int(n), _p(t), C.byref(r))
+        out["valid"] = valid.astype(bool)
+        if rc == E_NONUNIT_QUAT:
+            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
+            e.partial = out
+            raise e
+        self._ck(rc)
+        return out
+
+    def trajectory_covariance_d(self, t_d_ptr, n, out_d_ptrs, valid_d_ptr, frame=0, radius=1e8, jacobi_scaling=True):
+        """lvx_trajectory_covariance_d: device addresses; out_d_ptrs maps "cov" / "sigma" / "window_cov" / "window_idx" to addresses (absent: not computed).  Only
+        enqueues; synchronize() reports a lost pivot or a non-unit quaternion."""
+        r = TrajCov(*[out_d_ptrs.get(f) for f in ("cov", "sigma", "window_cov", "window_idx")], valid_d_ptr)
+        opt = self._traj_cov_options(radius, jacobi_scaling)
+        self._ck(self._l.lvx_trajectory_covariance_d(self._h, C.byref(opt), C.c_int(frame), C.c_int(n), C.c_void_p(t_d_ptr), C.byref(r)))
 
     def lm_solve(self, state, max_iterations=50, **kw):
         """TrajectoryEstimator::Solve(max_iterations) equivalent.  Returns (state, summary dict with per-iteration history)."""
