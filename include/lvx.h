@@ -376,6 +376,43 @@ int lvx_trajectory_covariance(lvx_ctx* ctx, const lvx_traj_cov_options* opt, int
  * (nothing written) or a non-unit quaternion is reported by the next lvx_synchronize, as lvx_sample_trajectory_d's errors are. */
 int lvx_trajectory_covariance_d(lvx_ctx* ctx, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov* out_d);
 
+/* Uncertainty of LANDMARKS in the same damped system: the variance of the inverse depth rho_l, its covariance with the reference pose, and the covariance of the map
+ * point.  The landmarks are eliminated before the band; with E_l the landmark's row of the normal equations over the reduced (band + border) scalars,
+ * w_l = s_l^2 / (s_l^2 H_ll + lmd_l / radius) and Sigma_xx the covariance of the reduced system (the selected inverse lvx_trajectory_covariance reads),
+ *   Sigma_ll = w_l + w_l^2 E_l Sigma_xx E_l^T,   Sigma_lx = -w_l E_l Sigma_xx.
+ * Contract of lvx_trajectory_covariance word for word: the last LVX_EVAL_NORMAL_EQ evaluation at its state, its error word read first, LVX_E_STATE without one or on a
+ * context of a joint solve, copies only, one host stop, always the sequential factor, LVX_E_NOTPD writes nothing, all sums in a fixed order (two calls return the same
+ * bits), any output array but `valid` may be NULL.  The sweep of the selected inverse stops at the lowest band position a queried landmark needs (the first coupling
+ * of its row, its reference window).
+ *   The reference pose is the LVX_FRAME_CAMERA pose at t_ref = (t0_ref[l] + tau_C) + v_ref readout / rows, y_h = Unproject(uv_ref) (the radtan iteration when the
+ *   camera is distorted): point = R_C(t_ref) (y_h / rho) + p_C(t_ref) in the world frame.
+ *   window_idx[i][0] = the landmark's tangent index 6 N + 22 + l; [1..31] the 31 scalars of that pose as lvx_trajectory_covariance orders them, -1 constant.
+ *   window_cov[i] = Sigma over those 32 scalars (zero rows / columns at -1); var_rho = window_cov[i][0][0] bit for bit; sigma_rho its square root.
+ *   point_cov[i] = J window_cov[i] J^T, J = [ -R_C y_h / rho^2 | (I, -[R_C y_h / rho]_x) J_pose ] (3 x 32).
+ * valid = 0 (zeros, window_idx -1) for a landmark that is constant under the lock mask or whose reference pose cannot be evaluated (outside the trajectory; a non-unit
+ * control quaternion, and the call returns LVX_E_NONUNIT_QUAT with the rest filled).  A FREE landmark that no row reaches (H_ll = 0) is not special: s_l = 1,
+ * var_rho = radius / 1e-6 — the direction is reported, not hidden.  The bound rho >= 0 is ignored; rho = 0 is a point at infinity (point and point_cov not finite).
+ * Landmark-landmark covariances are off the factor's pattern and are not available.
+ * LVX_E_ARG: NULL context / options / out / valid, n <= 0, n > the number of landmarks, an id outside [0, L), radius <= 0, reserved != 0, and the LDS limits of
+ * lvx_trajectory_covariance. */
+typedef struct lvx_landmark_cov_options { double radius; int32_t jacobi_scaling; int32_t reserved; } lvx_landmark_cov_options;   /* 1e8, 1, 0 */
+#define LVX_LM_COV_W 32
+typedef struct lvx_landmark_cov {
+  double*  var_rho;     /* [n]; may be NULL */
+  double*  sigma_rho;   /* [n]; may be NULL */
+  double*  point;       /* [n][3] world frame; may be NULL */
+  double*  point_cov;   /* [n][9] row-major; may be NULL */
+  double*  window_cov;  /* [n][32 * 32]; may be NULL */
+  int32_t* window_idx;  /* [n][32] tangent index, -1 = constant or absent; may be NULL */
+  uint8_t* valid;       /* [n] */
+} lvx_landmark_cov;
+int lvx_landmark_cov_default_options(lvx_landmark_cov_options* opt);
+/* landmark_id [n] (NULL: 0 .. n - 1), in any order, repeats allowed */
+int lvx_landmark_covariance(lvx_ctx* ctx, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id, lvx_landmark_cov* out);
+/* landmark_id_d and the arrays of out_d are DEVICE addresses; only enqueues on the context's stream.  An id outside [0, L) is an invalid entry; a lost pivot (nothing
+ * written) or a non-unit quaternion is reported by the next lvx_synchronize. */
+int lvx_landmark_covariance_d(lvx_ctx* ctx, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id_d, const lvx_landmark_cov* out_d);
+
 /* x (+) delta with ceres::EigenQuaternionParameterization::Plus on quaternion blocks */
 int lvx_plus(lvx_ctx* ctx, const double* state, const double* delta, double* state_out);
 

@@ -160,6 +160,7 @@ struct lvx_ctx {
   int lm_elim_kernel = 0;     // lvx_layout::lm_elim_kernel: which landmark elimination the last solve launched
   lvx::DevBuf d_ccov;         // lvx_calibration_covariance: the record k_calib_cov writes (LVX_CCOV_N doubles); ..._shared: record, kept factor and message of k_joint_cov_*
   lvx::DevBuf d_tcov, d_tcov_io; void* h_tcov = nullptr; size_t h_tcov_cap = 0; bool tcov_d_unchecked = false;   // lvx_trajectory_covariance: [lowest band position | selected band | ring of k_band_selinv], [times | outputs] of the host form and their pinned mirror; a _d call awaits lvx_synchronize's look at its pivot word
+  lvx::DevBuf d_lcov;         // lvx_landmark_covariance: the wide band store of the selected inverse, SigW [nb][TB + 1] (its staging and flag words are lvx_trajectory_covariance's)
   lvx::DevBuf d_bcrD, d_bcrG, d_bcrInfo, d_Y2, d_gram, d_bcrLinv; bool bcr_linv = false;   // d_bcrLinv: inverses of the factors' 16 x 16 diagonal triangles (k_potrf_batched -> k_trsm_reg)
   void* blas = nullptr;
   int bcr_b = 0, bcr_nblk = 0, bcr_nreal = 0;

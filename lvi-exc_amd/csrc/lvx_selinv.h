@@ -1,4 +1,5 @@
-// lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and the pose covariances read from it (lvx_trajectory_covariance).
+// lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and what is read from it: pose covariances (lvx_trajectory_covariance) and
+// landmark covariances (lvx_landmark_covariance, at the end of the file).
 // Included by lvx_solver.hip (its translation unit holds the factor's kernels).
 //
 // reduce_to_border(force_seq) leaves   Lb[j (bw + 1) + d] = L(j + d, j)   (band Cholesky),   Z[r ldz + j] = (L^-1 A_bc)(j, r)   and   S = A_cc - Zc^T Zc (unfactored),
@@ -13,10 +14,10 @@
 // which is the 16-step recurrence inside the panel written once.  Sigma_TT lives in a RING: a dense symmetric (R + nbd') x (R + nbd') array, R = TB + 16, band position
 // p at slot p mod R — the panel's own 16 slots are those of the positions that just left the window.  512 KB at bw = 180, nbd = 46: resident in L2.  One workgroup,
 // no atomics, no waiting on another workgroup; what a query reads afterwards is stored apart: SigB[j][d] = Sigma(j + d, j), d <= 23, and Sigma(border r, j) over Z's
-// border rows in place.
+// border rows in place.  For the landmark call the same values also go to SigW[j][d], d <= TB (every d the panel's columns reach lies on the block pattern).
 #pragma once
 #include "lvx_chol16.h"
-#include "lvx_trajcov.h"
+#include "lvx_lmcov.h"
 
 namespace lvx {
 
@@ -85,6 +86,7 @@ struct SelInv {
   double* D; int M;       // the ring, zero on entry: [M][M], M = R + up16(nbd)
   double* SigB;           // [nb][SI_BD]
   const int* lowest; const int* info;
+  double* SigW;           // [nb][TB + 1], or null: SigW[j][d] = Sigma(j + d, j), d <= TB (lvx_landmark_covariance)
 };
 __global__ __launch_bounds__(SI_NT) void k_band_selinv(SelInv g) {
   extern __shared__ double ds[];
@@ -186,7 +188,11 @@ __global__ __launch_bounds__(SI_NT) void k_band_selinv(SelInv g) {
       D[(size_t)s * M + sJ + c] = v;
       D[(size_t)(sJ + c) * M + s] = v;
       if (c < nk) {
-        if (i < TB) { const int d = 16 + i - c; if (d < SI_BD && j0 + 16 + i < nb) g.SigB[(size_t)(j0 + c) * SI_BD + d] = v; }
+        if (i < TB) {
+          const int d = 16 + i - c;
+          if (d < SI_BD && j0 + 16 + i < nb) g.SigB[(size_t)(j0 + c) * SI_BD + d] = v;
+          if (g.SigW && d <= TB && j0 + 16 + i < nb) g.SigW[(size_t)(j0 + c) * (TB + 1) + d] = v;
+        }
         else if (i - TB < nbd) g.Z[(size_t)(i - TB) * g.ldz + j0 + c] = v;
       }
     }
@@ -194,7 +200,7 @@ __global__ __launch_bounds__(SI_NT) void k_band_selinv(SelInv g) {
       const int a = tid >> 4, b = tid & 15;
       const double v = (a < nk && b < nk) ? P[a * ldg + b] : 0.0;
       D[(size_t)(sJ + a) * M + sJ + b] = v;
-      if (a >= b && a < nk) g.SigB[(size_t)(j0 + b) * SI_BD + (a - b)] = v;
+      if (a >= b && a < nk) { g.SigB[(size_t)(j0 + b) * SI_BD + (a - b)] = v; if (g.SigW) g.SigW[(size_t)(j0 + b) * (TB + 1) + (a - b)] = v; }
     }
     __threadfence();
     __syncthreads();
@@ -269,6 +275,160 @@ __global__ __launch_bounds__(64) void k_pose_cov(PoseCov g) {
   __syncthreads();
   if (lane < 36 && g.cov) g.cov[(size_t)i * 36 + lane] = Cv[lane / 6][lane % 6];
   if (lane < 6 && g.sigma) g.sigma[(size_t)i * 6 + lane] = sqrt(Cv[lane][lane]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// lvx_landmark_covariance.  The landmarks were eliminated before the band (k_lm_schur): with E_l the landmark's row of DevCommon::lmH over its band window and the
+// border, d_l = s_l^2 H_ll + lmd_l / radius, w_l = s_l^2 / d_l and Sigma_xx the UNSCALED covariance of the reduced system (the selected inverse above),
+//   Sigma_ll = w_l + w_l^2 E_l Sigma_xx E_l^T,      Sigma_lx = -w_l E_l Sigma_xx
+// Every entry of Sigma_xx that E_l or the reference pose's window touches lies on the factor's pattern: the elimination wrote E_l^T E_l into the band, so the reach of
+// a landmark's row is <= bw <= TB.  Those entries are read from SigW[j][d] = Sigma(j + d, j), d <= TB, which k_band_selinv stores beside SigB when asked to.
+// ---------------------------------------------------------------------------------------------------------
+struct LmQuery {
+  const double* state; int N; double t0, dt; CamIntr cam; const double* lm_uv; const double* lm_t0; int L; const int* ord;
+  const double* lmH; const int* p0s; int wl, nbd_ext, ls;   // lmH null: no landmark rows were formed (no reprojection block): every free landmark is unobserved
+  int n; const int* ids;                                     // ids null: 0 .. n - 1
+};
+// the query's landmark (-1: outside [0, L) or constant under the lock mask) and the knot interval of its reference pose
+__device__ __forceinline__ int lc_landmark(const LmQuery& q, int i, KnotRef* k, bool* pose) {
+  const int l = q.ids ? q.ids[i] : i;
+  if (l < 0 || l >= q.L || q.ord[6 * (size_t)q.N + 22 + l] != LVX_LM_BASE + l) return -1;
+  const double tau = q.state[7 * (size_t)q.N + 31];
+  *pose = traj_knot(q.t0, q.dt, q.N, landmark_ref_time(q.cam, tau, q.lm_uv[2 * (size_t)l + 1], q.lm_t0[l]), k);
+  return l;
+}
+// lowest band position any query needs -> *lowest (the caller starts it at nb): the reference pose's window and, where rows reached the landmark, its first coupling
+__global__ void k_lc_lowest(LmQuery q, int* lowest) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= q.n) return;
+  KnotRef k; bool pose = false;
+  const int l = lc_landmark(q, i, &k, &pose);
+  if (l < 0 || !pose) return;
+  int lo = 0x7fffffff;
+  for (int c = 0; c < 24; ++c) { const int o = q.ord[6 * k.i0 + c]; if (o >= 0 && o < lo) lo = o; }
+  if (q.lmH && q.lmH[(size_t)l * q.ls + q.wl + q.nbd_ext] > 0.0 && q.p0s[l] < lo) lo = q.p0s[l];
+  if (lo != 0x7fffffff) atomicMin(lowest, lo);
+}
+
+struct LmCov {
+  LmQuery q;
+  const double* SigW; int TB; const double* Z; int ldz, nb, nbd; const double* Scc;
+  const double* scale; const double* lmd; double inv_radius;   // scale / lmd: SolveWork's, [band | border | landmarks]
+  const int* info; int force_bad;
+  double* var; double* sigma; double* point; double* pcov; double* wcov; int32_t* widx; uint8_t* valid; int* flag; int* bad;
+};
+// Sigma' (scaled) between two positions: >= 0 a band position, < 0 border slot -1 - o
+__device__ __forceinline__ double lc_sigma(const LmCov& g, int pa, int pb) {
+  if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; return d <= g.TB ? g.SigW[(size_t)lo * (g.TB + 1) + d] : 0.0; }
+  if (pa >= 0) return g.Z[(size_t)(-1 - pb) * g.ldz + pa];
+  if (pb >= 0) return g.Z[(size_t)(-1 - pa) * g.ldz + pb];
+  const int ra = -1 - pa, rb = -1 - pb;
+  return g.Scc[(size_t)max(ra, rb) * g.nbd + min(ra, rb)];
+}
+// One wavefront per queried landmark.  Lane 0 evaluates the map point and its 3 x 32 Jacobian (lvx_lmcov.h); the non-zeros of the landmark's row are compacted by
+// ballot in index order (value times the Jacobi scale of its column, position); E Sigma E^T runs over the pairs a <= b with the lanes along b — the entries of one row
+// of SigW, consecutive where the couplings are — each lane adding its terms in (a, b) order, the lanes joined by a butterfly (every lane ends with the same bits); the 31
+// cross terms take a lane pair per window scalar.  The window, J W J^T and the stores follow k_pose_cov.  Dynamic LDS: ev [ne] doubles | epos [ne] ints, ne = wl + nbd.
+__global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
+  extern __shared__ double lds_e[];
+  __shared__ double Jp[6][TCOV_W], J[3][LCOV_W], W[LCOV_W][LCOV_W + 1], T[3][LCOV_W], sc[LCOV_W], Cv[3][3], Pw[3];
+  __shared__ int idx[LCOV_W], pos[LCOV_W], status, lm_s;
+  const LmQuery& q = g.q;
+  const int lane = threadIdx.x, i = blockIdx.x, ne = q.wl + g.nbd;
+  double* ev = lds_e; int* epos = (int*)(lds_e + ne);
+  if (g.force_bad || g.info[0] != 0 || g.info[1] != 0) { if (lane == 0 && i == 0) *g.bad = 1; return; }   // a lost pivot: nothing is written
+  if (lane == 0) {
+    KnotRef k; bool pose = false;
+    const int l = lc_landmark(q, i, &k, &pose);
+    int st = RES_RANGE;
+    if (l >= 0 && pose) {
+      const SplineRef sp{q.t0, q.dt, q.N, q.state, q.state + 3 * (size_t)q.N};
+      const double* ss = q.state + 7 * (size_t)q.N + 24;
+      SensorCal cam; cam.q = load_q(ss); cam.p = load_v3(ss + 4); cam.tau = ss[7];
+      st = landmark_point_jacobian(sp, q.cam, cam, l, q.lm_uv[2 * (size_t)l], q.lm_uv[2 * (size_t)l + 1], q.lm_t0[l], q.state[7 * (size_t)q.N + 32 + l], Jp, J, idx, Pw);
+      if (st == RES_NONUNIT) *g.flag = RES_NONUNIT;
+    }
+    status = st; lm_s = l;
+  }
+  __syncthreads();
+  const size_t W2 = (size_t)LCOV_W * LCOV_W;
+  if (status != RES_OK) {   // constant under the lock mask, or no reference pose: zeros
+    if (lane == 0) { g.valid[i] = 0; if (g.var) g.var[i] = 0.0; if (g.sigma) g.sigma[i] = 0.0; }
+    if (lane < 3 && g.point) g.point[(size_t)i * 3 + lane] = 0.0;
+    if (lane < 9 && g.pcov) g.pcov[(size_t)i * 9 + lane] = 0.0;
+    if (lane < LCOV_W && g.widx) g.widx[(size_t)i * LCOV_W + lane] = -1;
+    if (g.wcov) for (int e = lane; e < (int)W2; e += 64) g.wcov[(size_t)i * W2 + e] = 0.0;
+    return;
+  }
+  const int l = lm_s;
+  if (lane < LCOV_W) {
+    int o = LVX_DEAD, id = -1;
+    if (lane == 0) { o = LVX_LM_BASE; id = idx[0]; }
+    else if (idx[lane] >= 0) { o = q.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane]; }
+    pos[lane] = o;
+    sc[lane] = (lane == 0 || o == LVX_DEAD) ? 0.0 : g.scale[o >= 0 ? o : g.nb + (-1 - o)];
+    if (g.widx) g.widx[(size_t)i * LCOV_W + lane] = id;
+  }
+  // the landmark's row: non-zeros in index order
+  const double* row = q.lmH ? q.lmH + (size_t)l * q.ls : nullptr;
+  const double Hll = row ? row[q.wl + q.nbd_ext] : 0.0;
+  int nn = 0;
+  if (Hll > 0.0) {   // (k_lm_schur's test: a landmark no row reached was not eliminated, and its row is zero)
+    const int p0 = q.p0s[l];
+    for (int k0 = 0; k0 < ne; k0 += 64) {
+      const int k = k0 + lane;
+      double e = 0.0; int p = 0;
+      if (k < ne) { p = k < q.wl ? p0 + k : -1 - (k - q.wl); if (k >= q.wl || p < g.nb) e = row[k]; }
+      const bool nz = e != 0.0;
+      const unsigned long long mask = __ballot(nz);
+      if (nz) { const int at = nn + __popcll(mask & ((1ull << lane) - 1ull)); ev[at] = e * g.scale[p >= 0 ? p : g.nb + (-1 - p)]; epos[at] = p; }
+      nn += __popcll(mask);
+    }
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int a = 0; a < nn; ++a) {
+    const int pa = epos[a]; const double ea = ev[a];
+    for (int b = a + lane; b < nn; b += 64) { const double t = ea * ev[b] * lc_sigma(g, pa, epos[b]); acc += b == a ? t : 2.0 * t; }
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  const int m = lane & 31, pm = pos[m];
+  double cm = 0.0;
+  if (m > 0 && pm != LVX_DEAD) for (int a = lane >> 5; a < nn; a += 2) cm += ev[a] * lc_sigma(g, epos[a], pm);
+  cm += __shfl_xor(cm, 32);
+  double s = 1.0, dmp = 1e-6;   // no landmark rows: the solver holds no diagonal for the landmarks; an unobserved one has scale 1 and the floor of the damping
+  if (row) { s = g.scale[g.nb + g.nbd + l]; dmp = g.lmd[g.nb + g.nbd + l]; }
+  const double w = s * s / (s * s * Hll + dmp * g.inv_radius);
+  for (int e = lane; e < (int)W2; e += 64) {
+    const int a = e / LCOV_W, b = e % LCOV_W;
+    double v = 0.0;
+    if (a > 0 && b > 0) { const int pa = pos[a], pb = pos[b]; if (pa != LVX_DEAD && pb != LVX_DEAD) v = lc_sigma(g, pa, pb) * (sc[a] * sc[b]); }
+    W[a][b] = v;
+  }
+  __syncthreads();
+  if (lane == 0) W[0][0] = w + w * w * acc;
+  else if (lane < LCOV_W) { const double v = pm != LVX_DEAD ? -w * cm * sc[lane] : 0.0; W[0][lane] = v; W[lane][0] = v; }
+  __syncthreads();
+  if (g.wcov) for (int e = lane; e < (int)W2; e += 64) g.wcov[(size_t)i * W2 + e] = W[e / LCOV_W][e % LCOV_W];
+  for (int e = lane; e < 3 * LCOV_W; e += 64) {
+    const int r = e / LCOV_W, b = e % LCOV_W;
+    double t = 0.0;
+    for (int a = 0; a < LCOV_W; ++a) t += J[r][a] * W[a][b];
+    T[r][b] = t;
+  }
+  __syncthreads();
+  if (lane < 9) {
+    const int r = lane / 3, s2 = lane % 3;
+    if (r >= s2) {
+      double t = 0.0;
+      for (int b = 0; b < LCOV_W; ++b) t += T[r][b] * J[s2][b];
+      Cv[r][s2] = t; Cv[s2][r] = t;
+    }
+  }
+  __syncthreads();
+  if (lane < 9 && g.pcov) g.pcov[(size_t)i * 9 + lane] = Cv[lane / 3][lane % 3];
+  if (lane < 3 && g.point) g.point[(size_t)i * 3 + lane] = Pw[lane];
+  if (lane == 0) { g.valid[i] = 1; if (g.var) g.var[i] = W[0][0]; if (g.sigma) g.sigma[i] = sqrt(W[0][0]); }
 }
 
 }  // namespace lvx

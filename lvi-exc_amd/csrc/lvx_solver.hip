@@ -23,6 +23,7 @@
 #include <dlfcn.h>
 #include <rccl/rccl.h>   // types only: the entry points are resolved with dlsym (rccl_api)
 
+#include <functional>
 #include "lvx_ctx.h"
 #include "lvx_lm_policy.h"
 #include "lvx_symeig.h"
@@ -1726,41 +1727,54 @@ int lvx_traj_cov_default_options(lvx_traj_cov_options* o) {
   o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
   return LVX_OK;
 }
-// lvx_calibration_covariance's front half with the sequential band Cholesky forced, then the selected inverse of that factor (lvx_selinv.h) and one wavefront per
-// query.  Everything is queued: t_d and the arrays of o are device addresses; flags[0] takes RES_NONUNIT, flags[1] a lost pivot (nothing written then).
-static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov& o, int* flags) {
+// lvx_calibration_covariance's front half with the sequential band Cholesky forced, then the selected inverse of that factor (lvx_selinv.h): what
+// lvx_trajectory_covariance and lvx_landmark_covariance share.  lowest(head) queues the kernel that lowers *head (started at nb) to the lowest band position a query
+// needs; wide: the band store SigW (d <= TB, lvx_ctx::d_lcov) is written beside SigB.  Everything is queued.
+struct SelInvOut { double* SigB; double* SigW; int TB; };
+static int selinv_enqueue(lvx_ctx* c, const std::string& who, double radius, int scaling, bool wide, SolveWork& w, SelInvOut* so, const std::function<void(int*)>& lowest) {
   int rc;
-  SolveWork w;
   if ((rc = solver_alloc(c, w))) return rc;
   const int nb = c->nb, bw = c->bw, nbd = c->nbd;
-  if (nbd > 96) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: border of " + std::to_string(nbd) + " scalars (up to 96 fit the one-workgroup inverse)");
+  if (nbd > 96) return fail(c, LVX_E_ARG, who + ": border of " + std::to_string(nbd) + " scalars (up to 96 fit the one-workgroup inverse)");
   const int TB = si_tb(bw), R = TB + 16, mT = TB + si_up16(nbd), M = R + si_up16(nbd);
   const size_t lds_si = ((size_t)(16 + mT) * 17 + (size_t)32 * (mT + 1) + 3 * 16 * 17) * 8;
-  if (nb > 0 && lds_si > 160 * 1024) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: half-bandwidth " + std::to_string(bw) + " too wide for the panel of the selected inverse");
+  if (nb > 0 && lds_si > 160 * 1024) return fail(c, LVX_E_ARG, who + ": half-bandwidth " + std::to_string(bw) + " too wide for the panel of the selected inverse");
   const size_t nb1 = (size_t)std::max(nb, 1);
   if ((rc = dev_alloc(c, c->d_tcov, (8 + nb1 * SI_BD + (size_t)M * M) * 8))) return rc;
+  if (wide && (rc = dev_alloc(c, c->d_lcov, nb1 * (size_t)(TB + 1) * 8))) return rc;
   int* head = (int*)c->d_tcov.p; double* SigB = (double*)c->d_tcov.p + 8; double* D = SigB + nb1 * SI_BD;
+  so->SigB = SigB; so->SigW = wide ? (double*)c->d_lcov.p : nullptr; so->TB = TB;
   hipStream_t st = c->stream;
   EvalLocal e; bool gconv = false;
   if ((rc = local_after_eval(c, w, &e, false))) return rc;   // the diagonal of THIS evaluation (queued; nothing of *e is used)
-  if ((rc = apply_diag(c, w, true, opt->jacobi_scaling, 1e-6, 1e32, e, nullptr, 0.0, &gconv))) return rc;
+  if ((rc = apply_diag(c, w, true, scaling, 1e-6, 1e32, e, nullptr, 0.0, &gconv))) return rc;
   StageTimer tm(c);
   bool bcr_used = false;
   w.lm_done = false;
-  if ((rc = reduce_to_border(c, w, opt->radius, true, &bcr_used, tm))) return rc;
+  if ((rc = reduce_to_border(c, w, radius, true, &bcr_used, tm))) return rc;
   const size_t lds_b = (size_t)2 * nbd * (nbd + 1) * 8;
   LVX_HIP(c, hipFuncSetAttribute((const void*)k_border_inv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b));
   hipLaunchKernelGGL(k_border_inv, dim3(1), dim3(SI_NT), lds_b, st, w.S, nbd, w.info);
   LVX_HIP(c, hipMemsetD32Async((hipDeviceptr_t)head, nb, 1, st));
-  const double* state_d = c->last_state_d;
   if (nb > 0) {
-    hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, head);
+    lowest(head);
     LVX_HIP(c, hipMemsetAsync(D, 0, (size_t)M * M * 8, st));
-    SelInv g{(const double*)w.L, nb, bw, w.Z, w.ldz, nbd, (const double*)w.S, D, M, SigB, (const int*)head, (const int*)w.info};
+    SelInv g{(const double*)w.L, nb, bw, w.Z, w.ldz, nbd, (const double*)w.S, D, M, SigB, (const int*)head, (const int*)w.info, so->SigW};
     LVX_HIP(c, hipFuncSetAttribute((const void*)k_band_selinv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_si));
     hipLaunchKernelGGL(k_band_selinv, dim3(1), dim3(SI_NT), lds_si, st, g);
   }
-  PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, (const double*)SigB, (const double*)w.Z, w.ldz, nb, nbd, (const double*)w.S, (const double*)w.scale,
+  return LVX_OK;
+}
+// One wavefront per query behind the selected inverse: t_d and the arrays of o are device addresses; flags[0] takes RES_NONUNIT, flags[1] a lost pivot (nothing
+// written then).
+static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov& o, int* flags) {
+  int rc;
+  SolveWork w; SelInvOut so;
+  hipStream_t st = c->stream;
+  const double* state_d = c->last_state_d;
+  if ((rc = selinv_enqueue(c, "lvx_trajectory_covariance", opt->radius, opt->jacobi_scaling, false, w, &so, [&](int* head) {
+        hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, head); }))) return rc;
+  PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, (const double*)so.SigB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale,
             (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.cov, o.sigma, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
   hipLaunchKernelGGL(k_pose_cov, dim3((unsigned)n), dim3(64), 0, st, p);
   LVX_HIP(c, hipGetLastError());
@@ -1819,6 +1833,90 @@ int lvx_trajectory_covariance(lvx_ctx* c, const lvx_traj_cov_options* opt, int f
   }
   void* dst[6] = {nullptr, out->cov, out->sigma, out->window_cov, out->window_idx, out->valid};
   for (int k = 1; k < 6; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
+  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
+  return LVX_OK;
+}
+
+int lvx_landmark_cov_default_options(lvx_landmark_cov_options* o) {
+  if (!o) return LVX_E_ARG;
+  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
+  return LVX_OK;
+}
+// The selected inverse with the wide band store, then one wavefront per queried landmark (k_landmark_cov).  ids_d (device, or null for 0 .. n - 1) and the arrays of o
+// are device addresses; flags as traj_cov_enqueue's.
+static int lm_cov_enqueue(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* ids_d, const lvx_landmark_cov& o, int* flags) {
+  int rc;
+  SolveWork w; SelInvOut so;
+  hipStream_t st = c->stream;
+  LmQuery q{};
+  q.state = c->last_state_d; q.N = c->N; q.t0 = c->t0; q.dt = c->dt; q.cam = c->cam; q.lm_uv = (const double*)c->d_lm_uv.p; q.lm_t0 = (const double*)c->d_lm_t0.p; q.L = c->L;
+  q.ord = (const int*)c->d_ord.p; q.p0s = (const int*)c->d_lm_p0.p; q.wl = c->lm_wl; q.nbd_ext = c->nbd_ext; q.ls = c->lm_ls; q.n = n; q.ids = ids_d;
+  if ((rc = selinv_enqueue(c, "lvx_landmark_covariance", opt->radius, opt->jacobi_scaling, true, w, &so, [&](int* head) {
+        q.lmH = w.lm ? (const double*)c->d_lmH.p : nullptr;
+        hipLaunchKernelGGL(k_lc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, head); }))) return rc;
+  q.lmH = w.lm ? (const double*)c->d_lmH.p : nullptr;
+  LmCov g{q, (const double*)so.SigW, so.TB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale, (const double*)w.lmd, 1.0 / opt->radius,
+          (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.var_rho, o.sigma_rho, o.point, o.point_cov, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
+  const size_t lds = (size_t)(c->lm_wl + c->nbd) * 12 + 16;
+  hipLaunchKernelGGL(k_landmark_cov, dim3((unsigned)n), dim3(64), lds, st, g);
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+static int lm_cov_args(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const lvx_landmark_cov* out) {
+  if (!c) return LVX_E_ARG;
+  if (!opt || !out || !out->valid || n <= 0 || !(opt->radius > 0) || opt->reserved != 0) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: n <= 0, radius <= 0, reserved != 0 or a required pointer is NULL");
+  if (n > c->L) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: n exceeds the number of landmarks");
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_landmark_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_landmark_covariance: the context takes part in a joint solve");
+  LVX_HIP(c, hipSetDevice(c->device));
+  return check_last_eval(c);
+}
+int lvx_landmark_covariance_d(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id_d, const lvx_landmark_cov* out_d) {
+  int rc = lm_cov_args(c, opt, n, out_d);
+  if (rc) return rc;
+  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
+    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
+    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
+  }
+  c->tcov_d_unchecked = true;
+  return lm_cov_enqueue(c, opt, n, landmark_id_d, *out_d, (int*)c->d_tj[3].p + 1);
+}
+int lvx_landmark_covariance(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id, lvx_landmark_cov* out) {
+  int rc = lm_cov_args(c, opt, n, out);
+  if (rc) return rc;
+  if (landmark_id) for (int i = 0; i < n; ++i) if (landmark_id[i] < 0 || landmark_id[i] >= c->L) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: landmark id out of range");
+  hipStream_t st = c->stream;
+  // device and pinned images (lvx_trajectory_covariance's): [ids | var_rho | sigma_rho | point | point_cov | window_cov | window_idx | valid | flags (2 ints)]
+  const size_t nn = (size_t)n, W2 = (size_t)LVX_LM_COV_W * LVX_LM_COV_W;
+  size_t off[9]; size_t cur = 0;
+  const size_t bytes[8] = {landmark_id ? nn * 4 : 0, out->var_rho ? nn * 8 : 0, out->sigma_rho ? nn * 8 : 0, out->point ? nn * 24 : 0, out->point_cov ? nn * 72 : 0,
+                           out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_LM_COV_W * 4 : 0, nn};
+  for (int k = 0; k < 8; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
+  off[8] = cur; cur += 16;
+  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
+  if (c->h_tcov_cap < cur) {
+    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
+    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
+    c->h_tcov_cap = cur;
+  }
+  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
+  if (landmark_id) { std::memcpy(h, landmark_id, nn * 4); LVX_HIP(c, hipMemcpyAsync(d, h, nn * 4, hipMemcpyHostToDevice, st)); }
+  LVX_HIP(c, hipMemsetAsync(d + off[8], 0, 16, st));
+  lvx_landmark_cov od;
+  od.var_rho = out->var_rho ? (double*)(d + off[1]) : nullptr; od.sigma_rho = out->sigma_rho ? (double*)(d + off[2]) : nullptr; od.point = out->point ? (double*)(d + off[3]) : nullptr;
+  od.point_cov = out->point_cov ? (double*)(d + off[4]) : nullptr; od.window_cov = out->window_cov ? (double*)(d + off[5]) : nullptr;
+  od.window_idx = out->window_idx ? (int32_t*)(d + off[6]) : nullptr; od.valid = (uint8_t*)(d + off[7]);
+  if ((rc = lm_cov_enqueue(c, opt, n, landmark_id ? (const int32_t*)d : nullptr, od, (int*)(d + off[8])))) return rc;
+  LVX_HIP(c, hipMemcpyAsync(h + off[1], d + off[1], cur - off[1], hipMemcpyDeviceToHost, st));
+  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
+  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
+  int fl[2]; std::memcpy(fl, h + off[8], 8);
+  if (fl[1]) {
+    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
+    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
+  }
+  void* dst[8] = {nullptr, out->var_rho, out->sigma_rho, out->point, out->point_cov, out->window_cov, out->window_idx, out->valid};
+  for (int k = 1; k < 8; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
   if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
   return LVX_OK;
 }

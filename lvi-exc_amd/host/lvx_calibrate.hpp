@@ -70,8 +70,12 @@ struct CalibrateOptions {
   double covariance_radius = 1e8;  // the radius of the damped system the covariance belongs to (what it means)
   double trajectory_covariance_step = 0;   // seconds, 0 = off: lvx_trajectory_covariance of the pose at every stage's final state, sampled with SampleTimes over the IMU span (the same evaluation as `covariance`, the same radius): StageReport::trajectory_sigma
   int trajectory_covariance_frame = LVX_FRAME_LIDAR;   // the frame of those poses.  A stage that locks the trajectory and a sensor's extrinsics (the camera-surfel stage: LiDAR) reports exact zeros for that sensor's frame
+  bool landmark_covariance = false;   // lvx_landmark_covariance of every landmark at every stage's final state (the same evaluation as `covariance`, the same radius): StageReport::landmark_sigma.  A stage that holds the landmarks constant carries no record
   int verbose = 1;
 };
+// lvx_landmark_covariance over a list of landmarks: var_rho / sigma_rho [n] (inverse depth), point [n][3] (world), point_cov [n][9], valid [n]; rho [n] the inverse depths
+// themselves where the caller gave the state (empty otherwise)
+struct LandmarkUncertainty { double radius = 0; std::vector<int32_t> ids; std::vector<double> rho, var_rho, sigma_rho, point, point_cov; std::vector<uint8_t> valid; };
 // lvx_trajectory_covariance over a list of times: cov [n][36], sigma [n][6] (metres, RADIANS), valid [n]
 struct TrajectoryUncertainty { int frame = 0; double radius = 0; std::vector<double> t, cov, sigma; std::vector<uint8_t> valid; };
 struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_surfel_points = 0, n_cam_surfel = 0;
@@ -81,6 +85,7 @@ struct StageReport { std::string name; lvx_lm_summary lm; int n_planes = 0, n_su
                      int init_prefix = -1; lvx_rotinit_result init{};   // the "Initialization" report (CalibrateOptions::init_lidar_rotation): index into InitializationPrefixes and the record that passed
                      bool has_covariance = false; lvx_calib_cov covariance{};   // CalibrateOptions::covariance: the record at the state the stage's solve ended at (false: the option is off, or the call reported LVX_E_NOTPD)
                      bool has_trajectory_sigma = false; TrajectoryUncertainty trajectory_sigma;   // CalibrateOptions::trajectory_covariance_step: pose sigmas (trajectory_covariance_frame) along the spline at the stage's final state (false: off, or LVX_E_NOTPD)
+                     bool has_landmark_sigma = false; LandmarkUncertainty landmark_sigma;   // CalibrateOptions::landmark_covariance: every landmark at the stage's final state (false: off, the stage holds the landmarks constant, or LVX_E_NOTPD)
                      int n_lidar_poses = 0; lvx_family_stats lidar_pos_before{}, lidar_pos_after{}; };   // trajInitFromLidarPose: blocks attached; with error_statistics, lvx_lidar_pose_statistics around the solve
 // what one DataAssociation round produced (kept when CalibrateOptions::keep_history): the state it ran at, the surfel map, the full SurfelPoint list and —
 // keep_clouds — the de-skewed scans [n_scans][H][W][4]
@@ -245,6 +250,40 @@ inline std::string FormatTrajectoryUncertainty(const TrajectoryUncertainty& r) {
   char buf[512];
   std::snprintf(buf, sizeof buf, "[Trajectory] position std (m): worst %.6e at t = %.6f, median %.6e (%d valid samples, radius %.6e)\n[Trajectory] rotation std (deg): worst %.6e at t = %.6f, median %.6e\n",
                 sp[wp], r.t[at[wp]], median(sp), (int)sp.size(), r.radius, deg * sr[wr], r.t[at[wr]], deg * median(sr));
+  return buf;
+}
+// lvx_landmark_covariance at the normal equations (and the state) of the context's last LVX_EVAL_NORMAL_EQ evaluation; ids empty: every landmark in order; opts = nullptr:
+// the defaults; state (the one of that evaluation): fills LandmarkUncertainty::rho, which FormatLandmarkUncertainty divides by
+inline LandmarkUncertainty LandmarkCovariance(lvx_ctx* ctx, const std::vector<int32_t>& ids = {}, const lvx_landmark_cov_options* opts = nullptr, const std::vector<double>* state = nullptr) {
+  LandmarkUncertainty r; r.ids = ids;
+  lvx_landmark_cov_options o; lvx_landmark_cov_default_options(&o);
+  if (opts) o = *opts;
+  r.radius = o.radius;
+  lvx_layout lo{};
+  ThrowOnError(ctx, lvx_get_layout(ctx, &lo));
+  if (ids.empty()) { r.ids.resize((size_t)std::max(lo.n_landmarks, 0)); for (size_t i = 0; i < r.ids.size(); ++i) r.ids[i] = (int32_t)i; }
+  const size_t n = r.ids.size();
+  if (n == 0) return r;
+  r.var_rho.assign(n, 0.0); r.sigma_rho.assign(n, 0.0); r.point.assign(3 * n, 0.0); r.point_cov.assign(9 * n, 0.0); r.valid.assign(n, 0);
+  lvx_landmark_cov out{r.var_rho.data(), r.sigma_rho.data(), r.point.data(), r.point_cov.data(), nullptr, nullptr, r.valid.data()};
+  ThrowOnError(ctx, lvx_landmark_covariance(ctx, &o, (int)n, ids.empty() ? nullptr : r.ids.data(), &out));
+  if (state) { r.rho.resize(n); for (size_t i = 0; i < n; ++i) r.rho[i] = state->at(7 * (size_t)lo.n_knots + 32 + (size_t)r.ids[i]); }
+  return r;
+}
+// What a user reads off it, one line: the median and the largest relative depth sigma, sigma_rho / |rho| (to first order the relative sigma of the depth 1 / rho), over
+// the valid landmarks, and which landmark is the worst.  Without LandmarkUncertainty::rho the sigmas of the inverse depth themselves.
+//   [Landmarks] relative depth std: median a, max b at landmark l (n valid of m, radius r)
+inline std::string FormatLandmarkUncertainty(const LandmarkUncertainty& r) {
+  std::vector<double> rel; std::vector<size_t> at;
+  const bool have_rho = r.rho.size() == r.valid.size();
+  for (size_t i = 0; i < r.valid.size(); ++i) if (r.valid[i]) { rel.push_back(have_rho ? r.sigma_rho[i] / std::fabs(r.rho[i]) : r.sigma_rho[i]); at.push_back(i); }
+  if (rel.empty()) return "[Landmarks] no valid landmark\n";
+  const size_t w = (size_t)(std::max_element(rel.begin(), rel.end()) - rel.begin());
+  std::vector<double> v = rel;
+  std::nth_element(v.begin(), v.begin() + v.size() / 2, v.end());
+  char buf[320];
+  std::snprintf(buf, sizeof buf, "[Landmarks] %s std: median %.6e, max %.6e at landmark %d (%d valid of %d, radius %.6e)\n", have_rho ? "relative depth" : "inverse depth",
+                v[v.size() / 2], rel[w], (int)r.ids[at[w]], (int)rel.size(), (int)r.valid.size(), r.radius);
   return buf;
 }
 struct PoseComparison { lvx_pose_errors errors{}; std::vector<double> abs_trans, abs_rot; };
@@ -700,9 +739,10 @@ class Calibrator {
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_before_));
     check(lvx_lm_solve(ctx_, state->data(), &o, &s));
     if (opt_.error_statistics) check(lvx_error_statistics(ctx_, state->data(), &stats_after_));
-    has_cov_ = false; has_tsig_ = false;
+    has_cov_ = false; has_tsig_ = false; has_lsig_ = false;
     const bool want_tsig = opt_.trajectory_covariance_step > 0 && !in_.imu_t.empty();
-    if (opt_.covariance || want_tsig) {   // the normal equations at the final state (the loop's last ones may belong to a rejected candidate), then the calls
+    const bool want_lsig = opt_.landmark_covariance && !in_.lm_t0.empty();
+    if (opt_.covariance || want_tsig || want_lsig) {   // the normal equations at the final state (the loop's last ones may belong to a rejected candidate), then the calls
       double cost = 0.0;
       check(lvx_evaluate(ctx_, state->data(), LVX_EVAL_COST | LVX_EVAL_NORMAL_EQ, &cost, nullptr));
     }
@@ -715,6 +755,21 @@ class Calibrator {
       const int rc = times.empty() ? LVX_OK : lvx_trajectory_covariance(ctx_, &to, opt_.trajectory_covariance_frame, (int)times.size(), times.data(), &out);
       if (rc == LVX_E_NOTPD) { if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] trajectory covariance: %s\n", lvx_last_error(ctx_)); }   // no record for this stage; the calibration goes on
       else { check(rc); has_tsig_ = true; if (opt_.verbose) std::fputs(FormatTrajectoryUncertainty(tsig_).c_str(), stderr); }
+    }
+    if (want_lsig) {
+      lvx_landmark_cov_options lo; lvx_landmark_cov_default_options(&lo); lo.radius = opt_.covariance_radius;
+      const size_t L = in_.lm_t0.size();
+      lsig_ = LandmarkUncertainty{}; lsig_.radius = lo.radius; lsig_.ids.resize(L); lsig_.rho.resize(L);
+      for (size_t l = 0; l < L; ++l) { lsig_.ids[l] = (int32_t)l; lsig_.rho[l] = (*state)[7 * (size_t)in_.n_knots + 32 + l]; }
+      lsig_.var_rho.assign(L, 0.0); lsig_.sigma_rho.assign(L, 0.0); lsig_.point.assign(3 * L, 0.0); lsig_.point_cov.assign(9 * L, 0.0); lsig_.valid.assign(L, 0);
+      lvx_landmark_cov out{lsig_.var_rho.data(), lsig_.sigma_rho.data(), lsig_.point.data(), lsig_.point_cov.data(), nullptr, nullptr, lsig_.valid.data()};
+      const int rc = lvx_landmark_covariance(ctx_, &lo, (int)L, nullptr, &out);
+      if (rc == LVX_E_NOTPD) { if (opt_.verbose) std::fprintf(stderr, "[lvx calibrate] landmark covariance: %s\n", lvx_last_error(ctx_)); }   // no record for this stage; the calibration goes on
+      else {
+        check(rc);
+        has_lsig_ = std::find(lsig_.valid.begin(), lsig_.valid.end(), (uint8_t)1) != lsig_.valid.end();   // none valid: the stage holds the landmarks constant
+        if (has_lsig_ && opt_.verbose) std::fputs(FormatLandmarkUncertainty(lsig_).c_str(), stderr);
+      }
     }
     if (opt_.covariance) {
       lvx_calib_cov_options co; lvx_calib_cov_default_options(&co); co.radius = opt_.covariance_radius;
@@ -734,6 +789,7 @@ class Calibrator {
     r->has_stats = opt_.error_statistics; r->stats_before = stats_before_; r->stats_after = stats_after_;
     r->has_covariance = has_cov_; r->covariance = cov_;
     r->has_trajectory_sigma = has_tsig_; r->trajectory_sigma = tsig_;
+    r->has_landmark_sigma = has_lsig_; r->landmark_sigma = has_lsig_ ? lsig_ : LandmarkUncertainty{};
   }
   void check(int rc) {
     if (rc == LVX_OK) return;
@@ -769,6 +825,7 @@ class Calibrator {
   lvx_error_stats stats_before_{}, stats_after_{};
   bool has_cov_ = false; lvx_calib_cov cov_{};
   bool has_tsig_ = false; TrajectoryUncertainty tsig_;
+  bool has_lsig_ = false; LandmarkUncertainty lsig_;
 };
 
 }  // namespace lvx_host

@@ -112,6 +112,19 @@ class TrajCov(C.Structure):
     _fields_ = [("cov", C.c_void_p), ("sigma", C.c_void_p), ("window_cov", C.c_void_p), ("window_idx", C.c_void_p), ("valid", C.c_void_p)]
 
 
+LM_COV_W = 32   # window of lvx_landmark_covariance: the landmark's inverse depth, then the 31 scalars of the camera-frame pose at its reference time
+
+
+class LandmarkCovOptions(C.Structure):
+    _fields_ = [("radius", C.c_double), ("jacobi_scaling", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LandmarkCov(C.Structure):
+    """lvx_landmark_cov: host or device addresses; a NULL member (but valid) is not computed."""
+    _fields_ = [("var_rho", C.c_void_p), ("sigma_rho", C.c_void_p), ("point", C.c_void_p), ("point_cov", C.c_void_p), ("window_cov", C.c_void_p), ("window_idx", C.c_void_p),
+                ("valid", C.c_void_p)]
+
+
 N_SHARED = 14   # the shared extrinsic scalars of a joint solve: canonical slot k = c - 8
 
 
@@ -494,6 +507,44 @@ class Context:
         r = TrajCov(*[out_d_ptrs.get(f) for f in ("cov", "sigma", "window_cov", "window_idx")], valid_d_ptr)
         opt = self._traj_cov_options(radius, jacobi_scaling)
         self._ck(self._l.lvx_trajectory_covariance_d(self._h, C.byref(opt), C.c_int(frame), C.c_int(n), C.c_void_p(t_d_ptr), C.byref(r)))
+
+    def _landmark_cov_options(self, radius, jacobi_scaling):
+        opt = LandmarkCovOptions()
+        self._l.lvx_landmark_cov_default_options(C.byref(opt))
+        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
+        return opt
+
+    def landmark_covariance(self, radius=1e8, jacobi_scaling=True, ids=None, window=True):
+        """Uncertainty of the landmarks `ids` (default: all, in order) in the DAMPED system of the last evaluate(normal_eq=True), at the state of that evaluation
+        (lvx_landmark_covariance).  Returns a dict: var_rho [n], sigma_rho [n] (inverse depth), point [n, 3] (world), point_cov [n, 3, 3], valid [n] bool; with
+        window=True also window_cov [n, 32, 32] over (rho, the 31 scalars of the camera-frame pose at the reference time) and window_idx [n, 32] (tangent index, -1
+        constant or absent).  An invalid entry (constant landmark, no reference pose) holds zeros.  A non-unit control quaternion raises LvxError(E_NONUNIT_QUAT) whose
+        `partial` attribute is that dict."""
+        n = getattr(self, "_n_landmarks", 0) if ids is None else len(ids)
+        ids = None if ids is None else _i(np.atleast_1d(ids))
+        out = dict(var_rho=np.zeros(n), sigma_rho=np.zeros(n), point=np.zeros((n, 3)), point_cov=np.zeros((n, 3, 3)))
+        if window:
+            out["window_cov"] = np.zeros((n, LM_COV_W, LM_COV_W))
+            out["window_idx"] = np.full((n, LM_COV_W), -1, np.int32)
+        valid = np.zeros(n, np.uint8)
+        r = LandmarkCov(out["var_rho"].ctypes.data, out["sigma_rho"].ctypes.data, out["point"].ctypes.data, out["point_cov"].ctypes.data,
+                        out["window_cov"].ctypes.data if window else None, out["window_idx"].ctypes.data if window else None, valid.ctypes.data)
+        opt = self._landmark_cov_options(radius, jacobi_scaling)
+        rc = self._l.lvx_landmark_covariance(self._h, C.byref(opt), C.c_int(n), _p(ids) if ids is not None else None, C.byref(r))
+        out["valid"] = valid.astype(bool)
+        if rc == E_NONUNIT_QUAT:
+            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
+            e.partial = out
+            raise e
+        self._ck(rc)
+        return out
+
+    def landmark_covariance_d(self, ids_d_ptr, n, out_d_ptrs, valid_d_ptr, radius=1e8, jacobi_scaling=True):
+        """lvx_landmark_covariance_d: device addresses (ids_d_ptr 0 / None: landmarks 0 .. n - 1); out_d_ptrs maps "var_rho" / "sigma_rho" / "point" / "point_cov" /
+        "window_cov" / "window_idx" to addresses (absent: not computed).  Only enqueues; synchronize() reports a lost pivot or a non-unit quaternion."""
+        r = LandmarkCov(*[out_d_ptrs.get(f) for f in ("var_rho", "sigma_rho", "point", "point_cov", "window_cov", "window_idx")], valid_d_ptr)
+        opt = self._landmark_cov_options(radius, jacobi_scaling)
+        self._ck(self._l.lvx_landmark_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(ids_d_ptr) if ids_d_ptr else None, C.byref(r)))
 
     def lm_solve(self, state, max_iterations=50, **kw):
         """TrajectoryEstimator::Solve(max_iterations) equivalent.  Returns (state, summary dict with per-iteration history)."""
