@@ -273,7 +273,9 @@ int lvx_synchronize(lvx_ctx* ctx);
 #define LVX_KERNEL_FIXUP 16         /* the exact per-segment kernel over the fused kernels' fallback lists (lvx_layout::fallback_rows), all families */
 #define LVX_NUM_KERNELS 17          /* entries lvx_get_kernel_ms writes: unchanged, callers size their arrays by it */
 #define LVX_KERNEL_LIDAR_POS 17     /* the per-segment kernel over the LiDAR-pose blocks: beyond LVX_NUM_KERNELS, read with lvx_get_kernel_ms_ext */
-#define LVX_NUM_KERNELS_EXT 18
+#define LVX_KERNEL_POSE_COV 18      /* k_pose_cov of lvx_trajectory_covariance (the selected inverse in front of it is not part of the record) */
+#define LVX_KERNEL_POINT_COV 19     /* k_pt_hub + k_point_cov of lvx_map_point_covariance (likewise) */
+#define LVX_NUM_KERNELS_EXT 20
 /* enable: 0 off | 1 every launch | 2 + k: only the launches of kernel k (e.g. 2 + LVX_FAM_SURFEL: the dominant kernel — two event
  * records per pass instead of ~20, which cost ~5 % of a config-4 pass).  While profiling is on, passes are issued launch by launch (no graph replay). */
 int lvx_set_profiling(lvx_ctx* ctx, int enable);
@@ -412,6 +414,48 @@ int lvx_landmark_covariance(lvx_ctx* ctx, const lvx_landmark_cov_options* opt, i
 /* landmark_id_d and the arrays of out_d are DEVICE addresses; only enqueues on the context's stream.  An id outside [0, L) is an invalid entry; a lost pivot (nothing
  * written) or a non-unit quaternion is reported by the next lvx_synchronize. */
 int lvx_landmark_covariance_d(lvx_ctx* ctx, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id_d, const lvx_landmark_cov* out_d);
+
+/* Uncertainty of LiDAR MAP POINTS in the same damped system: how far a scan point moves in the map under the uncertainty of the trajectory and of q_LI, p_LI, tau_L.
+ * A point p_L measured at t is placed in the LiDAR frame at t_map as lvx_get_scans_in_map, lvx_undistort_scan and lvx_render_map_d place it,
+ *   p_M = T_L(t_map)^-1 T_L(t) p_L,   T_L(t) the LVX_FRAME_LIDAR pose at t + tau_L   (LiDARSurfelPoint::reprojectPoint2map),
+ * with t_map the context's, as the surfel / camera-surfel families set it.  With a plane normal as dir3, var_dir is the predicted variance of that surfel row.
+ * Contract of lvx_trajectory_covariance word for word: the last LVX_EVAL_NORMAL_EQ evaluation at its state, its error word read first, LVX_E_STATE without one or on a
+ * context of a joint solve, copies only, one host stop, always the sequential factor, LVX_E_NOTPD writes nothing, LVX_E_NONUNIT_QUAT with the rest filled, all sums in
+ * a fixed order: a point's record is the same bits alone, in any batch and at any position of the input.  Times arrive in any order.
+ *   window_idx[i][0..23]: the four knots of the pose at t + tau_L, [24..47]: the four knots of the pose at t_map + tau_L, [48..54]: the LiDAR's theta (3), p (3),
+ *     tau (1); -1 constant.  A time inside the window of t_map repeats indices in both knot groups: the window is gathered by index, so that is exact.
+ *   window_cov[i] = Sigma over those 55 scalars (zero rows / columns at -1): rows 0..23 + 48..54 are lvx_trajectory_covariance's LVX_FRAME_LIDAR window at t, rows
+ *     24..47 + 48..54 the one at t_map, bit for bit.  12 KB per point: for tests and small n.
+ *   cov[i] = J window_cov[i] J^T, J (3 x 55) the derivative of p_M (lvi-exc_amd/csrc/lvx_ptcov.h); sigma = sqrt of its diagonal (metres); sigma_max = sqrt of its
+ *     largest eigenvalue; var_dir = dir^T cov dir, written only when dir3 is given.  The product is formed from the two poses' 6 x 6 blocks (the one at t_map once per
+ *     call), whose terms cancel as t approaches t_map, where the point stops moving: the absolute error of cov is a few eps of the variance the pose at t alone would
+ *     give the point (1e-10 m in sigma), and at t = t_map a diagonal entry of -1e-21 can come out; sigma and sigma_max count it as zero.
+ * valid = 0 (zeros, window_idx -1) for a point whose time is outside the trajectory or whose coordinates are not finite; the others are unaffected.  A point all of
+ * whose scalars are constant under the lock mask is valid with cov exactly zero.
+ * LVX_E_STATE also when no surfel / camera-surfel family has set t_map, and when a free knot scalar of the pose at t_map + tau_L is a band position of the factor
+ * rather than a border slot (the hub knots are laid out around t_map; a locked tau_L far from zero leaves them): its cross terms are off the factor's pattern, and the
+ * call refuses (nothing written) rather than return zeros.  LVX_E_ARG: NULL context / options / points / t / out / valid, n <= 0, radius <= 0, reserved != 0, and the
+ * LDS limits of lvx_trajectory_covariance. */
+typedef struct lvx_point_cov_options { double radius; int32_t jacobi_scaling; int32_t reserved; } lvx_point_cov_options;   /* 1e8, 1, 0 */
+#define LVX_PT_COV_W 55
+typedef struct lvx_point_cov {
+  double*  point;      /* [n][3] p_M, LiDAR frame at t_map; may be NULL */
+  double*  cov;        /* [n][9] row-major; may be NULL */
+  double*  sigma;      /* [n][3] metres; may be NULL */
+  double*  sigma_max;  /* [n]; may be NULL */
+  double*  var_dir;    /* [n]; written only when dir3 is given; may be NULL */
+  double*  window_cov; /* [n][55 * 55]; may be NULL */
+  int32_t* window_idx; /* [n][55] tangent index, -1 = constant; may be NULL */
+  uint8_t* valid;      /* [n] */
+} lvx_point_cov;
+int lvx_point_cov_default_options(lvx_point_cov_options* opt);
+/* pt_lidar3 [n][3], t [n], dir3 [n][3] or NULL (directions in the map frame, e.g. unit plane normals) */
+int lvx_map_point_covariance(lvx_ctx* ctx, const lvx_point_cov_options* opt, int n, const double* pt_lidar3, const double* t, const double* dir3, lvx_point_cov* out);
+/* DEVICE addresses; only enqueues on the context's stream.  A lost pivot or a t_map window off the border (nothing written) or a non-unit quaternion is reported by the
+ * next lvx_synchronize. */
+int lvx_map_point_covariance_d(lvx_ctx* ctx, const lvx_point_cov_options* opt, int n, const double* pt3_d, const double* t_d, const double* dir3_d, const lvx_point_cov* out_d);
+/* the same for points in the scan buffers' layout: xyzi4_d [n][4] float (x, y, z, intensity), 16-byte aligned; no directions */
+int lvx_map_point_covariance_xyzi_d(lvx_ctx* ctx, const lvx_point_cov_options* opt, int n, const float* xyzi4_d, const double* t_d, const lvx_point_cov* out_d);
 
 /* x (+) delta with ceres::EigenQuaternionParameterization::Plus on quaternion blocks */
 int lvx_plus(lvx_ctx* ctx, const double* state, const double* delta, double* state_out);

@@ -22,6 +22,7 @@ const SwitchName* switch_table(int* count) {
     {"TEST_BAD_PIVOT", &Switches::test_bad_pivot, false},   // lvx_solve_step: declare a pivot failure where there was none (the tests' way into the sequential redo)
     {"TEST_COMPACT_ONE", &Switches::test_compact_one, false},   // surfel_compact_launch: k_surfel_compact (one workgroup) whatever the co-residency bound says
     {"TEST_LM_SCHUR_ONE", &Switches::test_lm_schur_one, false},   // solve_local: k_lm_schur (one workgroup per landmark) whatever the LDS size of the group panel says
+    {"PTCOV_VALU", &Switches::ptcov_valu, false},   // lvx_map_point_covariance: the per-lane product instead of the MFMA tiles (tools/ptcov_profile.py measures both)
   };
   *count = (int)(sizeof(tab) / sizeof(tab[0]));
   return tab;
@@ -122,7 +123,7 @@ void lvx_destroy(lvx_ctx* c) {
   handoff_destroy(c);
   traj_destroy(c);
   rotinit_destroy(c);
-  for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv, &c->d_ccov, &c->d_tcov, &c->d_tcov_io, &c->d_lcov}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv, &c->d_ccov, &c->d_tcov, &c->d_tcov_io, &c->d_lcov, &c->d_ptcov}) if (b->p) (void)hipFree(b->p);
   if (c->h_tcov) (void)hipHostFree(c->h_tcov);
   for (auto& e : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);

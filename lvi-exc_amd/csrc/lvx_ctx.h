@@ -67,7 +67,7 @@ struct DevBuf {
 // Experiment / debug switches: read ONCE from the environment (LVX_<NAME>) when the context is created and changed afterwards only
 // through lvx_set_switch — the evaluation and solve paths never call getenv.
 struct Switches {
-  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0, test_bad_pivot = 0, test_compact_one = 0, test_lm_schur_one = 0, imu_fixed_slices = 0;   // imu_fixed_slices: the wavefronts of k_imu_own take fixed 64-sample slices of a batch instead of the window-balanced ones (measurement); test_lm_schur_one: the tests' way into k_lm_schur (one workgroup per landmark) on problems whose group panel fits the LDS; test_compact_one: the tests' way into k_surfel_compact (the single-workgroup plane compaction) on a device whose co-residency bound no test map exceeds; test_bad_pivot: the tests' way into the solver's failed-pivot branch (a failure is declared where there was none); rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
+  int force_legacy = 0, serial = 0, no_graph = 0, deterministic = 0, clear_all = 0, solver_seq = 0, solver_timing = 0, chunk_r = 0, chunk_r_imu = 0, chunk_r_rep = 0, chunk_rows = 0, rep_rows = 0, da_sync = 0, rep_fused = 0, solver_nd = 0, test_bad_pivot = 0, test_compact_one = 0, test_lm_schur_one = 0, imu_fixed_slices = 0, ptcov_valu = 0;   // imu_fixed_slices: the wavefronts of k_imu_own take fixed 64-sample slices of a batch instead of the window-balanced ones (measurement); test_lm_schur_one: the tests' way into k_lm_schur (one workgroup per landmark) on problems whose group panel fits the LDS; test_compact_one: the tests' way into k_surfel_compact (the single-workgroup plane compaction) on a device whose co-residency bound no test map exceeds; test_bad_pivot: the tests' way into the solver's failed-pivot branch (a failure is declared where there was none); rep_fused: 1 = the single-launch reprojection kernel (k_reproj_fused; measured slower, opt-in), otherwise the five-launch chain
 };
 struct SwitchName { const char* name; int Switches::*field; bool relayout; };
 const SwitchName* switch_table(int* count);
@@ -161,6 +161,7 @@ struct lvx_ctx {
   lvx::DevBuf d_ccov;         // lvx_calibration_covariance: the record k_calib_cov writes (LVX_CCOV_N doubles); ..._shared: record, kept factor and message of k_joint_cov_*
   lvx::DevBuf d_tcov, d_tcov_io; void* h_tcov = nullptr; size_t h_tcov_cap = 0; bool tcov_d_unchecked = false;   // lvx_trajectory_covariance: [lowest band position | selected band | ring of k_band_selinv], [times | outputs] of the host form and their pinned mirror; a _d call awaits lvx_synchronize's look at its pivot word
   lvx::DevBuf d_lcov;         // lvx_landmark_covariance: the wide band store of the selected inverse, SigW [nb][TB + 1] (its staging and flag words are lvx_trajectory_covariance's)
+  lvx::DevBuf d_ptcov;        // lvx_map_point_covariance: the record k_pt_hub leaves for k_point_cov (lvx::PtHub; staging and flag words are lvx_trajectory_covariance's)
   lvx::DevBuf d_bcrD, d_bcrG, d_bcrInfo, d_Y2, d_gram, d_bcrLinv; bool bcr_linv = false;   // d_bcrLinv: inverses of the factors' 16 x 16 diagonal triangles (k_potrf_batched -> k_trsm_reg)
   void* blas = nullptr;
   int bcr_b = 0, bcr_nblk = 0, bcr_nreal = 0;

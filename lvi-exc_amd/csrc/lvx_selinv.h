@@ -1,5 +1,5 @@
 // lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and what is read from it: pose covariances (lvx_trajectory_covariance) and
-// landmark covariances (lvx_landmark_covariance, at the end of the file).
+// landmark covariances (lvx_landmark_covariance) and LiDAR map point covariances (lvx_map_point_covariance, at the end of the file).
 // Included by lvx_solver.hip (its translation unit holds the factor's kernels).
 //
 // reduce_to_border(force_seq) leaves   Lb[j (bw + 1) + d] = L(j + d, j)   (band Cholesky),   Z[r ldz + j] = (L^-1 A_bc)(j, r)   and   S = A_cc - Zc^T Zc (unfactored),
@@ -18,6 +18,7 @@
 #pragma once
 #include "lvx_chol16.h"
 #include "lvx_lmcov.h"
+#include "lvx_ptcov.h"
 
 namespace lvx {
 
@@ -429,6 +430,296 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
   if (lane < 9 && g.pcov) g.pcov[(size_t)i * 9 + lane] = Cv[lane / 3][lane % 3];
   if (lane < 3 && g.point) g.point[(size_t)i * 3 + lane] = Pw[lane];
   if (lane == 0) { g.valid[i] = 1; if (g.var) g.var[i] = W[0][0]; if (g.sigma) g.sigma[i] = sqrt(W[0][0]); }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// lvx_map_point_covariance (lvx_ptcov.h has the algebra).  A map is 1e5 .. 1e6 points per call, so a LANE owns a point here, not a wavefront.
+//   k_pt_hub     once per call, one wavefront: the pose Jacobian J0 at t_map + tau_L, its window W00 (hub knots and the LiDAR's scalars: border x border) and
+//                C00 = J0 W00 J0^T, exactly as k_pose_cov forms them.  It also decides what makes the whole call fail: a lost pivot (status 1), a scalar of the t_map
+//                window that is a BAND position — its cross terms with a point's knots would be off the factor's pattern (status 2).
+//   k_point_cov  256 points per workgroup.  Every lane evaluates its own pose Jacobian and Gk = A_k Jk (3 x 31, registers).  The windows depend on the knot interval
+//                only: the workgroup walks the DISTINCT intervals of its points in ascending order (an integer minimum in LDS — times may arrive in any order), stages
+//                Wkk (32 x 32 padded), Wk0 and B0 = Wk0 J0^T (32 x 16 padded) once per interval, and the lanes of that interval take their turn: per wavefront and
+//                group of 16 lanes, T = Gk [Wkk | B0] is 3 row tiles x 3 column tiles x 8 steps of v_mfma_f64_16x16x4_f64 (tile row = point, one tile per row of
+//                Gk), staged through a 16-point tile in LDS that first holds Gk and then T; pt_cov_assemble finishes in registers.
+// A point's bits depend on its own inputs and on its interval's windows only — every sum has a fixed order and an MFMA row never sees another row — so they are the
+// same alone, in any batch and at any position.  No atomics on floating-point data.  512 registers (one wavefront per SIMD); the compiler spills 718 of them to
+// scratch (780 bytes per lane) around the pose evaluation in front of the loop.
+// ---------------------------------------------------------------------------------------------------------
+#define PC_NT 256
+#define PC_TS 115        // doubles per point of a wavefront's tile: Gk as [3][32] (96), then T as [3][PCOV_TW] (114); odd, so 16 points spread over the banks
+struct PtAccess { const int* ord; const double* SigB; const double* Z; int ldz, nb, nbd; const double* Scc; const double* scale; };
+// Sigma' (scaled) between two live positions, as k_pose_cov reads it: >= 0 a band position, < 0 border slot -1 - o
+__device__ __forceinline__ double pc_sigma(const PtAccess& s, int pa, int pb) {
+  if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; return d < SI_BD ? s.SigB[(size_t)lo * SI_BD + d] : 0.0; }
+  if (pa >= 0) return s.Z[(size_t)(-1 - pb) * s.ldz + pa];
+  if (pb >= 0) return s.Z[(size_t)(-1 - pa) * s.ldz + pb];
+  const int ra = -1 - pa, rb = -1 - pb;
+  return s.Scc[(size_t)max(ra, rb) * s.nbd + min(ra, rb)];
+}
+__device__ __forceinline__ double pc_scale(const PtAccess& s, int o) { return o == LVX_DEAD ? 0.0 : s.scale[o >= 0 ? o : s.nb + (-1 - o)]; }
+struct PtHub {   // what k_pt_hub leaves for k_point_cov
+  double J0[6][32];                 // column 31 zero
+  double W00[TCOV_W][TCOV_W];
+  double C00[36], q0[4], p0[3], sc[TCOV_W];
+  int pos[TCOV_W], idx[TCOV_W];     // ord[] of the window's scalars; their tangent indices, -1 constant
+  int status;                       // 0 ok, 1 a lost pivot, 2 the window of t_map is off the border, 3 a non-unit control quaternion at t_map (every point is invalid)
+};
+struct PtCov {
+  const double* state; int N; double t0, dt, t_map; int n;
+  const double* pt; const float* xyzi; const double* t; const double* dir;   // pt [n][3] or xyzi [n][4] (the scan buffers' layout)
+  PtAccess s; const int* info; int force_bad; PtHub* hub;
+  double* point; double* cov; double* sigma; double* sigma_max; double* var_dir; double* wcov; int32_t* widx; uint8_t* valid; int* flag; int* bad;
+};
+__device__ __forceinline__ SensorCal pc_lidar(const PtCov& g) {
+  const double* ss = g.state + 7 * (size_t)g.N + 16;
+  SensorCal ext; ext.q = load_q(ss); ext.p = load_v3(ss + 4); ext.tau = ss[7];
+  return ext;
+}
+__global__ __launch_bounds__(64) void k_pt_hub(PtCov g) {
+  __shared__ double J[6][TCOV_W], W[TCOV_W][TCOV_W + 1], T[6][TCOV_W], sc[TCOV_W], Cv[6][6];
+  __shared__ int idx[TCOV_W], pos[TCOV_W], status;
+  const int lane = threadIdx.x;
+  PtHub* h = g.hub;
+  if (g.force_bad || g.info[0] != 0 || g.info[1] != 0) { if (lane == 0) { h->status = 1; *g.bad = 1; } return; }   // a lost pivot: nothing is written
+  if (lane == 0) {
+    const SplineRef sp{g.t0, g.dt, g.N, g.state, g.state + 3 * (size_t)g.N};
+    const SensorCal ext = pc_lidar(g);
+    int st = traj_pose_jacobian(sp, 1, ext, g.t_map + ext.tau, J, idx);
+    quat q0; v3 p0;
+    if (st == RES_OK && pt_lidar_pose(sp, ext, g.t_map + ext.tau, &q0, &p0) != RES_OK) st = RES_NONUNIT;
+    if (st == RES_OK) { h->q0[0] = q0.x; h->q0[1] = q0.y; h->q0[2] = q0.z; h->q0[3] = q0.w; h->p0[0] = p0.x; h->p0[1] = p0.y; h->p0[2] = p0.z; }
+    status = st;
+  }
+  __syncthreads();
+  if (status == RES_RANGE) { if (lane == 0) { h->status = 2; *g.bad = 2; } return; }   // t_map + tau_L has left the trajectory
+  if (status == RES_NONUNIT) { if (lane == 0) { h->status = 3; *g.flag = RES_NONUNIT; } return; }
+  int o = LVX_DEAD;
+  if (lane < TCOV_W) {
+    int id = -1;
+    o = g.s.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane];
+    pos[lane] = o; sc[lane] = pc_scale(g.s, o);
+    h->pos[lane] = o; h->idx[lane] = id; h->sc[lane] = sc[lane];
+  }
+  if (__any(lane < 24 && o != LVX_DEAD && o >= 0)) { if (lane == 0) { h->status = 2; *g.bad = 2; } return; }   // a free knot scalar of the t_map window in the band
+  __syncthreads();
+  for (int e = lane; e < TCOV_W * TCOV_W; e += 64) {
+    const int a = e / TCOV_W, b = e % TCOV_W;
+    const int pa = pos[a], pb = pos[b];
+    double v = 0.0;
+    if (pa != LVX_DEAD && pb != LVX_DEAD) { v = pc_sigma(g.s, pa, pb); v *= sc[a] * sc[b]; }
+    W[a][b] = v; h->W00[a][b] = v;
+  }
+  for (int e = lane; e < 6 * 32; e += 64) h->J0[e >> 5][e & 31] = (e & 31) < TCOV_W ? J[e >> 5][e & 31] : 0.0;
+  __syncthreads();
+  for (int e = lane; e < 6 * TCOV_W; e += 64) {
+    const int r = e / TCOV_W, b = e % TCOV_W;
+    double s = 0.0;
+    for (int a = 0; a < TCOV_W; ++a) s += J[r][a] * W[a][b];
+    T[r][b] = s;
+  }
+  __syncthreads();
+  if (lane < 36) {
+    const int r = lane / 6, s2 = lane % 6;
+    if (r >= s2) {
+      double s = 0.0;
+      for (int b = 0; b < TCOV_W; ++b) s += T[r][b] * J[s2][b];
+      Cv[r][s2] = s; Cv[s2][r] = s;
+    }
+  }
+  __syncthreads();
+  if (lane < 36) h->C00[lane] = Cv[lane / 6][lane % 6];
+  if (lane == 0) h->status = 0;
+}
+
+// the 55 x 55 window and its indices of one point (tests and small n): k-window column a stands at a (a < 24) or 24 + a, 0-window column b at 24 + b
+__device__ __forceinline__ void pc_write_window(const PtCov& g, size_t i, const double (*Wkk)[33], const double (*Wk0)[32], const PtHub* h, const int* idxk, const int* idx0) {
+  if (g.widx) for (int c = 0; c < PCOV_W; ++c) g.widx[i * PCOV_W + c] = (c >= 24 && c < 48) ? idx0[c - 24] : idxk[c < 24 ? c : c - 24];
+  if (!g.wcov) return;
+  const size_t W2 = (size_t)PCOV_W * PCOV_W;
+  for (int e = 0; e < (int)W2; ++e) {
+    const int A = e / PCOV_W, B = e % PCOV_W;
+    const bool Ak = A < 24 || A >= 48, Bk = B < 24 || B >= 48;
+    double v;
+    if (Ak && Bk) v = Wkk[A < 24 ? A : A - 24][B < 24 ? B : B - 24];
+    else if (Ak) v = Wk0[A < 24 ? A : A - 24][B - 24];
+    else if (Bk) v = Wk0[B < 24 ? B : B - 24][A - 24];
+    else v = h->W00[A - 24][B - 24];
+    g.wcov[i * W2 + e] = v;
+  }
+}
+// MFMA = false (switch PTCOV_VALU): the plain formulation for comparison — every lane multiplies its own Gk against the staged window, read from LDS as a broadcast
+template <bool MFMA>
+__global__ __launch_bounds__(PC_NT) void k_point_cov(PtCov g) {
+  extern __shared__ double pc_tiles[];   // [PC_NT / 64][16][PC_TS]
+  __shared__ double Wkk[32][33], Bk[32][17], Wk0[TCOV_W][32], J0s[6][32], C00s[36], sck[32], sc0[32];
+  __shared__ int posk[32], idxk[32], pos0[32], idx0[32], s_key;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, fi = lane & 15, fk = lane >> 4;
+  const size_t i = (size_t)blockIdx.x * PC_NT + tid;
+  const PtHub* h = g.hub;
+  const int hs = h->status;
+  if (hs == 1 || hs == 2) return;   // the call fails as a whole: nothing is written
+  const bool in = i < (size_t)g.n;
+  for (int e = tid; e < 6 * 32; e += PC_NT) J0s[e >> 5][e & 31] = h->J0[e >> 5][e & 31];
+  if (tid < 36) C00s[tid] = h->C00[tid];
+  if (tid < 32) { const bool w = tid < TCOV_W; pos0[tid] = w ? h->pos[tid] : LVX_DEAD; idx0[tid] = w ? h->idx[tid] : -1; sc0[tid] = w ? h->sc[tid] : 0.0; }
+  // the lane's point: geometry and Gk = A_k Jk
+  v3 pL = mk(0, 0, 0), vv = mk(0, 0, 0), pm = mk(0, 0, 0);
+  double tk = 0.0;
+  if (in) {
+    if (g.xyzi) { const float4 f = ((const float4*)g.xyzi)[i]; pL = mk((double)f.x, (double)f.y, (double)f.z); }
+    else pL = load_v3(g.pt + 3 * i);
+    tk = g.t[i];
+  }
+  const quat q0 = mkq(h->q0[3], h->q0[0], h->q0[1], h->q0[2]);
+  const v3 p0 = mk(h->p0[0], h->p0[1], h->p0[2]);
+  int key = -1;
+  double Gk[3][TCOV_W];
+#pragma unroll
+  for (int r = 0; r < 3; ++r)
+#pragma unroll
+    for (int c = 0; c < TCOV_W; ++c) Gk[r][c] = 0.0;
+  if (in && hs == 0 && isfinite(pL.x) && isfinite(pL.y) && isfinite(pL.z)) {
+    const SplineRef sp{g.t0, g.dt, g.N, g.state, g.state + 3 * (size_t)g.N};
+    const SensorCal ext = pc_lidar(g);
+    KnotRef kr;
+    if (traj_knot(g.t0, g.dt, g.N, tk + ext.tau, &kr)) {
+      double Jk[6][TCOV_W]; int ik[TCOV_W];
+      int st = traj_pose_jacobian(sp, 1, ext, tk + ext.tau, Jk, ik);
+      quat qk; v3 pk;
+      if (st == RES_OK && pt_lidar_pose(sp, ext, tk + ext.tau, &qk, &pk) != RES_OK) st = RES_NONUNIT;
+      if (st == RES_OK) {
+        v3 r;
+        pt_chain(qk, pk, q0, p0, pL, &r, &vv, &pm);
+        pt_lever(Jk, r, Gk);
+        key = kr.i0;
+      } else if (st == RES_NONUNIT) *g.flag = RES_NONUNIT;
+    }
+  }
+  const bool valid = key >= 0;
+  double cov[9];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) cov[e] = 0.0;
+  double* tile = pc_tiles + (size_t)wave * 16 * PC_TS;
+  const size_t W2 = (size_t)PCOV_W * PCOV_W;
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) s_key = 0x7fffffff;
+    __syncthreads();
+    if (key >= 0) atomicMin(&s_key, key);
+    __syncthreads();
+    const int cur = s_key;
+    if (cur == 0x7fffffff) break;
+    // the interval's windows, once for the workgroup
+    if (tid < 32) {
+      int o = LVX_DEAD, id = -1;
+      if (tid < TCOV_W) { const int gi = tid < 24 ? 6 * cur + tid : 6 * g.N + 8 + (tid - 24); o = g.s.ord[gi]; if (o != LVX_DEAD) id = gi; }
+      posk[tid] = o; idxk[tid] = id; sck[tid] = pc_scale(g.s, o);
+    }
+    __syncthreads();
+    for (int e = tid; e < 32 * 32; e += PC_NT) {
+      const int a = e >> 5, b = e & 31;
+      const int pa = posk[a];
+      double vk = 0.0, v0 = 0.0;
+      if (pa != LVX_DEAD) {
+        const int pb = posk[b], qb = pos0[b];
+        if (pb != LVX_DEAD) { vk = pc_sigma(g.s, pa, pb); vk *= sck[a] * sck[b]; }
+        if (qb != LVX_DEAD) { v0 = pc_sigma(g.s, pa, qb); v0 *= sck[a] * sc0[b]; }
+      }
+      Wkk[a][b] = vk;
+      if (a < TCOV_W) Wk0[a][b] = v0;
+    }
+    __syncthreads();
+    for (int e = tid; e < 32 * 16; e += PC_NT) {
+      const int a = e >> 4, m = e & 15;
+      double s = 0.0;
+      if (a < TCOV_W && m < 6) for (int b = 0; b < TCOV_W; ++b) s += Wk0[a][b] * J0s[m][b];
+      Bk[a][m] = s;
+    }
+    __syncthreads();
+    const bool mine = key == cur;
+    const unsigned long long act = __ballot(mine);
+    if (!MFMA) {
+      if (mine) {
+        double Tl[3 * PCOV_TW];
+#pragma unroll
+        for (int b = 0; b < PCOV_TW; ++b) {
+          double t0 = 0.0, t1 = 0.0, t2 = 0.0;
+          if (b != 31) {
+#pragma unroll
+            for (int a = 0; a < TCOV_W; ++a) { const double w = b < 31 ? Wkk[a][b] : Bk[a][b - 32]; t0 += Gk[0][a] * w; t1 += Gk[1][a] * w; t2 += Gk[2][a] * w; }
+          }
+          Tl[b] = t0; Tl[PCOV_TW + b] = t1; Tl[2 * PCOV_TW + b] = t2;
+        }
+        pt_cov_assemble(Gk, Tl, PCOV_TW, C00s, vv, rotmat(q0), cov);
+        pc_write_window(g, i, Wkk, Wk0, h, idxk, idx0);
+      }
+    } else
+    for (int grp = 0; grp < 4; ++grp) {
+      const bool any = ((act >> (16 * grp)) & 0xffffull) != 0;   // uniform over the wavefront; the barriers below are reached by every wavefront all the same
+      if (any && fk == grp) {
+        double* Gp = tile + fi * PC_TS;
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+          for (int c = 0; c < TCOV_W; ++c) Gp[32 * r + c] = mine ? Gk[r][c] : 0.0;
+          Gp[32 * r + 31] = 0.0;
+        }
+      }
+      __syncthreads();
+      d4c acc[3][3];
+      if (any) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int nt = 0; nt < 3; ++nt) acc[r][nt] = d4c{0.0, 0.0, 0.0, 0.0};
+        // A[i = fi][k = fk] = Gk of point fi, B[k = fk][j = fi] = the window's row 4 s + fk
+        for (int s = 0; s < 8; ++s) {
+          const int k = 4 * s + fk;
+          const double b0 = Wkk[k][fi], b1 = Wkk[k][16 + fi], b2 = Bk[k][fi];
+#pragma unroll
+          for (int r = 0; r < 3; ++r) {
+            const double a = tile[fi * PC_TS + 32 * r + k];
+            acc[r][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b0, acc[r][0], 0, 0, 0);
+            acc[r][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b1, acc[r][1], 0, 0, 0);
+            acc[r][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b2, acc[r][2], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();   // every read of Gk is done: the tile now takes T (C/D: column = lane & 15, row = (lane >> 4) + 4 v)
+      if (any) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+          for (int nt = 0; nt < 3; ++nt) {
+            const int col = 16 * nt + fi;
+            if (col < PCOV_TW) {
+#pragma unroll
+              for (int v = 0; v < 4; ++v) tile[(fk + 4 * v) * PC_TS + PCOV_TW * r + col] = acc[r][nt][v];
+            }
+          }
+      }
+      __syncthreads();
+      if (mine && fk == grp) {
+        pt_cov_assemble(Gk, tile + fi * PC_TS, PCOV_TW, C00s, vv, rotmat(q0), cov);
+        pc_write_window(g, i, Wkk, Wk0, h, idxk, idx0);
+      }
+      __syncthreads();
+    }
+    if (mine) key = -1;
+  }
+  if (!in) return;
+  g.valid[i] = valid ? 1 : 0;
+  if (g.point) { g.point[3 * i] = pm.x; g.point[3 * i + 1] = pm.y; g.point[3 * i + 2] = pm.z; }
+  if (g.cov) for (int e = 0; e < 9; ++e) g.cov[9 * i + e] = cov[e];
+  // (a point measured at t_map itself does not move at all: the four terms cancel to rounding, a diagonal entry of -1e-21 counts as zero)
+  if (g.sigma) { g.sigma[3 * i] = sqrt(cov[0] < 0.0 ? 0.0 : cov[0]); g.sigma[3 * i + 1] = sqrt(cov[4] < 0.0 ? 0.0 : cov[4]); g.sigma[3 * i + 2] = sqrt(cov[8] < 0.0 ? 0.0 : cov[8]); }
+  if (g.sigma_max) g.sigma_max[i] = valid ? pt_sigma_max(cov) : 0.0;
+  if (g.var_dir && g.dir) g.var_dir[i] = valid ? pt_var_dir(cov, load_v3(g.dir + 3 * i)) : 0.0;
+  if (!valid) {
+    if (g.widx) for (int c = 0; c < PCOV_W; ++c) g.widx[i * PCOV_W + c] = -1;
+    if (g.wcov) for (int e = 0; e < (int)W2; ++e) g.wcov[i * W2 + e] = 0.0;
+  }
 }
 
 }  // namespace lvx

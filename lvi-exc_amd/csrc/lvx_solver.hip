@@ -1776,7 +1776,7 @@ static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int fra
         hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, head); }))) return rc;
   PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, (const double*)so.SigB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale,
             (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.cov, o.sigma, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
-  hipLaunchKernelGGL(k_pose_cov, dim3((unsigned)n), dim3(64), 0, st, p);
+  { ProfScope ps(c, LVX_KERNEL_POSE_COV); hipLaunchKernelGGL(k_pose_cov, dim3((unsigned)n), dim3(64), 0, st, p); }
   LVX_HIP(c, hipGetLastError());
   return LVX_OK;
 }
@@ -1917,6 +1917,111 @@ int lvx_landmark_covariance(lvx_ctx* c, const lvx_landmark_cov_options* opt, int
   }
   void* dst[8] = {nullptr, out->var_rho, out->sigma_rho, out->point, out->point_cov, out->window_cov, out->window_idx, out->valid};
   for (int k = 1; k < 8; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
+  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
+  return LVX_OK;
+}
+
+int lvx_point_cov_default_options(lvx_point_cov_options* o) {
+  if (!o) return LVX_E_ARG;
+  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
+  return LVX_OK;
+}
+// The selected inverse down to the lowest band position a point's window holds (k_tc_lowest in the LiDAR frame), k_pt_hub once, then k_point_cov with a lane per
+// point.  pt_d [n][3] or xyzi_d [n][4] float, t_d, dir_d (or null) and the arrays of o are device addresses; flags as traj_cov_enqueue's, flags[1] = 2 when the window of
+// t_map is off the border.
+static int pt_cov_enqueue(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt_d, const float* xyzi_d, const double* t_d, const double* dir_d, const lvx_point_cov& o,
+                          int* flags) {
+  int rc;
+  SolveWork w; SelInvOut so;
+  hipStream_t st = c->stream;
+  const double* state_d = c->last_state_d;
+  if ((rc = dev_alloc(c, c->d_ptcov, sizeof(PtHub)))) return rc;
+  if ((rc = selinv_enqueue(c, "lvx_map_point_covariance", opt->radius, opt->jacobi_scaling, false, w, &so, [&](int* head) {
+        hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, (int)LVX_FRAME_LIDAR, n, t_d, (const int*)c->d_ord.p, head); }))) return rc;
+  PtCov g{};
+  g.state = state_d; g.N = c->N; g.t0 = c->t0; g.dt = c->dt; g.t_map = c->t_map; g.n = n; g.pt = pt_d; g.xyzi = xyzi_d; g.t = t_d; g.dir = dir_d;
+  g.s = PtAccess{(const int*)c->d_ord.p, (const double*)so.SigB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale};
+  g.info = (const int*)w.info; g.force_bad = c->sw.test_bad_pivot ? 1 : 0; g.hub = (PtHub*)c->d_ptcov.p;
+  g.point = o.point; g.cov = o.cov; g.sigma = o.sigma; g.sigma_max = o.sigma_max; g.var_dir = o.var_dir; g.wcov = o.window_cov; g.widx = o.window_idx; g.valid = o.valid;
+  g.flag = flags; g.bad = flags + 1;
+  const size_t lds = (size_t)(PC_NT / 64) * 16 * PC_TS * 8;   // the wavefronts' tiles of the MFMA product
+  const dim3 grid((unsigned)(((size_t)n + PC_NT - 1) / PC_NT));
+  LVX_HIP(c, hipFuncSetAttribute((const void*)k_point_cov<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  {
+    ProfScope ps(c, LVX_KERNEL_POINT_COV);
+    hipLaunchKernelGGL(k_pt_hub, dim3(1), dim3(64), 0, st, g);
+    if (c->sw.ptcov_valu) hipLaunchKernelGGL(k_point_cov<false>, grid, dim3(PC_NT), 0, st, g);
+    else hipLaunchKernelGGL(k_point_cov<true>, grid, dim3(PC_NT), lds, st, g);
+  }
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+static int pt_cov_args(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const void* pt, const double* t, const lvx_point_cov* out) {
+  if (!c) return LVX_E_ARG;
+  if (!opt || !pt || !t || !out || !out->valid || n <= 0 || !(opt->radius > 0) || opt->reserved != 0)
+    return fail(c, LVX_E_ARG, "lvx_map_point_covariance: n <= 0, radius <= 0, reserved != 0 or a required pointer is NULL");
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_map_point_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: the context takes part in a joint solve");
+  if ((c->surf.n <= 0 && c->cs.n <= 0) || c->n_hub <= 0) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: no surfel / camera-surfel family has set t_map");
+  LVX_HIP(c, hipSetDevice(c->device));
+  return check_last_eval(c);
+}
+static int pt_cov_d(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt_d, const float* xyzi_d, const double* t_d, const double* dir_d, const lvx_point_cov* out_d) {
+  int rc = pt_cov_args(c, opt, n, pt_d ? (const void*)pt_d : (const void*)xyzi_d, t_d, out_d);
+  if (rc) return rc;
+  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
+    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
+    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
+  }
+  c->tcov_d_unchecked = true;
+  return pt_cov_enqueue(c, opt, n, pt_d, xyzi_d, t_d, dir_d, *out_d, (int*)c->d_tj[3].p + 1);
+}
+int lvx_map_point_covariance_d(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt3_d, const double* t_d, const double* dir3_d, const lvx_point_cov* out_d) {
+  return pt_cov_d(c, opt, n, pt3_d, nullptr, t_d, dir3_d, out_d);
+}
+int lvx_map_point_covariance_xyzi_d(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const float* xyzi4_d, const double* t_d, const lvx_point_cov* out_d) {
+  return pt_cov_d(c, opt, n, nullptr, xyzi4_d, t_d, nullptr, out_d);
+}
+int lvx_map_point_covariance(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt_lidar3, const double* t, const double* dir3, lvx_point_cov* out) {
+  int rc = pt_cov_args(c, opt, n, pt_lidar3, t, out);
+  if (rc) return rc;
+  hipStream_t st = c->stream;
+  // device and pinned images (lvx_trajectory_covariance's): [points | t | dir | point | cov | sigma | sigma_max | var_dir | window_cov | window_idx | valid | flags (2 ints)]
+  const size_t nn = (size_t)n, W2 = (size_t)LVX_PT_COV_W * LVX_PT_COV_W;
+  const bool vd = dir3 && out->var_dir;
+  enum { NIN = 3, NARR = 11 };
+  size_t off[NARR + 1]; size_t cur = 0;
+  const size_t bytes[NARR] = {nn * 24, nn * 8, vd ? nn * 24 : 0, out->point ? nn * 24 : 0, out->cov ? nn * 72 : 0, out->sigma ? nn * 24 : 0, out->sigma_max ? nn * 8 : 0, vd ? nn * 8 : 0,
+                              out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_PT_COV_W * 4 : 0, nn};
+  for (int k = 0; k < NARR; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
+  off[NARR] = cur; cur += 16;
+  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
+  if (c->h_tcov_cap < cur) {
+    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
+    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
+    c->h_tcov_cap = cur;
+  }
+  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
+  std::memcpy(h + off[0], pt_lidar3, bytes[0]); std::memcpy(h + off[1], t, bytes[1]);
+  if (vd) std::memcpy(h + off[2], dir3, bytes[2]);
+  LVX_HIP(c, hipMemcpyAsync(d, h, off[NIN], hipMemcpyHostToDevice, st));
+  LVX_HIP(c, hipMemsetAsync(d + off[NARR], 0, 16, st));
+  auto at = [&](int k) { return bytes[k] ? (void*)(d + off[k]) : nullptr; };
+  lvx_point_cov od;
+  od.point = (double*)at(3); od.cov = (double*)at(4); od.sigma = (double*)at(5); od.sigma_max = (double*)at(6); od.var_dir = (double*)at(7); od.window_cov = (double*)at(8);
+  od.window_idx = (int32_t*)at(9); od.valid = (uint8_t*)at(10);
+  if ((rc = pt_cov_enqueue(c, opt, n, (const double*)(d + off[0]), nullptr, (const double*)(d + off[1]), vd ? (const double*)(d + off[2]) : nullptr, od, (int*)(d + off[NARR])))) return rc;
+  LVX_HIP(c, hipMemcpyAsync(h + off[NIN], d + off[NIN], cur - off[NIN], hipMemcpyDeviceToHost, st));
+  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
+  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
+  int fl[2]; std::memcpy(fl, h + off[NARR], 8);
+  if (fl[1] == 2) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: a free scalar of the pose at t_map is a band position of the factor (its cross terms are off the pattern)");
+  if (fl[1]) {
+    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
+    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
+  }
+  void* dst[NARR] = {nullptr, nullptr, nullptr, out->point, out->cov, out->sigma, out->sigma_max, out->var_dir, out->window_cov, out->window_idx, out->valid};
+  for (int k = NIN; k < NARR; ++k) if (dst[k] && bytes[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
   if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
   return LVX_OK;
 }

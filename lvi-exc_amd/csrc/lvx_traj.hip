@@ -167,11 +167,12 @@ void traj_destroy(lvx_ctx* c) {
 int traj_check_d(lvx_ctx* c) {
   if ((!c->tj_d_unchecked && !c->tcov_d_unchecked) || !c->d_tj[3].p) return LVX_OK;
   c->tj_d_unchecked = false; c->tcov_d_unchecked = false;
-  int w[2] = {0, 0};   // [1] a non-unit control quaternion in a _d query, [2] a lost pivot in lvx_trajectory_covariance_d / lvx_landmark_covariance_d
+  int w[2] = {0, 0};   // [1] a non-unit control quaternion in a _d query, [2] a lost pivot in lvx_trajectory_covariance_d / lvx_landmark_covariance_d / lvx_map_point_covariance_d (2: the latter's t_map window off the border)
   int* flag = (int*)c->d_tj[3].p + 1;
   LVX_HIP(c, hipMemcpy(w, flag, 8, hipMemcpyDeviceToHost));
   if (!w[0] && !w[1]) return LVX_OK;
   LVX_HIP(c, hipMemset(flag, 0, 8));
+  if (w[1] == 2) return fail(c, LVX_E_STATE, "lvx_map_point_covariance_d: a free scalar of the pose at t_map is a band position (nothing was written)");
   if (w[1]) return fail(c, LVX_E_NOTPD, "lvx_trajectory_covariance_d / lvx_landmark_covariance_d: damped normal equations not positive definite (nothing was written)");
   return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
 }

@@ -270,6 +270,38 @@ inline LandmarkUncertainty LandmarkCovariance(lvx_ctx* ctx, const std::vector<in
   if (state) { r.rho.resize(n); for (size_t i = 0; i < n; ++i) r.rho[i] = state->at(7 * (size_t)lo.n_knots + 32 + (size_t)r.ids[i]); }
   return r;
 }
+// lvx_map_point_covariance over LiDAR points [n][3] measured at `times`: the point in the map frame [n][3], cov [n][9], sigma [n][3] (metres), sigma_max [n], valid [n];
+// dirs [n][3] (optional, e.g. unit plane normals in the map frame): var_dir [n] = dir^T cov dir, the predicted variance of a surfel row
+struct MapPointUncertainty { double radius = 0; std::vector<double> point, cov, sigma, sigma_max, var_dir; std::vector<uint8_t> valid; };
+inline MapPointUncertainty MapPointCovariance(lvx_ctx* ctx, const std::vector<double>& points, const std::vector<double>& times, const std::vector<double>& dirs = {},
+                                              const lvx_point_cov_options* opts = nullptr) {
+  const size_t n = times.size();
+  if (points.size() != 3 * n || (!dirs.empty() && dirs.size() != 3 * n)) throw std::invalid_argument("MapPointCovariance: three coordinates (and direction components) per time");
+  MapPointUncertainty r;
+  lvx_point_cov_options o; lvx_point_cov_default_options(&o);
+  if (opts) o = *opts;
+  r.radius = o.radius;
+  if (n == 0) return r;
+  r.point.assign(3 * n, 0.0); r.cov.assign(9 * n, 0.0); r.sigma.assign(3 * n, 0.0); r.sigma_max.assign(n, 0.0); r.valid.assign(n, 0);
+  if (!dirs.empty()) r.var_dir.assign(n, 0.0);
+  lvx_point_cov out{r.point.data(), r.cov.data(), r.sigma.data(), r.sigma_max.data(), dirs.empty() ? nullptr : r.var_dir.data(), nullptr, nullptr, r.valid.data()};
+  ThrowOnError(ctx, lvx_map_point_covariance(ctx, &o, (int)n, points.data(), times.data(), dirs.empty() ? nullptr : dirs.data(), &out));
+  return r;
+}
+// What a user reads off it, one line: the median and the largest sigma_max over the valid points, in millimetres
+//   [Map] point std (mm): median a, worst b at point i (n valid of m, radius r)
+inline std::string FormatMapPointUncertainty(const MapPointUncertainty& r) {
+  std::vector<double> s; std::vector<size_t> at;
+  for (size_t i = 0; i < r.valid.size(); ++i) if (r.valid[i]) { s.push_back(r.sigma_max[i]); at.push_back(i); }
+  if (s.empty()) return "[Map] no valid point\n";
+  const size_t w = (size_t)(std::max_element(s.begin(), s.end()) - s.begin());
+  const double worst = s[w];
+  std::nth_element(s.begin(), s.begin() + s.size() / 2, s.end());
+  char buf[200];
+  std::snprintf(buf, sizeof buf, "[Map] point std (mm): median %.4g, worst %.4g at point %zu (%zu valid of %zu, radius %g)\n", 1e3 * s[s.size() / 2], 1e3 * worst, at[w], at.size(),
+                r.valid.size(), r.radius);
+  return buf;
+}
 // What a user reads off it, one line: the median and the largest relative depth sigma, sigma_rho / |rho| (to first order the relative sigma of the depth 1 / rho), over
 // the valid landmarks, and which landmark is the worst.  Without LandmarkUncertainty::rho the sigmas of the inverse depth themselves.
 //   [Landmarks] relative depth std: median a, max b at landmark l (n valid of m, radius r)
@@ -552,6 +584,24 @@ class Calibrator {
   // first valid pose with LVX_ALIGN_FIRST
   PoseComparison CompareWithLoam(const std::vector<double>& state, int align = LVX_ALIGN_FIRST, bool key_only = false) {
     return ComparePoses(ctx_, state, LVX_FRAME_LIDAR, key_only ? in_.loam.key : in_.loam.all, align);
+  }
+  // lvx_map_point_covariance over the points of raw scan `scan_index` (lvx_get_scans_raw: whichever way the scans came in), at the normal equations and the state of the
+  // context's last LVX_EVAL_NORMAL_EQ evaluation; index_in_scan[i] = h * W + w of entry i.  Empty cells (NaN coordinates) are left out; every `step`-th point is taken.
+  // The host route: not the hot path (lvx_map_point_covariance_xyzi_d reads device buffers).
+  MapPointUncertainty MapPointCovariance(int scan_index, std::vector<int32_t>* index_in_scan = nullptr, int step = 1, const lvx_point_cov_options* opts = nullptr) {
+    if (scan_index < 0 || (size_t)scan_index >= n_scans_ || step < 1) throw std::invalid_argument("MapPointCovariance: scan index outside the scans, or step < 1");
+    const size_t HW = (size_t)in_.H * in_.W;
+    std::vector<lvx_point_xyzit> raw(HW);
+    check(lvx_get_scans_raw(ctx_, scan_index, 1, raw.data()));
+    std::vector<double> pts, t;
+    if (index_in_scan) index_in_scan->clear();
+    for (size_t k = 0; k < HW; k += (size_t)step) {
+      const lvx_point_xyzit& p = raw[k];
+      if (!std::isfinite(p.x) || !std::isfinite(p.y) || !std::isfinite(p.z)) continue;
+      pts.push_back(p.x); pts.push_back(p.y); pts.push_back(p.z); t.push_back(p.timestamp);
+      if (index_in_scan) index_in_scan->push_back((int32_t)k);
+    }
+    return lvx_host::MapPointCovariance(ctx_, pts, t, {}, opts);
   }
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }

@@ -31,7 +31,8 @@ EVAL_COST, EVAL_RESIDUALS, EVAL_NORMAL_EQ, EVAL_JACOBIAN, EVAL_JACOBIAN_BLOCKS =
 KERNEL_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf", "fold", "solve", "upstream", "clear", "reproj_jac", "reproj_obs", "reproj_ref", "reproj_cross", "reproj_lmrows", "reproj_fused", "fixup"]
 FAM_LIDAR_POS = 6       # LiDAR odometry position blocks (set_lidar_poses): not one of the six families of FAMILY_NAMES / family_rows()
 KERNEL_LIDAR_POS = 17   # beyond KERNEL_NAMES: kernel_ms_ext() returns it
-KERNEL_NAMES_EXT = KERNEL_NAMES + ["lidar_pos"]
+KERNEL_POSE_COV, KERNEL_POINT_COV = 18, 19   # k_pose_cov of trajectory_covariance; k_pt_hub + k_point_cov of map_point_covariance
+KERNEL_NAMES_EXT = KERNEL_NAMES + ["lidar_pos", "pose_cov", "point_cov"]
 JAC_WIDTH = 64
 
 
@@ -123,6 +124,19 @@ class LandmarkCov(C.Structure):
     """lvx_landmark_cov: host or device addresses; a NULL member (but valid) is not computed."""
     _fields_ = [("var_rho", C.c_void_p), ("sigma_rho", C.c_void_p), ("point", C.c_void_p), ("point_cov", C.c_void_p), ("window_cov", C.c_void_p), ("window_idx", C.c_void_p),
                 ("valid", C.c_void_p)]
+
+
+PT_COV_W = 55   # window of lvx_map_point_covariance: the four knots at t + tau_L, the four at t_map + tau_L, the LiDAR's theta (3), p (3), tau (1)
+
+
+class PointCovOptions(C.Structure):
+    _fields_ = [("radius", C.c_double), ("jacobi_scaling", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PointCov(C.Structure):
+    """lvx_point_cov: host or device addresses; a NULL member (but valid) is not computed."""
+    _fields_ = [("point", C.c_void_p), ("cov", C.c_void_p), ("sigma", C.c_void_p), ("sigma_max", C.c_void_p), ("var_dir", C.c_void_p), ("window_cov", C.c_void_p),
+                ("window_idx", C.c_void_p), ("valid", C.c_void_p)]
 
 
 N_SHARED = 14   # the shared extrinsic scalars of a joint solve: canonical slot k = c - 8
@@ -545,6 +559,56 @@ class Context:
         r = LandmarkCov(*[out_d_ptrs.get(f) for f in ("var_rho", "sigma_rho", "point", "point_cov", "window_cov", "window_idx")], valid_d_ptr)
         opt = self._landmark_cov_options(radius, jacobi_scaling)
         self._ck(self._l.lvx_landmark_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(ids_d_ptr) if ids_d_ptr else None, C.byref(r)))
+
+    def _point_cov_options(self, radius, jacobi_scaling):
+        opt = PointCovOptions()
+        self._l.lvx_point_cov_default_options(C.byref(opt))
+        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
+        return opt
+
+    def map_point_covariance(self, points, t, dirs=None, radius=1e8, jacobi_scaling=True, window=False):
+        """Uncertainty of LiDAR points [n, 3] measured at times t [n] once carried into the map frame (the LiDAR frame at t_map), in the DAMPED system of the last
+        evaluate(normal_eq=True) at the state of that evaluation (lvx_map_point_covariance).  Returns a dict: point [n, 3], cov [n, 3, 3], sigma [n, 3] (metres),
+        sigma_max [n], valid [n] bool; with dirs [n, 3] also var_dir [n] = dir^T cov dir; with window=True also window_cov [n, 55, 55] and window_idx [n, 55] (tangent
+        index, -1 constant).  An invalid point (time outside the trajectory, a coordinate that is not finite) holds zeros.  A non-unit control quaternion raises
+        LvxError(E_NONUNIT_QUAT) whose `partial` attribute is that dict."""
+        points = _d(np.atleast_2d(points))
+        t = _d(np.atleast_1d(t))
+        n = len(t)
+        if points.shape != (n, 3):
+            raise ValueError("points must be [n, 3] with one time each")
+        out = dict(point=np.zeros((n, 3)), cov=np.zeros((n, 3, 3)), sigma=np.zeros((n, 3)), sigma_max=np.zeros(n))
+        if dirs is not None:
+            dirs = _d(np.atleast_2d(dirs))
+            if dirs.shape != (n, 3):
+                raise ValueError("dirs must be [n, 3]")
+            out["var_dir"] = np.zeros(n)
+        if window:
+            out["window_cov"] = np.zeros((n, PT_COV_W, PT_COV_W))
+            out["window_idx"] = np.full((n, PT_COV_W), -1, np.int32)
+        valid = np.zeros(n, np.uint8)
+        r = PointCov(*[out[k].ctypes.data if k in out else None for k in ("point", "cov", "sigma", "sigma_max", "var_dir", "window_cov", "window_idx")], valid.ctypes.data)
+        opt = self._point_cov_options(radius, jacobi_scaling)
+        rc = self._l.lvx_map_point_covariance(self._h, C.byref(opt), C.c_int(n), _p(points), _p(t), _p(dirs), C.byref(r))
+        out["valid"] = valid.astype(bool)
+        if rc == E_NONUNIT_QUAT:
+            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
+            e.partial = out
+            raise e
+        self._ck(rc)
+        return out
+
+    def map_point_covariance_d(self, points_d_ptr, t_d_ptr, n, out_d_ptrs, valid_d_ptr, dirs_d_ptr=None, xyzi=False, radius=1e8, jacobi_scaling=True):
+        """lvx_map_point_covariance_d (xyzi=True: lvx_map_point_covariance_xyzi_d, points as [n, 4] float32 in the scan buffers' layout, no directions): device
+        addresses; out_d_ptrs maps "point" / "cov" / "sigma" / "sigma_max" / "var_dir" / "window_cov" / "window_idx" to addresses (absent: not computed).  Only
+        enqueues; synchronize() reports a lost pivot, a t_map window off the border or a non-unit quaternion."""
+        r = PointCov(*[out_d_ptrs.get(f) for f in ("point", "cov", "sigma", "sigma_max", "var_dir", "window_cov", "window_idx")], valid_d_ptr)
+        opt = self._point_cov_options(radius, jacobi_scaling)
+        if xyzi:
+            self._ck(self._l.lvx_map_point_covariance_xyzi_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(points_d_ptr), C.c_void_p(t_d_ptr), C.byref(r)))
+        else:
+            self._ck(self._l.lvx_map_point_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(points_d_ptr), C.c_void_p(t_d_ptr),
+                                                       C.c_void_p(dirs_d_ptr) if dirs_d_ptr else None, C.byref(r)))
 
     def lm_solve(self, state, max_iterations=50, **kw):
         """TrajectoryEstimator::Solve(max_iterations) equivalent.  Returns (state, summary dict with per-iteration history)."""
