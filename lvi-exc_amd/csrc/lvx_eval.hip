@@ -1097,6 +1097,14 @@ struct NoRow {};
 template <class F, class = void> struct RowOf { using type = NoRow; static constexpr bool prefetch = false; };
 template <class F> struct RowOf<F, std::void_t<typename F::Row>> { using type = typename F::Row; static constexpr bool prefetch = true; };
 
+// Scatter table entry of one lane and tile slot of the panel-major assemblies (k_family_mfma, imu_assemble), in BYTES so that a window costs one multiply-add and the
+// LDS add per slot: bits 0 .. 23 the accumulator entry of a window at the base of the chunk's knot range, bits 24 .. 31 what it moves by per tangent scalar of the
+// window's offset (8 ACC_BW: band, 8: bd / gk, 0: gg / gG and the dummies).  A slot without a target (lower triangle, padding) carries the lane's DUMMY slot behind
+// the accumulators: the window adds its tile value there as it stands (the dummy slots are never read).  No entry is tested against the top of the accumulator
+// range: a row is valid only if its interval lies at most CR + 1 above the window base, so the 24 rows of its window end inside the (CR + 5) * 6 accumulator rows.
+#define IMU_RT_ROWS 24                   // rows of a window: 4 knots x 6 tangent scalars
+__device__ __forceinline__ unsigned imu_rt_entry(int idx, int step) { return (unsigned)(idx * 8) | ((unsigned)(step * 8) << 24); }
+static_assert(ACC_BW * 8 < 256, "the band step of a scatter table entry is 8 bits");
 // F::PMAJ (families with WS == 1: every row of a window has the same local columns, no shift): the wavefront writes the rows of GL lanes into its
 // panel ONCE and then walks the windows inside the panel — a window is the set of panel rows whose lanes share a knot interval; its k-steps
 // run over that row span and mask the rows of other windows.  With the window-major loop a panel held one window (8 IMU samples: 8 of 64
@@ -1140,7 +1148,7 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
   double* acc_gg = acc_bd + NG * ACC_LV;              // [NG][NG]
   double* acc_gk = acc_gg + NG * NG;                  // [ACC_LV]
   double* acc_gG = acc_gk + ACC_LV;                   // [NG]
-  const int dummy = (int)(acc_gG + NG - sm);          // 64 doubles: where a lane adds +0.0 when its tile position has no accumulator entry (branch-free scatter)
+  const int dummy = (int)(acc_gG + NG - sm);          // 64 doubles: where a lane adds its tile value when the tile position has no accumulator entry (branch-free scatter)
   double* panels = acc_gG + NG + 64;                  // 4 x [PR][LDP]
   So3Pre* pre_tab = (So3Pre*)(panels + 4 * PR * LDP); // [CR + 4] control-point pairs (k_lo + e, k_lo + e + 1), families with USE_PRE
   int* kpos = (int*)(pre_tab + (F::USE_PRE ? CR + 4 : 0));   // [ACC_LV]
@@ -1189,8 +1197,8 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
   auto cls = [](int lc) { return lc < NKL ? 6 * (lc / KPK) + F::LVO + lc % KPK : (lc < NKL + NGP ? -1 - (DEPG + lc - NKL) : (lc == NKL + NGP ? -100 : -200)); };
   const int frag_off = (lane >> 4) * LDP + (lane & 15);
   double mycost = 0.0;
-  // panel-major families: where accumulator register (tile pair t, v) of THIS lane goes at the end of a window — LDS index (doubles, relative
-  // to sm) | multiplier of the window base (0: none, 1: wb, 2: wb * ACC_BW) << 16 | largest accumulator row touched (relative to wb) << 18, or -1
+  // panel-major families: where accumulator register (tile pair t, v) of THIS lane goes at the end of a window — a scatter table entry (imu_rt_entry above: byte
+  // offset | bytes per tangent scalar of the window's offset), the lane's dummy slot where the tile position has no accumulator entry
   int rtab[PanelMajor<F>::on ? G::NTP * 4 : 1];
   if constexpr (PanelMajor<F>::on) {
     int t = 0;
@@ -1205,15 +1213,15 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
           if (!(ci == cj && col < row)) {
             const int ra = cls(row), cb = cls(col);
             if (ra >= 0) {
-              if (cb >= 0) { const int d = cb - ra; if (d >= 0 && d < ACC_BW) ent = ((int)(acc_band - sm) + ra * ACC_BW + d) | (2 << 16) | (cb << 18); }
-              else if (cb > -100) ent = ((int)(acc_bd - sm) + (-1 - cb) * ACC_LV + ra) | (1 << 16) | (ra << 18);
-              else if (cb == -100) ent = ((int)(acc_gk - sm) + ra) | (1 << 16) | (ra << 18);
+              if (cb >= 0) { const int d = cb - ra; if (d >= 0 && d < ACC_BW) ent = (int)imu_rt_entry((int)(acc_band - sm) + ra * ACC_BW + d, ACC_BW); }
+              else if (cb > -100) ent = (int)imu_rt_entry((int)(acc_bd - sm) + (-1 - cb) * ACC_LV + ra, 1);
+              else if (cb == -100) ent = (int)imu_rt_entry((int)(acc_gk - sm) + ra, 1);
             } else if (ra > -100 && !F::SKIP_GG) {
-              if (cb > -100 && cb < 0) ent = (int)(acc_gg - sm) + (-1 - ra) * NG + (-1 - cb);
-              else if (cb == -100) ent = (int)(acc_gG - sm) + (-1 - ra);
+              if (cb > -100 && cb < 0) ent = (int)imu_rt_entry((int)(acc_gg - sm) + (-1 - ra) * NG + (-1 - cb), 0);
+              else if (cb == -100) ent = (int)imu_rt_entry((int)(acc_gG - sm) + (-1 - ra), 0);
             }
           }
-          rtab[t * 4 + v] = ent;
+          rtab[t * 4 + v] = ent != -1 ? ent : (int)imu_rt_entry(dummy + lane, 0);
         }
   }
   typename RowOf<F>::type nxt{};
@@ -1293,18 +1301,17 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
         KT(2)
         while (rem) {                                         // windows inside the panel (wave-uniform control flow)
           const int l0 = __ffsll((long long)rem) - 1;
-          const int kw = __builtin_amdgcn_readfirstlane(__shfl(key, l0));
-          const unsigned long long wm = __ballot(valid && key == kw) & pmask;
+          const int kw = __builtin_amdgcn_readlane(key, l0);   // (l0 is wave-uniform: a v_readlane; __shfl went through the LDS crossbar and waited for it)
+          const unsigned long long km = __ballot(valid && key == kw) & rem;
+          const unsigned long long wm = km & ~(km + (1ull << l0));   // the RUN of lanes with this key from l0 on (imu_assemble)
           rem &= ~wm;
           const int lhi = 63 - __clzll((long long)wm);
           const int wb = (kw - k_lo) * 6;
           const int r_lo = (l0 - g0) * NR, r_hi = (lhi - g0 + 1) * NR;   // the window's row span in the panel
-          const unsigned long long wsh = wm >> g0;
           d4 D[G::NTP];
 #pragma unroll
           for (int t = 0; t < G::NTP; ++t) D[t] = d4{0.0, 0.0, 0.0, 0.0};
           const int nks = (r_hi - r_lo + 3) >> 2;
-          const bool contig = __popcll(wm) == lhi - l0 + 1;   // sorted families: always (wave-uniform)
           // U k-steps per trip, their LDS reads issued before the first product: one read -> select -> MFMA chain per k-step leaves the LDS
           // latency exposed (measured: 480 cycles per k-step).  A full interval of 8 IMU samples is 6 k-steps = one trip; a padded k-step
           // multiplies zeros.
@@ -1314,8 +1321,7 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
 #pragma unroll
             for (int q = 0; q < U; ++q) {
               const int rr = r_lo + 4 * (ks + q) + (lane >> 4);
-              bool mine = rr < r_hi;
-              if (!contig) mine = mine && ((wsh >> (rr / NR)) & 1ull);   // rows of other windows inside the span contribute zeros
+              const bool mine = rr < r_hi;
               const double* src = P + min(rr, PR - 1) * LDP + (lane & 15);
 #pragma unroll
               for (int c = 0; c < NT; ++c) { const double x = src[c * 16]; f[q][c] = mine ? x : 0.0; }
@@ -1333,17 +1339,14 @@ __global__ __launch_bounds__(256, OCC) void k_family_mfma(F fam, DevCommon cm, c
           for (; ks + 6 <= nks; ks += 6) trip(ks, std::integral_constant<int, 6>{});
           for (; ks < nks; ks += 2) trip(ks, std::integral_constant<int, 2>{});
           KT(3)
-          const int wbB = wb * ACC_BW;
-          // branch-free: every lane issues every LDS add — to its accumulator entry, or +0.0 to a dummy slot of its own (no entry at this tile position, or beyond the
-          // accumulator window).  A `continue` per slot made every slot a basic block: branch + exec-mask juggling + the wait for the MFMA result, slot after slot
+          // every lane issues every LDS add at the address its table entry gives for this window's offset; a slot without a target adds to the lane's dummy slot.
+          // (No test against the top of the accumulators: a valid row has 6 (key - k_lo + 4) <= LVU <= ACC_LV.)
 #pragma unroll
           for (int t = 0; t < G::NTP; ++t)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
-              const int te = rtab[t * 4 + v];
-              const bool ok = te >= 0 && wb + (te >> 18) < ACC_LV;
-              const int m = (te >> 16) & 3;
-              atomicAdd(&sm[ok ? (te & 0xffff) + (m == 2 ? wbB : (m == 1 ? wb : 0)) : dummy + lane], ok ? D[t][v] : 0.0);
+              const unsigned te = (unsigned)rtab[t * 4 + v];
+              atomicAdd((double*)((char*)sm + ((te & 0xffffffu) + (te >> 24) * (unsigned)wb)), D[t][v]);
             }
           KT(4)
         }
@@ -1565,21 +1568,22 @@ template <class PG> __device__ __forceinline__ void imu_build_rtab(int* rtab, in
         if (!(ci == cj && col < row)) {
           const int ra = imu_cls<PG>(row), cb = imu_cls<PG>(col);
           if (ra >= 0) {
-            if (cb >= 0) { const int d = cb - ra; if (d >= 0 && d < ACC_BW) ent = ((int)(A.band - sm) + ra * ACC_BW + d) | (2 << 16) | (cb << 18); }
-            else if (cb > -100) ent = ((int)(A.bd - sm) + (-1 - cb) * A.lv + ra) | (1 << 16) | (ra << 18);
-            else if (cb == -100) ent = ((int)(A.gk - sm) + ra) | (1 << 16) | (ra << 18);
+            if (cb >= 0) { const int d = cb - ra; if (d >= 0 && d < ACC_BW) ent = (int)imu_rt_entry((int)(A.band - sm) + ra * ACC_BW + d, ACC_BW); }
+            else if (cb > -100) ent = (int)imu_rt_entry((int)(A.bd - sm) + (-1 - cb) * A.lv + ra, 1);
+            else if (cb == -100) ent = (int)imu_rt_entry((int)(A.gk - sm) + ra, 1);
           } else if (ra > -100) {
-            if (cb > -100 && cb < 0) ent = (int)(A.gg - sm) + (-1 - ra) * IMU_NGA + (-1 - cb);
-            else if (cb == -100) ent = (int)(A.gG - sm) + (-1 - ra);
+            if (cb > -100 && cb < 0) ent = (int)imu_rt_entry((int)(A.gg - sm) + (-1 - ra) * IMU_NGA + (-1 - cb), 0);
+            else if (cb == -100) ent = (int)imu_rt_entry((int)(A.gG - sm) + (-1 - ra), 0);
           }
         }
-        rtab[t * 4 + v] = ent;
+        rtab[t * 4 + v] = ent != -1 ? ent : (int)imu_rt_entry((int)(A.gG - sm) + IMU_NGA + lane, 0);
       }
 }
 // rows of this wavefront's 64 lanes -> panel by panel -> windows (runs of equal knot interval) -> MFMA -> LDS accumulators
 // nhalo: lanes below it hold HALO samples (of the three intervals in front of the workgroup's primary range, see the schedule below); windows never mix the two kinds.
 // HALO = false: a trip without halo lanes (all but the first one or two of a workgroup) — the scatter without the halo predicate
-template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(double* sm, double* P, const int* rtab, bool valid, int key, int k_lo, int acc_lv, const double* r, const double (*J)[PG::NCJ], int lane, int dummy, int nhalo) {
+// A window's key is read from its first lane with v_readlane (l0 is wave-uniform; __shfl went through the LDS crossbar and waited for it in front of every window).
+template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(double* sm, double* P, const int* rtab, bool valid, int key, int k_lo, const double* r, const double (*J)[PG::NCJ], int lane, int dummy, int nhalo) {
   constexpr int NR = PG::NR, NT = PG::NT, LDP = PG::LDP, PR = PG::PR, GL = PG::GL;
   const unsigned long long vm = __ballot(valid);
   for (int g0 = 0; g0 < 64; g0 += GL) {
@@ -1601,14 +1605,15 @@ template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(doub
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     while (rem) {
       const int l0 = __ffsll((long long)rem) - 1;
-      const int kw = __builtin_amdgcn_readfirstlane(__shfl(key, l0));
-      const unsigned long long wm = __ballot(valid && key == kw) & pmask;
+      const int kw = __builtin_amdgcn_readlane(key, l0);
+      // a window is the RUN of valid lanes with this key that starts at l0 (lanes of the same key behind an invalid one make a window of their own: same sums), so
+      // every row of its span is the window's and the fragment reads mask by the span alone (a bit mask over the span cost every k-step an exec-masked block of 10 instructions)
+      const unsigned long long km = __ballot(valid && key == kw) & rem;
+      const unsigned long long wm = km & ~(km + (1ull << l0));
       rem &= ~wm;
       const int lhi = 63 - __clzll((long long)wm);
       const int wb = (kw - k_lo) * 6;
       const int r_lo = (l0 - g0) * NR, r_hi = (lhi - g0 + 1) * NR;
-      const unsigned long long wsh = wm >> g0;
-      const bool contig = __popcll(wm) == lhi - l0 + 1;
       d4 D[PG::NTP];
 #pragma unroll
       for (int t = 0; t < PG::NTP; ++t) D[t] = d4{0.0, 0.0, 0.0, 0.0};
@@ -1619,8 +1624,7 @@ template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(doub
 #pragma unroll
         for (int q = 0; q < U; ++q) {
           const int rr = r_lo + 4 * (ks + q) + (lane >> 4);
-          bool mine = rr < r_hi;
-          if (!contig) mine = mine && ((wsh >> (rr / NR)) & 1ull);
+          const bool mine = rr < r_hi;
           const double* src = P + min(rr, PR - 1) * LDP + (lane & 15);
 #pragma unroll
           for (int c = 0; c < NT; ++c) { const double x = src[c * 16]; f[q][c] = mine ? x : 0.0; }
@@ -1637,20 +1641,21 @@ template <class PG, bool HALO> __device__ __forceinline__ void imu_assemble(doub
       int ks = 0;
       for (; ks + 6 <= nks; ks += 6) trip(ks, std::integral_constant<int, 6>{});
       for (; ks < nks; ks += 2) trip(ks, std::integral_constant<int, 2>{});
-      const int wbB = wb * ACC_BW;
-      const int mlo = l0 < nhalo ? 1 : 0;   // a halo window adds to the knot-indexed accumulators (band, bd, gk: modes 2 and 1) only; gg / gG (mode 0) belong to the sample's primary workgroup
-      // BRANCH-FREE scatter: every lane issues every LDS add — to its accumulator entry, or +0.0 to a dummy slot of its own when the tile position has no entry (lower
-      // triangle, padding), lies beyond the window or is not a halo window's to add.  With a `continue` per slot every slot was a basic block of its own: exec-mask juggling, a branch and the 76-cycle
-      // wait for the MFMA result, one slot after the other (180 cycles per slot on the one wavefront per SIMD this kernel runs at).
+      const bool halo_w = l0 < nhalo;   // a halo window adds to the knot-indexed accumulators (band, bd, gk) only; gg / gG (step 0) belong to the sample's primary workgroup
+      // BRANCH-FREE scatter: every lane issues every LDS add (with a `continue` per slot every slot was a basic block of its own: exec-mask juggling, a branch and the
+      // 76-cycle wait for the MFMA result, 180 cycles per slot on the one wavefront per SIMD this kernel runs at) — at the address its table entry gives for this
+      // window's offset, which is wave-uniform: no decode, no select on address or value (the decode of a packed mode / row entry was 5 selects per slot and, at 494
+      // registers, their loop-invariant masks reloaded from SGPR spill lanes).  Only the trips that hold halo lanes (HALO) look at the entry: a halo window sends
+      // what would go to gg / gG to the lane's dummy slot instead.
 #pragma unroll
       for (int t = 0; t < PG::NTP; ++t)
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
-          const int te = rtab[t * 4 + v];
-          const int m = (te >> 16) & 3;
-          const bool ok = te >= 0 && (!HALO || m >= mlo) && wb + (te >> 18) < acc_lv;
-          const int idx = ok ? (te & 0xffff) + (m == 2 ? wbB : (m == 1 ? wb : 0)) : dummy + lane;
-          atomicAdd(&sm[idx], ok ? D[t][v] : 0.0);
+          const unsigned te = (unsigned)rtab[t * 4 + v];
+          const unsigned step = te >> 24;
+          unsigned off = (te & 0xffffffu) + step * (unsigned)wb;
+          if (HALO) off = (halo_w && step == 0u) ? (unsigned)(dummy + lane) * 8u : off;
+          atomicAdd((double*)((char*)sm + off), D[t][v]);
         }
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1724,6 +1729,7 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
   const int prim0 = ow.wg_c0[gridDim.x + 1 + wg];
   const bool use_halo = ow.own_k != nullptr && want_ne;
   constexpr int NACC = ACC_LV * ACC_BW + IMU_NGA * ACC_LV + IMU_NGA * IMU_NGA + ACC_LV + IMU_NGA;
+  static_assert((CR + 1) * 6 + IMU_RT_ROWS <= ACC_LV, "the window of a valid sample (interval <= k_lo + CR + 1, tested below) ends inside the accumulators: the scatter does not test it");
   for (int e = tid; e < NACC; e += 256) sm[e] = 0.0;   // (the panels need no clearing: every row a k-step reads is rewritten, the padding columns with it)
   int* urng = gpos + IMU_NGA;                        // [2]: first / last accumulator row of a batch end whose columns this workgroup does not store
   if (tid < IMU_NGA) gpos[tid] = cm.ord[6 * cm.N + tid];
@@ -1820,7 +1826,7 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
           }
         }
         if constexpr (EXP) { if (in && !valid && !hal) { put_skipped(cm, LVX_FAM_GYRO, fam.perm[si]); put_skipped(cm, LVX_FAM_ACCEL, fam.perm[si]); } }
-        if (want_ne) { if (base < prim0) imu_assemble<ImuG, true>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuG, false>(sm, P, rtg, valid, key, k_lo, ACC_LV, r, J, lane, NACC, 0); }
+        if (want_ne) { if (base < prim0) imu_assemble<ImuG, true>(sm, P, rtg, valid, key, k_lo, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuG, false>(sm, P, rtg, valid, key, k_lo, r, J, lane, NACC, 0); }
         IKT(2)
       }
       {   // accelerometer block (accel_residual, lvx_resid.h)
@@ -1863,7 +1869,7 @@ __global__ __launch_bounds__(256, 1) void k_imu_own(ImuFused fam, DevCommon cm, 
             if constexpr (EXP) put_record<3, ACC_NC>(cm, LVX_FAM_ACCEL, fam.perm[si], key, -1, -1, [&](int a, int c) { return J[a][c]; });
           }
         }
-        if (want_ne) { if (base < prim0) imu_assemble<ImuA, true>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuA, false>(sm, P, rta, valid, key, k_lo, ACC_LV, r, J, lane, NACC, 0); }
+        if (want_ne) { if (base < prim0) imu_assemble<ImuA, true>(sm, P, rta, valid, key, k_lo, r, J, lane, NACC, prim0 - base); else imu_assemble<ImuA, false>(sm, P, rta, valid, key, k_lo, r, J, lane, NACC, 0); }
         IKT(3)
       }
     }
