@@ -159,9 +159,10 @@ struct lvx_ctx {
   int solver_fallbacks = 0;   // lvx_layout::solver_fallbacks
   int lm_elim_kernel = 0;     // lvx_layout::lm_elim_kernel: which landmark elimination the last solve launched
   lvx::DevBuf d_ccov;         // lvx_calibration_covariance: the record k_calib_cov writes (LVX_CCOV_N doubles); ..._shared: record, kept factor and message of k_joint_cov_*
-  lvx::DevBuf d_tcov, d_tcov_io; void* h_tcov = nullptr; size_t h_tcov_cap = 0; bool tcov_d_unchecked = false;   // lvx_trajectory_covariance: [lowest band position | selected band | ring of k_band_selinv], [times | outputs] of the host form and their pinned mirror; a _d call awaits lvx_synchronize's look at its pivot word
-  lvx::DevBuf d_lcov;         // lvx_landmark_covariance: the wide band store of the selected inverse, SigW [nb][TB + 1] (its staging and flag words are lvx_trajectory_covariance's)
-  lvx::DevBuf d_ptcov;        // lvx_map_point_covariance: the record k_pt_hub leaves for k_point_cov (lvx::PtHub; staging and flag words are lvx_trajectory_covariance's)
+  lvx::DevBuf d_tcov; bool tcov_d_unchecked = false;   // the selected inverse (selinv_enqueue): [lowest band position | selected band SigB | ring of k_band_selinv]; a _d covariance query awaits lvx_synchronize's look at its pivot word
+  lvx::DevBuf d_cov_io; void* h_cov = nullptr; size_t h_cov_cap = 0;   // the staging the host forms of the three covariance queries share (cov_stage): [inputs | outputs | flag words] and its pinned mirror
+  lvx::DevBuf d_lcov;         // lvx_landmark_covariance: the wide band store of the selected inverse, SigW [nb][TB + 1]
+  lvx::DevBuf d_ptcov;        // lvx_map_point_covariance: the record k_pt_hub leaves for k_point_cov (lvx::PtHub)
   lvx::DevBuf d_bcrD, d_bcrG, d_bcrInfo, d_Y2, d_gram, d_bcrLinv; bool bcr_linv = false;   // d_bcrLinv: inverses of the factors' 16 x 16 diagonal triangles (k_potrf_batched -> k_trsm_reg)
   void* blas = nullptr;
   int bcr_b = 0, bcr_nblk = 0, bcr_nreal = 0;
@@ -280,6 +281,7 @@ int handoff_fetch_ids(lvx_ctx* c);   // surf.id0 of a device-origin family, fetc
 void traj_destroy(lvx_ctx* c);    // lvx_traj.hip
 void rotinit_destroy(lvx_ctx* c); // lvx_rotinit.hip
 int traj_check_d(lvx_ctx* c);      // lvx_traj.hip: the non-unit-quaternion flag of the _d trajectory queries (lvx_synchronize)
+int traj_flag_words(lvx_ctx* c);   // lvx_traj.hip: creates the flag words d_tj[3] of the trajectory queries on first use (the _d covariance queries of lvx_solver.hip share them)
 // leaves + separators elimination (lvx_nd.h): nd_plan decides from the column profile whether it applies (nd_active afterwards) and sizes its buffers
 int nd_plan(lvx_ctx* c, int nrhs);
 bool nd_active(const lvx_ctx* c);

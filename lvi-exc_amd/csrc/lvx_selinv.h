@@ -1,5 +1,7 @@
-// lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and what is read from it: pose covariances (lvx_trajectory_covariance) and
-// landmark covariances (lvx_landmark_covariance) and LiDAR map point covariances (lvx_map_point_covariance, at the end of the file).
+// lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and the three queries that read it.  In file order: the selected inverse
+// (k_border_inv, k_band_selinv); what the queries share (SigmaView and its accessors, the window of a pose's scalars, J W J^T); then what each adds — pose covariances
+// (lvx_trajectory_covariance: nothing but the pose Jacobian), landmark covariances (lvx_landmark_covariance: the eliminated landmark's row) and LiDAR map point
+// covariances (lvx_map_point_covariance: a lane per point, two pose windows and their cross block).
 // Included by lvx_solver.hip (its translation unit holds the factor's kernels).
 //
 // reduce_to_border(force_seq) leaves   Lb[j (bw + 1) + d] = L(j + d, j)   (band Cholesky),   Z[r ldz + j] = (L^-1 A_bc)(j, r)   and   S = A_cc - Zc^T Zc (unfactored),
@@ -208,19 +210,84 @@ __global__ __launch_bounds__(SI_NT) void k_band_selinv(SelInv g) {
   }
 }
 
-// One wavefront per query: lane 0 evaluates the pose and its Jacobian (lvx_trajcov.h) into LDS, the 31 scalars go through ord[] (>= 0 a band position, < 0 border
-// slot -1 - o, LVX_DEAD constant), the window of Sigma is gathered and unscaled, cov = J W J^T with every sum in index order (lower triangle computed, mirrored).
+// ---------------------------------------------------------------------------------------------------------
+// What every query reads from the factored step, written once.
+//   SigmaView       ord[] and the stores of Sigma' (the SCALED system's selected inverse): a band store with its row stride (SigB, stride SI_BD, or SigW, stride
+//                   TB + 1), Z's border rows, Sigma_cc, the Jacobi scale and the pivot words.
+//   sigma_at        Sigma' between two positions: >= 0 a band position, < 0 border slot -1 - o.  scale_at: the Jacobi scale of a position, 0 for LVX_DEAD.
+//   window_scalars  a window's tangent indices -> pos[] (through ord[]; LVX_DEAD constant or absent), sc[] and the index written out (-1 where dead).
+//   window_gather   W[a][b] = Sigma'(pos a, pos b) sc[a] sc[b] (unscaled), element e = lane, lane + 64, ...; zero where either scalar is dead.
+//   window_sandwich T = J W over a ascending, C = T J^T for r >= s over b ascending, mirrored: every sum in index order.
+// The helpers work on the calling kernel's __shared__ arrays, one wavefront per window; the bit identity between the queries (a landmark's pose window against
+// lvx_trajectory_covariance's, a point's t_map window likewise) is that of one piece of code.
+// ---------------------------------------------------------------------------------------------------------
+struct SigmaView {
+  const int* ord;
+  const double* band; int stride;   // band[j stride + d] = Sigma'(j + d, j), d < stride
+  const double* Z; int ldz, nb, nbd; const double* Scc; const double* scale;
+  const int* info; int force_bad;   // the factor's pivot codes; the tests' switch TEST_BAD_PIVOT
+};
+__device__ __forceinline__ bool sigma_lost(const SigmaView& v) { return v.force_bad || v.info[0] != 0 || v.info[1] != 0; }
+__device__ __forceinline__ double sigma_at(const SigmaView& v, int pa, int pb) {
+  if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; return d < v.stride ? v.band[(size_t)lo * v.stride + d] : 0.0; }
+  if (pa >= 0) return v.Z[(size_t)(-1 - pb) * v.ldz + pa];
+  if (pb >= 0) return v.Z[(size_t)(-1 - pa) * v.ldz + pb];
+  const int ra = -1 - pa, rb = -1 - pb;
+  return v.Scc[(size_t)max(ra, rb) * v.nbd + min(ra, rb)];
+}
+__device__ __forceinline__ double scale_at(const SigmaView& v, int o) { return o == LVX_DEAD ? 0.0 : v.scale[o >= 0 ? o : v.nb + (-1 - o)]; }
+// lanes first .. W - 1, one window scalar each (idx < 0: absent); widx null: not asked for
+template <int W>
+__device__ __forceinline__ void window_scalars(const SigmaView& v, const int* idx, int first, int lane, int* pos, double* sc, int32_t* widx) {
+  if (lane < first || lane >= W) return;
+  int o = LVX_DEAD, id = -1;
+  if (idx[lane] >= 0) { o = v.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane]; }
+  pos[lane] = o; sc[lane] = scale_at(v, o);
+  if (widx) widx[lane] = id;
+}
+// out null: not asked for; otherwise the window as [W][W], dense
+template <int W>
+__device__ __forceinline__ void window_gather(const SigmaView& v, const int* pos, const double* sc, int lane, double (*Wm)[W + 1], double* out) {
+  for (int e = lane; e < W * W; e += 64) {
+    const int a = e / W, b = e % W, pa = pos[a], pb = pos[b];
+    double s = 0.0;
+    if (pa != LVX_DEAD && pb != LVX_DEAD) s = sigma_at(v, pa, pb) * (sc[a] * sc[b]);
+    Wm[a][b] = s;
+    if (out) out[e] = s;
+  }
+}
+// (W complete before the call; C complete after it)
+template <int R, int W>
+__device__ __forceinline__ void window_sandwich(const double (*J)[W], const double (*Wm)[W + 1], int lane, double (*T)[W], double (*C)[R]) {
+  for (int e = lane; e < R * W; e += 64) {
+    const int r = e / W, b = e % W;
+    double s = 0.0;
+    for (int a = 0; a < W; ++a) s += J[r][a] * Wm[a][b];
+    T[r][b] = s;
+  }
+  __syncthreads();
+  if (lane < R * R) {
+    const int r = lane / R, s2 = lane % R;
+    if (r >= s2) {
+      double s = 0.0;
+      for (int b = 0; b < W; ++b) s += T[r][b] * J[s2][b];
+      C[r][s2] = s; C[s2][r] = s;
+    }
+  }
+  __syncthreads();
+}
+
+// lvx_trajectory_covariance.  One wavefront per query: lane 0 evaluates the pose and its 6 x 31 Jacobian (lvx_trajcov.h) into LDS; the shared pieces do the rest.
+// An invalid query (outside the trajectory, a non-unit control quaternion) holds zeros and indices of -1.
 struct PoseCov {
-  const double* state; int N; double t0, dt; int frame, n; const double* t; const int* ord;
-  const double* SigB; const double* Z; int ldz, nb, nbd; const double* Scc; const double* scale;
-  const int* info; int force_bad;
+  const double* state; int N; double t0, dt; int frame, n; const double* t; SigmaView v;
   double* cov; double* sigma; double* wcov; int32_t* widx; uint8_t* valid; int* flag; int* bad;
 };
 __global__ __launch_bounds__(64) void k_pose_cov(PoseCov g) {
   __shared__ double J[6][TCOV_W], W[TCOV_W][TCOV_W + 1], T[6][TCOV_W], sc[TCOV_W], Cv[6][6];
   __shared__ int idx[TCOV_W], pos[TCOV_W], status;
   const int lane = threadIdx.x, i = blockIdx.x;
-  if (g.force_bad || g.info[0] != 0 || g.info[1] != 0) { if (lane == 0 && i == 0) *g.bad = 1; return; }   // a lost pivot: nothing is written
+  if (sigma_lost(g.v)) { if (lane == 0 && i == 0) *g.bad = 1; return; }   // a lost pivot: nothing is written
   if (lane == 0) {
     const SplineRef sp{g.t0, g.dt, g.N, g.state, g.state + 3 * (size_t)g.N};
     SensorCal ext; ext.q = mkq(1, 0, 0, 0); ext.p = mk(0, 0, 0); ext.tau = 0.0;
@@ -233,47 +300,21 @@ __global__ __launch_bounds__(64) void k_pose_cov(PoseCov g) {
     status = st;
   }
   __syncthreads();
-  const bool ok = status == RES_OK;
-  if (lane < TCOV_W) {
-    int o = LVX_DEAD, id = -1;
-    if (ok && idx[lane] >= 0) { o = g.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane]; }
-    pos[lane] = o;
-    sc[lane] = o == LVX_DEAD ? 0.0 : g.scale[o >= 0 ? o : g.nb + (-1 - o)];
-    if (g.widx) g.widx[(size_t)i * TCOV_W + lane] = id;
+  const size_t W2 = (size_t)TCOV_W * TCOV_W;
+  if (status != RES_OK) {
+    if (lane == 0) g.valid[i] = 0;
+    if (lane < TCOV_W && g.widx) g.widx[(size_t)i * TCOV_W + lane] = -1;
+    if (g.wcov) for (int e = lane; e < (int)W2; e += 64) g.wcov[(size_t)i * W2 + e] = 0.0;
+    if (lane < 36 && g.cov) g.cov[(size_t)i * 36 + lane] = 0.0;
+    if (lane < 6 && g.sigma) g.sigma[(size_t)i * 6 + lane] = 0.0;
+    return;
   }
-  if (lane == 0) g.valid[i] = ok ? 1 : 0;
+  window_scalars<TCOV_W>(g.v, idx, 0, lane, pos, sc, g.widx ? g.widx + (size_t)i * TCOV_W : nullptr);
+  if (lane == 0) g.valid[i] = 1;
   __syncthreads();
-  for (int e = lane; e < TCOV_W * TCOV_W; e += 64) {
-    const int a = e / TCOV_W, b = e % TCOV_W;
-    const int pa = pos[a], pb = pos[b];
-    double v = 0.0;
-    if (pa != LVX_DEAD && pb != LVX_DEAD) {
-      if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; v = d < SI_BD ? g.SigB[(size_t)lo * SI_BD + d] : 0.0; }
-      else if (pa >= 0) v = g.Z[(size_t)(-1 - pb) * g.ldz + pa];
-      else if (pb >= 0) v = g.Z[(size_t)(-1 - pa) * g.ldz + pb];
-      else { const int ra = -1 - pa, rb = -1 - pb; v = g.Scc[(size_t)max(ra, rb) * g.nbd + min(ra, rb)]; }
-      v *= sc[a] * sc[b];
-    }
-    W[a][b] = v;
-    if (g.wcov) g.wcov[(size_t)i * TCOV_W * TCOV_W + e] = v;
-  }
+  window_gather<TCOV_W>(g.v, pos, sc, lane, W, g.wcov ? g.wcov + (size_t)i * W2 : nullptr);
   __syncthreads();
-  for (int e = lane; e < 6 * TCOV_W; e += 64) {
-    const int r = e / TCOV_W, b = e % TCOV_W;
-    double s = 0.0;
-    if (ok) for (int a = 0; a < TCOV_W; ++a) s += J[r][a] * W[a][b];
-    T[r][b] = s;
-  }
-  __syncthreads();
-  if (lane < 36) {
-    const int r = lane / 6, s2 = lane % 6;
-    if (r >= s2) {
-      double s = 0.0;
-      if (ok) for (int b = 0; b < TCOV_W; ++b) s += T[r][b] * J[s2][b];
-      Cv[r][s2] = s; Cv[s2][r] = s;
-    }
-  }
-  __syncthreads();
+  window_sandwich<6, TCOV_W>(J, W, lane, T, Cv);
   if (lane < 36 && g.cov) g.cov[(size_t)i * 36 + lane] = Cv[lane / 6][lane % 6];
   if (lane < 6 && g.sigma) g.sigma[(size_t)i * 6 + lane] = sqrt(Cv[lane][lane]);
 }
@@ -283,7 +324,8 @@ __global__ __launch_bounds__(64) void k_pose_cov(PoseCov g) {
 // border, d_l = s_l^2 H_ll + lmd_l / radius, w_l = s_l^2 / d_l and Sigma_xx the UNSCALED covariance of the reduced system (the selected inverse above),
 //   Sigma_ll = w_l + w_l^2 E_l Sigma_xx E_l^T,      Sigma_lx = -w_l E_l Sigma_xx
 // Every entry of Sigma_xx that E_l or the reference pose's window touches lies on the factor's pattern: the elimination wrote E_l^T E_l into the band, so the reach of
-// a landmark's row is <= bw <= TB.  Those entries are read from SigW[j][d] = Sigma(j + d, j), d <= TB, which k_band_selinv stores beside SigB when asked to.
+// a landmark's row is <= bw <= TB.  Those entries are read from SigW[j][d] = Sigma(j + d, j), d <= TB, which k_band_selinv stores beside SigB when asked to: the
+// query's SigmaView has SigW as its band store.  On top of the shared pieces the query adds the landmark's row (E_l Sigma_xx E_l^T and the 31 cross terms).
 // ---------------------------------------------------------------------------------------------------------
 struct LmQuery {
   const double* state; int N; double t0, dt; CamIntr cam; const double* lm_uv; const double* lm_t0; int L; const int* ord;
@@ -313,31 +355,23 @@ __global__ void k_lc_lowest(LmQuery q, int* lowest) {
 
 struct LmCov {
   LmQuery q;
-  const double* SigW; int TB; const double* Z; int ldz, nb, nbd; const double* Scc;
-  const double* scale; const double* lmd; double inv_radius;   // scale / lmd: SolveWork's, [band | border | landmarks]
-  const int* info; int force_bad;
+  SigmaView v;                                   // the band store is SigW: the couplings of a landmark's row reach up to TB
+  const double* lmd; double inv_radius;          // lmd and v.scale: SolveWork's, [band | border | landmarks]
   double* var; double* sigma; double* point; double* pcov; double* wcov; int32_t* widx; uint8_t* valid; int* flag; int* bad;
 };
-// Sigma' (scaled) between two positions: >= 0 a band position, < 0 border slot -1 - o
-__device__ __forceinline__ double lc_sigma(const LmCov& g, int pa, int pb) {
-  if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; return d <= g.TB ? g.SigW[(size_t)lo * (g.TB + 1) + d] : 0.0; }
-  if (pa >= 0) return g.Z[(size_t)(-1 - pb) * g.ldz + pa];
-  if (pb >= 0) return g.Z[(size_t)(-1 - pa) * g.ldz + pb];
-  const int ra = -1 - pa, rb = -1 - pb;
-  return g.Scc[(size_t)max(ra, rb) * g.nbd + min(ra, rb)];
-}
 // One wavefront per queried landmark.  Lane 0 evaluates the map point and its 3 x 32 Jacobian (lvx_lmcov.h); the non-zeros of the landmark's row are compacted by
 // ballot in index order (value times the Jacobi scale of its column, position); E Sigma E^T runs over the pairs a <= b with the lanes along b — the entries of one row
 // of SigW, consecutive where the couplings are — each lane adding its terms in (a, b) order, the lanes joined by a butterfly (every lane ends with the same bits); the 31
-// cross terms take a lane pair per window scalar.  The window, J W J^T and the stores follow k_pose_cov.  Dynamic LDS: ev [ne] doubles | epos [ne] ints, ne = wl + nbd.
+// cross terms take a lane pair per window scalar.  Window scalar 0 is the landmark itself: dead to the shared gather, its row and column of W are written afterwards.
+// Dynamic LDS: ev [ne] doubles | epos [ne] ints, ne = wl + nbd.
 __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
   extern __shared__ double lds_e[];
   __shared__ double Jp[6][TCOV_W], J[3][LCOV_W], W[LCOV_W][LCOV_W + 1], T[3][LCOV_W], sc[LCOV_W], Cv[3][3], Pw[3];
   __shared__ int idx[LCOV_W], pos[LCOV_W], status, lm_s;
   const LmQuery& q = g.q;
-  const int lane = threadIdx.x, i = blockIdx.x, ne = q.wl + g.nbd;
+  const int lane = threadIdx.x, i = blockIdx.x, ne = q.wl + g.v.nbd;
   double* ev = lds_e; int* epos = (int*)(lds_e + ne);
-  if (g.force_bad || g.info[0] != 0 || g.info[1] != 0) { if (lane == 0 && i == 0) *g.bad = 1; return; }   // a lost pivot: nothing is written
+  if (sigma_lost(g.v)) { if (lane == 0 && i == 0) *g.bad = 1; return; }   // a lost pivot: nothing is written
   if (lane == 0) {
     KnotRef k; bool pose = false;
     const int l = lc_landmark(q, i, &k, &pose);
@@ -362,14 +396,8 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
     return;
   }
   const int l = lm_s;
-  if (lane < LCOV_W) {
-    int o = LVX_DEAD, id = -1;
-    if (lane == 0) { o = LVX_LM_BASE; id = idx[0]; }
-    else if (idx[lane] >= 0) { o = q.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane]; }
-    pos[lane] = o;
-    sc[lane] = (lane == 0 || o == LVX_DEAD) ? 0.0 : g.scale[o >= 0 ? o : g.nb + (-1 - o)];
-    if (g.widx) g.widx[(size_t)i * LCOV_W + lane] = id;
-  }
+  window_scalars<LCOV_W>(g.v, idx, 1, lane, pos, sc, g.widx ? g.widx + (size_t)i * LCOV_W : nullptr);
+  if (lane == 0) { pos[0] = LVX_DEAD; sc[0] = 0.0; if (g.widx) g.widx[(size_t)i * LCOV_W] = idx[0]; }
   // the landmark's row: non-zeros in index order
   const double* row = q.lmH ? q.lmH + (size_t)l * q.ls : nullptr;
   const double Hll = row ? row[q.wl + q.nbd_ext] : 0.0;
@@ -379,10 +407,10 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
     for (int k0 = 0; k0 < ne; k0 += 64) {
       const int k = k0 + lane;
       double e = 0.0; int p = 0;
-      if (k < ne) { p = k < q.wl ? p0 + k : -1 - (k - q.wl); if (k >= q.wl || p < g.nb) e = row[k]; }
+      if (k < ne) { p = k < q.wl ? p0 + k : -1 - (k - q.wl); if (k >= q.wl || p < g.v.nb) e = row[k]; }
       const bool nz = e != 0.0;
       const unsigned long long mask = __ballot(nz);
-      if (nz) { const int at = nn + __popcll(mask & ((1ull << lane) - 1ull)); ev[at] = e * g.scale[p >= 0 ? p : g.nb + (-1 - p)]; epos[at] = p; }
+      if (nz) { const int at = nn + __popcll(mask & ((1ull << lane) - 1ull)); ev[at] = e * scale_at(g.v, p); epos[at] = p; }
       nn += __popcll(mask);
     }
   }
@@ -390,43 +418,23 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
   double acc = 0.0;
   for (int a = 0; a < nn; ++a) {
     const int pa = epos[a]; const double ea = ev[a];
-    for (int b = a + lane; b < nn; b += 64) { const double t = ea * ev[b] * lc_sigma(g, pa, epos[b]); acc += b == a ? t : 2.0 * t; }
+    for (int b = a + lane; b < nn; b += 64) { const double t = ea * ev[b] * sigma_at(g.v, pa, epos[b]); acc += b == a ? t : 2.0 * t; }
   }
   for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
   const int m = lane & 31, pm = pos[m];
   double cm = 0.0;
-  if (m > 0 && pm != LVX_DEAD) for (int a = lane >> 5; a < nn; a += 2) cm += ev[a] * lc_sigma(g, epos[a], pm);
+  if (pm != LVX_DEAD) for (int a = lane >> 5; a < nn; a += 2) cm += ev[a] * sigma_at(g.v, epos[a], pm);
   cm += __shfl_xor(cm, 32);
   double s = 1.0, dmp = 1e-6;   // no landmark rows: the solver holds no diagonal for the landmarks; an unobserved one has scale 1 and the floor of the damping
-  if (row) { s = g.scale[g.nb + g.nbd + l]; dmp = g.lmd[g.nb + g.nbd + l]; }
+  if (row) { s = g.v.scale[g.v.nb + g.v.nbd + l]; dmp = g.lmd[g.v.nb + g.v.nbd + l]; }
   const double w = s * s / (s * s * Hll + dmp * g.inv_radius);
-  for (int e = lane; e < (int)W2; e += 64) {
-    const int a = e / LCOV_W, b = e % LCOV_W;
-    double v = 0.0;
-    if (a > 0 && b > 0) { const int pa = pos[a], pb = pos[b]; if (pa != LVX_DEAD && pb != LVX_DEAD) v = lc_sigma(g, pa, pb) * (sc[a] * sc[b]); }
-    W[a][b] = v;
-  }
+  window_gather<LCOV_W>(g.v, pos, sc, lane, W, nullptr);
   __syncthreads();
   if (lane == 0) W[0][0] = w + w * w * acc;
   else if (lane < LCOV_W) { const double v = pm != LVX_DEAD ? -w * cm * sc[lane] : 0.0; W[0][lane] = v; W[lane][0] = v; }
   __syncthreads();
   if (g.wcov) for (int e = lane; e < (int)W2; e += 64) g.wcov[(size_t)i * W2 + e] = W[e / LCOV_W][e % LCOV_W];
-  for (int e = lane; e < 3 * LCOV_W; e += 64) {
-    const int r = e / LCOV_W, b = e % LCOV_W;
-    double t = 0.0;
-    for (int a = 0; a < LCOV_W; ++a) t += J[r][a] * W[a][b];
-    T[r][b] = t;
-  }
-  __syncthreads();
-  if (lane < 9) {
-    const int r = lane / 3, s2 = lane % 3;
-    if (r >= s2) {
-      double t = 0.0;
-      for (int b = 0; b < LCOV_W; ++b) t += T[r][b] * J[s2][b];
-      Cv[r][s2] = t; Cv[s2][r] = t;
-    }
-  }
-  __syncthreads();
+  window_sandwich<3, LCOV_W>(J, W, lane, T, Cv);
   if (lane < 9 && g.pcov) g.pcov[(size_t)i * 9 + lane] = Cv[lane / 3][lane % 3];
   if (lane < 3 && g.point) g.point[(size_t)i * 3 + lane] = Pw[lane];
   if (lane == 0) { g.valid[i] = 1; if (g.var) g.var[i] = W[0][0]; if (g.sigma) g.sigma[i] = sqrt(W[0][0]); }
@@ -435,7 +443,7 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
 // ---------------------------------------------------------------------------------------------------------
 // lvx_map_point_covariance (lvx_ptcov.h has the algebra).  A map is 1e5 .. 1e6 points per call, so a LANE owns a point here, not a wavefront.
 //   k_pt_hub     once per call, one wavefront: the pose Jacobian J0 at t_map + tau_L, its window W00 (hub knots and the LiDAR's scalars: border x border) and
-//                C00 = J0 W00 J0^T, exactly as k_pose_cov forms them.  It also decides what makes the whole call fail: a lost pivot (status 1), a scalar of the t_map
+//                C00 = J0 W00 J0^T, by the shared pieces.  It also decides what makes the whole call fail: a lost pivot (status 1), a scalar of the t_map
 //                window that is a BAND position — its cross terms with a point's knots would be off the factor's pattern (status 2).
 //   k_point_cov  256 points per workgroup.  Every lane evaluates its own pose Jacobian and Gk = A_k Jk (3 x 31, registers).  The windows depend on the knot interval
 //                only: the workgroup walks the DISTINCT intervals of its points in ascending order (an integer minimum in LDS — times may arrive in any order), stages
@@ -448,16 +456,6 @@ __global__ __launch_bounds__(64) void k_landmark_cov(LmCov g) {
 // ---------------------------------------------------------------------------------------------------------
 #define PC_NT 256
 #define PC_TS 115        // doubles per point of a wavefront's tile: Gk as [3][32] (96), then T as [3][PCOV_TW] (114); odd, so 16 points spread over the banks
-struct PtAccess { const int* ord; const double* SigB; const double* Z; int ldz, nb, nbd; const double* Scc; const double* scale; };
-// Sigma' (scaled) between two live positions, as k_pose_cov reads it: >= 0 a band position, < 0 border slot -1 - o
-__device__ __forceinline__ double pc_sigma(const PtAccess& s, int pa, int pb) {
-  if (pa >= 0 && pb >= 0) { const int lo = min(pa, pb), d = max(pa, pb) - lo; return d < SI_BD ? s.SigB[(size_t)lo * SI_BD + d] : 0.0; }
-  if (pa >= 0) return s.Z[(size_t)(-1 - pb) * s.ldz + pa];
-  if (pb >= 0) return s.Z[(size_t)(-1 - pa) * s.ldz + pb];
-  const int ra = -1 - pa, rb = -1 - pb;
-  return s.Scc[(size_t)max(ra, rb) * s.nbd + min(ra, rb)];
-}
-__device__ __forceinline__ double pc_scale(const PtAccess& s, int o) { return o == LVX_DEAD ? 0.0 : s.scale[o >= 0 ? o : s.nb + (-1 - o)]; }
 struct PtHub {   // what k_pt_hub leaves for k_point_cov
   double J0[6][32];                 // column 31 zero
   double W00[TCOV_W][TCOV_W];
@@ -468,7 +466,7 @@ struct PtHub {   // what k_pt_hub leaves for k_point_cov
 struct PtCov {
   const double* state; int N; double t0, dt, t_map; int n;
   const double* pt; const float* xyzi; const double* t; const double* dir;   // pt [n][3] or xyzi [n][4] (the scan buffers' layout)
-  PtAccess s; const int* info; int force_bad; PtHub* hub;
+  SigmaView v; PtHub* hub;
   double* point; double* cov; double* sigma; double* sigma_max; double* var_dir; double* wcov; int32_t* widx; uint8_t* valid; int* flag; int* bad;
 };
 __device__ __forceinline__ SensorCal pc_lidar(const PtCov& g) {
@@ -476,12 +474,13 @@ __device__ __forceinline__ SensorCal pc_lidar(const PtCov& g) {
   SensorCal ext; ext.q = load_q(ss); ext.p = load_v3(ss + 4); ext.tau = ss[7];
   return ext;
 }
+// The pose window of ONE query — the LiDAR frame at t_map — as k_pose_cov forms it, stored to PtHub; what is its own are the status decisions.
 __global__ __launch_bounds__(64) void k_pt_hub(PtCov g) {
   __shared__ double J[6][TCOV_W], W[TCOV_W][TCOV_W + 1], T[6][TCOV_W], sc[TCOV_W], Cv[6][6];
   __shared__ int idx[TCOV_W], pos[TCOV_W], status;
   const int lane = threadIdx.x;
   PtHub* h = g.hub;
-  if (g.force_bad || g.info[0] != 0 || g.info[1] != 0) { if (lane == 0) { h->status = 1; *g.bad = 1; } return; }   // a lost pivot: nothing is written
+  if (sigma_lost(g.v)) { if (lane == 0) { h->status = 1; *g.bad = 1; } return; }   // a lost pivot: nothing is written
   if (lane == 0) {
     const SplineRef sp{g.t0, g.dt, g.N, g.state, g.state + 3 * (size_t)g.N};
     const SensorCal ext = pc_lidar(g);
@@ -494,40 +493,14 @@ __global__ __launch_bounds__(64) void k_pt_hub(PtCov g) {
   __syncthreads();
   if (status == RES_RANGE) { if (lane == 0) { h->status = 2; *g.bad = 2; } return; }   // t_map + tau_L has left the trajectory
   if (status == RES_NONUNIT) { if (lane == 0) { h->status = 3; *g.flag = RES_NONUNIT; } return; }
-  int o = LVX_DEAD;
-  if (lane < TCOV_W) {
-    int id = -1;
-    o = g.s.ord[idx[lane]]; if (o != LVX_DEAD) id = idx[lane];
-    pos[lane] = o; sc[lane] = pc_scale(g.s, o);
-    h->pos[lane] = o; h->idx[lane] = id; h->sc[lane] = sc[lane];
-  }
-  if (__any(lane < 24 && o != LVX_DEAD && o >= 0)) { if (lane == 0) { h->status = 2; *g.bad = 2; } return; }   // a free knot scalar of the t_map window in the band
+  window_scalars<TCOV_W>(g.v, idx, 0, lane, pos, sc, h->idx);
+  if (lane < TCOV_W) { h->pos[lane] = pos[lane]; h->sc[lane] = sc[lane]; }
+  if (__any(lane < 24 && pos[lane] != LVX_DEAD && pos[lane] >= 0)) { if (lane == 0) { h->status = 2; *g.bad = 2; } return; }   // a free knot scalar of the t_map window in the band
   __syncthreads();
-  for (int e = lane; e < TCOV_W * TCOV_W; e += 64) {
-    const int a = e / TCOV_W, b = e % TCOV_W;
-    const int pa = pos[a], pb = pos[b];
-    double v = 0.0;
-    if (pa != LVX_DEAD && pb != LVX_DEAD) { v = pc_sigma(g.s, pa, pb); v *= sc[a] * sc[b]; }
-    W[a][b] = v; h->W00[a][b] = v;
-  }
+  window_gather<TCOV_W>(g.v, pos, sc, lane, W, &h->W00[0][0]);
   for (int e = lane; e < 6 * 32; e += 64) h->J0[e >> 5][e & 31] = (e & 31) < TCOV_W ? J[e >> 5][e & 31] : 0.0;
   __syncthreads();
-  for (int e = lane; e < 6 * TCOV_W; e += 64) {
-    const int r = e / TCOV_W, b = e % TCOV_W;
-    double s = 0.0;
-    for (int a = 0; a < TCOV_W; ++a) s += J[r][a] * W[a][b];
-    T[r][b] = s;
-  }
-  __syncthreads();
-  if (lane < 36) {
-    const int r = lane / 6, s2 = lane % 6;
-    if (r >= s2) {
-      double s = 0.0;
-      for (int b = 0; b < TCOV_W; ++b) s += T[r][b] * J[s2][b];
-      Cv[r][s2] = s; Cv[s2][r] = s;
-    }
-  }
-  __syncthreads();
+  window_sandwich<6, TCOV_W>(J, W, lane, T, Cv);
   if (lane < 36) h->C00[lane] = Cv[lane / 6][lane % 6];
   if (lane == 0) h->status = 0;
 }
@@ -613,8 +586,8 @@ __global__ __launch_bounds__(PC_NT) void k_point_cov(PtCov g) {
     // the interval's windows, once for the workgroup
     if (tid < 32) {
       int o = LVX_DEAD, id = -1;
-      if (tid < TCOV_W) { const int gi = tid < 24 ? 6 * cur + tid : 6 * g.N + 8 + (tid - 24); o = g.s.ord[gi]; if (o != LVX_DEAD) id = gi; }
-      posk[tid] = o; idxk[tid] = id; sck[tid] = pc_scale(g.s, o);
+      if (tid < TCOV_W) { const int gi = tid < 24 ? 6 * cur + tid : 6 * g.N + 8 + (tid - 24); o = g.v.ord[gi]; if (o != LVX_DEAD) id = gi; }
+      posk[tid] = o; idxk[tid] = id; sck[tid] = scale_at(g.v, o);
     }
     __syncthreads();
     for (int e = tid; e < 32 * 32; e += PC_NT) {
@@ -623,8 +596,8 @@ __global__ __launch_bounds__(PC_NT) void k_point_cov(PtCov g) {
       double vk = 0.0, v0 = 0.0;
       if (pa != LVX_DEAD) {
         const int pb = posk[b], qb = pos0[b];
-        if (pb != LVX_DEAD) { vk = pc_sigma(g.s, pa, pb); vk *= sck[a] * sck[b]; }
-        if (qb != LVX_DEAD) { v0 = pc_sigma(g.s, pa, qb); v0 *= sck[a] * sc0[b]; }
+        if (pb != LVX_DEAD) { vk = sigma_at(g.v, pa, pb); vk *= sck[a] * sck[b]; }
+        if (qb != LVX_DEAD) { v0 = sigma_at(g.v, pa, qb); v0 *= sck[a] * sc0[b]; }
       }
       Wkk[a][b] = vk;
       if (a < TCOV_W) Wk0[a][b] = v0;

@@ -1631,6 +1631,13 @@ static int reduce_candidate(LmRun& r, int lerr, const EvalLocal& ev, const doubl
   r2[4] += h[4]; r2[5] += h[5];
   return LVX_OK;
 }
+// the defaults of the three covariance queries on the selected inverse (a template: outside the C linkage block)
+template <class Opt>
+static int cov_default_options(Opt* o) {
+  if (!o) return LVX_E_ARG;
+  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
+  return LVX_OK;
+}
 
 extern "C" {
 
@@ -1722,13 +1729,12 @@ int lvx_calibration_covariance(lvx_ctx* c, const lvx_calib_cov_options* opt, lvx
   return LVX_OK;
 }
 
-int lvx_traj_cov_default_options(lvx_traj_cov_options* o) {
-  if (!o) return LVX_E_ARG;
-  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
-  return LVX_OK;
-}
+// ---- the covariance queries on the selected inverse: lvx_trajectory_covariance, lvx_landmark_covariance, lvx_map_point_covariance ----
+int lvx_traj_cov_default_options(lvx_traj_cov_options* o) { return cov_default_options(o); }
+int lvx_landmark_cov_default_options(lvx_landmark_cov_options* o) { return cov_default_options(o); }
+int lvx_point_cov_default_options(lvx_point_cov_options* o) { return cov_default_options(o); }
 // lvx_calibration_covariance's front half with the sequential band Cholesky forced, then the selected inverse of that factor (lvx_selinv.h): what
-// lvx_trajectory_covariance and lvx_landmark_covariance share.  lowest(head) queues the kernel that lowers *head (started at nb) to the lowest band position a query
+// the three queries share.  lowest(head) queues the kernel that lowers *head (started at nb) to the lowest band position a query
 // needs; wide: the band store SigW (d <= TB, lvx_ctx::d_lcov) is written beside SigB.  Everything is queued.
 struct SelInvOut { double* SigB; double* SigW; int TB; };
 static int selinv_enqueue(lvx_ctx* c, const std::string& who, double radius, int scaling, bool wide, SolveWork& w, SelInvOut* so, const std::function<void(int*)>& lowest) {
@@ -1765,6 +1771,77 @@ static int selinv_enqueue(lvx_ctx* c, const std::string& who, double radius, int
   }
   return LVX_OK;
 }
+// what a query's kernels read of the factored step: the band store is SigB (stride SI_BD) or SigW (stride TB + 1)
+static SigmaView sigma_view(lvx_ctx* c, const SolveWork& w, const double* band, int stride) {
+  return SigmaView{(const int*)c->d_ord.p, band, stride, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale, (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0};
+}
+// The checks the three queries make alike, in the order each of them always made its own: the context; the arguments (required_ok: the query's required pointers;
+// reserved null: lvx_trajectory_covariance has never looked at opt->reserved, and still does not); own_arg, the query's own argument condition (its message, null when
+// met); the preceding evaluation; the joint solve; own_state likewise; the device and the evaluation's error word.
+static int cov_common_args(lvx_ctx* c, const std::string& who, bool required_ok, double radius, const int32_t* reserved, int n, const char* own_arg, const char* own_state) {
+  if (!c) return LVX_E_ARG;
+  if (!required_ok || n <= 0 || !(radius > 0) || (reserved && *reserved != 0))
+    return fail(c, LVX_E_ARG, who + ": n <= 0, radius <= 0" + (reserved ? ", reserved != 0" : "") + " or a required pointer is NULL");
+  if (own_arg) return fail(c, LVX_E_ARG, who + ": " + own_arg);
+  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, who + " needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
+  if (is_joint(c)) return fail(c, LVX_E_STATE, who + ": the context takes part in a joint solve");
+  if (own_state) return fail(c, LVX_E_STATE, who + ": " + own_state);
+  LVX_HIP(c, hipSetDevice(c->device));
+  return check_last_eval(c);
+}
+// The flag words of a _d form: those of the _d trajectory queries (lvx_traj.hip), kept until lvx_synchronize looks.
+static int cov_d_flags(lvx_ctx* c, int** flags) {
+  int rc = traj_flag_words(c);
+  if (rc) return rc;
+  c->tcov_d_unchecked = true;
+  *flags = (int*)c->d_tj[3].p + 1;
+  return LVX_OK;
+}
+// The staging of a host form (lvx_ctx::d_cov_io and its pinned mirror h_cov, shared by the three queries): [inputs | outputs | 2 flag words], every array on a 16-byte
+// boundary.  An array the caller does not give (h null) takes no bytes, has no device address and is not computed.  cov_stage lays the arrays out, grows the two
+// buffers, uploads the inputs in one copy and clears the flags; behind the query's enqueue cov_finish brings outputs, flags and pivot codes back — the one host stop —
+// and turns the flags into the return code.
+struct CovArr { void* h; size_t bytes; };
+struct CovStage { enum { MAX = 12 }; int n, nin; void* h[MAX]; size_t bytes[MAX], off[MAX + 1], total; void* d[MAX]; int* flags; };
+static int cov_stage(lvx_ctx* c, std::initializer_list<CovArr> in, std::initializer_list<CovArr> out, CovStage* s) {
+  int rc;
+  s->n = 0; s->nin = (int)in.size();
+  size_t cur = 0;
+  for (const auto* list : {&in, &out})
+    for (const CovArr& a : *list) { const int k = s->n++; s->h[k] = a.h; s->bytes[k] = a.h ? a.bytes : 0; s->off[k] = cur; cur += (s->bytes[k] + 15) & ~(size_t)15; }
+  s->off[s->n] = cur; s->total = cur + 16;
+  if ((rc = dev_alloc(c, c->d_cov_io, s->total))) return rc;
+  if (c->h_cov_cap < s->total) {
+    if (c->h_cov) { (void)hipHostFree(c->h_cov); c->h_cov = nullptr; c->h_cov_cap = 0; }
+    LVX_HIP(c, hipHostMalloc(&c->h_cov, s->total, hipHostMallocDefault));
+    c->h_cov_cap = s->total;
+  }
+  char* d = (char*)c->d_cov_io.p; char* h = (char*)c->h_cov;
+  for (int k = 0; k < s->n; ++k) s->d[k] = s->bytes[k] ? d + s->off[k] : nullptr;
+  s->flags = (int*)(d + cur);
+  for (int k = 0; k < s->nin; ++k) if (s->bytes[k]) std::memcpy(h + s->off[k], s->h[k], s->bytes[k]);
+  if (s->off[s->nin]) LVX_HIP(c, hipMemcpyAsync(d, h, s->off[s->nin], hipMemcpyHostToDevice, c->stream));
+  LVX_HIP(c, hipMemsetAsync(s->flags, 0, 16, c->stream));
+  return LVX_OK;
+}
+// off_border: the message of flags[1] == 2 (lvx_map_point_covariance: the window of t_map is off the border), null for a query without that status
+static int cov_finish(lvx_ctx* c, const CovStage& s, const char* off_border = nullptr) {
+  hipStream_t st = c->stream;
+  const size_t o0 = s.off[s.nin];
+  char* d = (char*)c->d_cov_io.p; char* h = (char*)c->h_cov;
+  LVX_HIP(c, hipMemcpyAsync(h + o0, d + o0, s.total - o0, hipMemcpyDeviceToHost, st));
+  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
+  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
+  int fl[2]; std::memcpy(fl, h + s.off[s.n], 8);
+  if (fl[1] == 2 && off_border) return fail(c, LVX_E_STATE, off_border);
+  if (fl[1]) {
+    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
+    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
+  }
+  for (int k = s.nin; k < s.n; ++k) if (s.bytes[k]) std::memcpy(s.h[k], h + s.off[k], s.bytes[k]);
+  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
+  return LVX_OK;
+}
 // One wavefront per query behind the selected inverse: t_d and the arrays of o are device addresses; flags[0] takes RES_NONUNIT, flags[1] a lost pivot (nothing
 // written then).
 static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov& o, int* flags) {
@@ -1774,74 +1851,33 @@ static int traj_cov_enqueue(lvx_ctx* c, const lvx_traj_cov_options* opt, int fra
   const double* state_d = c->last_state_d;
   if ((rc = selinv_enqueue(c, "lvx_trajectory_covariance", opt->radius, opt->jacobi_scaling, false, w, &so, [&](int* head) {
         hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, head); }))) return rc;
-  PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, (const int*)c->d_ord.p, (const double*)so.SigB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale,
-            (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.cov, o.sigma, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
+  PoseCov p{state_d, c->N, c->t0, c->dt, frame, n, t_d, sigma_view(c, w, so.SigB, SI_BD), o.cov, o.sigma, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
   { ProfScope ps(c, LVX_KERNEL_POSE_COV); hipLaunchKernelGGL(k_pose_cov, dim3((unsigned)n), dim3(64), 0, st, p); }
   LVX_HIP(c, hipGetLastError());
   return LVX_OK;
 }
 static int traj_cov_args(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t, const lvx_traj_cov* out) {
-  if (!c) return LVX_E_ARG;
-  if (!opt || !t || !out || !out->valid || n <= 0 || !(opt->radius > 0)) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: n <= 0, radius <= 0 or a required pointer is NULL");
-  if (frame != LVX_FRAME_TRAJECTORY && frame != LVX_FRAME_LIDAR && frame != LVX_FRAME_CAMERA) return fail(c, LVX_E_ARG, "lvx_trajectory_covariance: unknown frame");
-  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_trajectory_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
-  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_trajectory_covariance: the context takes part in a joint solve");
-  LVX_HIP(c, hipSetDevice(c->device));
-  return check_last_eval(c);
+  const bool known = frame == LVX_FRAME_TRAJECTORY || frame == LVX_FRAME_LIDAR || frame == LVX_FRAME_CAMERA;
+  return cov_common_args(c, "lvx_trajectory_covariance", opt && t && out && out->valid, opt ? opt->radius : 0.0, nullptr, n, known ? nullptr : "unknown frame", nullptr);
 }
 int lvx_trajectory_covariance_d(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t_d, const lvx_traj_cov* out_d) {
   int rc = traj_cov_args(c, opt, frame, n, t_d, out_d);
-  if (rc) return rc;
-  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
-    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
-    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
-  }
-  c->tcov_d_unchecked = true;
-  return traj_cov_enqueue(c, opt, frame, n, t_d, *out_d, (int*)c->d_tj[3].p + 1);
+  int* flags;
+  if (rc || (rc = cov_d_flags(c, &flags))) return rc;
+  return traj_cov_enqueue(c, opt, frame, n, t_d, *out_d, flags);
 }
 int lvx_trajectory_covariance(lvx_ctx* c, const lvx_traj_cov_options* opt, int frame, int n, const double* t, lvx_traj_cov* out) {
   int rc = traj_cov_args(c, opt, frame, n, t, out);
   if (rc) return rc;
-  hipStream_t st = c->stream;
-  // device and pinned images: [t | cov | sigma | window_cov | window_idx | valid | flags (2 ints)]; an array the caller does not ask for is not computed
   const size_t nn = (size_t)n, W2 = (size_t)LVX_TRAJ_COV_W * LVX_TRAJ_COV_W;
-  size_t off[7]; size_t cur = 0;
-  const size_t bytes[6] = {nn * 8, out->cov ? nn * 36 * 8 : 0, out->sigma ? nn * 6 * 8 : 0, out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_TRAJ_COV_W * 4 : 0, nn};
-  for (int k = 0; k < 6; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
-  off[6] = cur; cur += 16;
-  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
-  if (c->h_tcov_cap < cur) {
-    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
-    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
-    c->h_tcov_cap = cur;
-  }
-  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
-  std::memcpy(h, t, nn * 8);
-  LVX_HIP(c, hipMemcpyAsync(d, h, nn * 8, hipMemcpyHostToDevice, st));
-  LVX_HIP(c, hipMemsetAsync(d + off[6], 0, 16, st));
-  lvx_traj_cov od;
-  od.cov = out->cov ? (double*)(d + off[1]) : nullptr; od.sigma = out->sigma ? (double*)(d + off[2]) : nullptr; od.window_cov = out->window_cov ? (double*)(d + off[3]) : nullptr;
-  od.window_idx = out->window_idx ? (int32_t*)(d + off[4]) : nullptr; od.valid = (uint8_t*)(d + off[5]);
-  if ((rc = traj_cov_enqueue(c, opt, frame, n, (const double*)d, od, (int*)(d + off[6])))) return rc;
-  LVX_HIP(c, hipMemcpyAsync(h + off[1], d + off[1], cur - off[1], hipMemcpyDeviceToHost, st));
-  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
-  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
-  int fl[2]; std::memcpy(fl, h + off[6], 8);
-  if (fl[1]) {
-    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
-    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
-  }
-  void* dst[6] = {nullptr, out->cov, out->sigma, out->window_cov, out->window_idx, out->valid};
-  for (int k = 1; k < 6; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
-  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
-  return LVX_OK;
+  CovStage s;
+  if ((rc = cov_stage(c, {{(void*)t, nn * 8}},
+                      {{out->cov, nn * 36 * 8}, {out->sigma, nn * 6 * 8}, {out->window_cov, nn * W2 * 8}, {out->window_idx, nn * LVX_TRAJ_COV_W * 4}, {out->valid, nn}}, &s))) return rc;
+  const lvx_traj_cov od{(double*)s.d[1], (double*)s.d[2], (double*)s.d[3], (int32_t*)s.d[4], (uint8_t*)s.d[5]};
+  if ((rc = traj_cov_enqueue(c, opt, frame, n, (const double*)s.d[0], od, s.flags))) return rc;
+  return cov_finish(c, s);
 }
 
-int lvx_landmark_cov_default_options(lvx_landmark_cov_options* o) {
-  if (!o) return LVX_E_ARG;
-  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
-  return LVX_OK;
-}
 // The selected inverse with the wide band store, then one wavefront per queried landmark (k_landmark_cov).  ids_d (device, or null for 0 .. n - 1) and the arrays of o
 // are device addresses; flags as traj_cov_enqueue's.
 static int lm_cov_enqueue(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* ids_d, const lvx_landmark_cov& o, int* flags) {
@@ -1855,77 +1891,36 @@ static int lm_cov_enqueue(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n
         q.lmH = w.lm ? (const double*)c->d_lmH.p : nullptr;
         hipLaunchKernelGGL(k_lc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, q, head); }))) return rc;
   q.lmH = w.lm ? (const double*)c->d_lmH.p : nullptr;
-  LmCov g{q, (const double*)so.SigW, so.TB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale, (const double*)w.lmd, 1.0 / opt->radius,
-          (const int*)w.info, c->sw.test_bad_pivot ? 1 : 0, o.var_rho, o.sigma_rho, o.point, o.point_cov, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
+  LmCov g{q, sigma_view(c, w, so.SigW, so.TB + 1), (const double*)w.lmd, 1.0 / opt->radius, o.var_rho, o.sigma_rho, o.point, o.point_cov, o.window_cov, o.window_idx, o.valid, flags, flags + 1};
   const size_t lds = (size_t)(c->lm_wl + c->nbd) * 12 + 16;
   hipLaunchKernelGGL(k_landmark_cov, dim3((unsigned)n), dim3(64), lds, st, g);
   LVX_HIP(c, hipGetLastError());
   return LVX_OK;
 }
 static int lm_cov_args(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const lvx_landmark_cov* out) {
-  if (!c) return LVX_E_ARG;
-  if (!opt || !out || !out->valid || n <= 0 || !(opt->radius > 0) || opt->reserved != 0) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: n <= 0, radius <= 0, reserved != 0 or a required pointer is NULL");
-  if (n > c->L) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: n exceeds the number of landmarks");
-  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_landmark_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
-  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_landmark_covariance: the context takes part in a joint solve");
-  LVX_HIP(c, hipSetDevice(c->device));
-  return check_last_eval(c);
+  return cov_common_args(c, "lvx_landmark_covariance", opt && out && out->valid, opt ? opt->radius : 0.0, opt ? &opt->reserved : nullptr, n,
+                         c && n > c->L ? "n exceeds the number of landmarks" : nullptr, nullptr);
 }
 int lvx_landmark_covariance_d(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id_d, const lvx_landmark_cov* out_d) {
   int rc = lm_cov_args(c, opt, n, out_d);
-  if (rc) return rc;
-  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
-    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
-    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
-  }
-  c->tcov_d_unchecked = true;
-  return lm_cov_enqueue(c, opt, n, landmark_id_d, *out_d, (int*)c->d_tj[3].p + 1);
+  int* flags;
+  if (rc || (rc = cov_d_flags(c, &flags))) return rc;
+  return lm_cov_enqueue(c, opt, n, landmark_id_d, *out_d, flags);
 }
 int lvx_landmark_covariance(lvx_ctx* c, const lvx_landmark_cov_options* opt, int n, const int32_t* landmark_id, lvx_landmark_cov* out) {
   int rc = lm_cov_args(c, opt, n, out);
   if (rc) return rc;
   if (landmark_id) for (int i = 0; i < n; ++i) if (landmark_id[i] < 0 || landmark_id[i] >= c->L) return fail(c, LVX_E_ARG, "lvx_landmark_covariance: landmark id out of range");
-  hipStream_t st = c->stream;
-  // device and pinned images (lvx_trajectory_covariance's): [ids | var_rho | sigma_rho | point | point_cov | window_cov | window_idx | valid | flags (2 ints)]
   const size_t nn = (size_t)n, W2 = (size_t)LVX_LM_COV_W * LVX_LM_COV_W;
-  size_t off[9]; size_t cur = 0;
-  const size_t bytes[8] = {landmark_id ? nn * 4 : 0, out->var_rho ? nn * 8 : 0, out->sigma_rho ? nn * 8 : 0, out->point ? nn * 24 : 0, out->point_cov ? nn * 72 : 0,
-                           out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_LM_COV_W * 4 : 0, nn};
-  for (int k = 0; k < 8; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
-  off[8] = cur; cur += 16;
-  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
-  if (c->h_tcov_cap < cur) {
-    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
-    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
-    c->h_tcov_cap = cur;
-  }
-  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
-  if (landmark_id) { std::memcpy(h, landmark_id, nn * 4); LVX_HIP(c, hipMemcpyAsync(d, h, nn * 4, hipMemcpyHostToDevice, st)); }
-  LVX_HIP(c, hipMemsetAsync(d + off[8], 0, 16, st));
-  lvx_landmark_cov od;
-  od.var_rho = out->var_rho ? (double*)(d + off[1]) : nullptr; od.sigma_rho = out->sigma_rho ? (double*)(d + off[2]) : nullptr; od.point = out->point ? (double*)(d + off[3]) : nullptr;
-  od.point_cov = out->point_cov ? (double*)(d + off[4]) : nullptr; od.window_cov = out->window_cov ? (double*)(d + off[5]) : nullptr;
-  od.window_idx = out->window_idx ? (int32_t*)(d + off[6]) : nullptr; od.valid = (uint8_t*)(d + off[7]);
-  if ((rc = lm_cov_enqueue(c, opt, n, landmark_id ? (const int32_t*)d : nullptr, od, (int*)(d + off[8])))) return rc;
-  LVX_HIP(c, hipMemcpyAsync(h + off[1], d + off[1], cur - off[1], hipMemcpyDeviceToHost, st));
-  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
-  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
-  int fl[2]; std::memcpy(fl, h + off[8], 8);
-  if (fl[1]) {
-    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
-    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
-  }
-  void* dst[8] = {nullptr, out->var_rho, out->sigma_rho, out->point, out->point_cov, out->window_cov, out->window_idx, out->valid};
-  for (int k = 1; k < 8; ++k) if (dst[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
-  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
-  return LVX_OK;
+  CovStage s;
+  if ((rc = cov_stage(c, {{(void*)landmark_id, nn * 4}},
+                      {{out->var_rho, nn * 8}, {out->sigma_rho, nn * 8}, {out->point, nn * 24}, {out->point_cov, nn * 72}, {out->window_cov, nn * W2 * 8},
+                       {out->window_idx, nn * LVX_LM_COV_W * 4}, {out->valid, nn}}, &s))) return rc;
+  const lvx_landmark_cov od{(double*)s.d[1], (double*)s.d[2], (double*)s.d[3], (double*)s.d[4], (double*)s.d[5], (int32_t*)s.d[6], (uint8_t*)s.d[7]};
+  if ((rc = lm_cov_enqueue(c, opt, n, (const int32_t*)s.d[0], od, s.flags))) return rc;
+  return cov_finish(c, s);
 }
 
-int lvx_point_cov_default_options(lvx_point_cov_options* o) {
-  if (!o) return LVX_E_ARG;
-  o->radius = 1e8; o->jacobi_scaling = 1; o->reserved = 0;
-  return LVX_OK;
-}
 // The selected inverse down to the lowest band position a point's window holds (k_tc_lowest in the LiDAR frame), k_pt_hub once, then k_point_cov with a lane per
 // point.  pt_d [n][3] or xyzi_d [n][4] float, t_d, dir_d (or null) and the arrays of o are device addresses; flags as traj_cov_enqueue's, flags[1] = 2 when the window of
 // t_map is off the border.
@@ -1940,8 +1935,7 @@ static int pt_cov_enqueue(lvx_ctx* c, const lvx_point_cov_options* opt, int n, c
         hipLaunchKernelGGL(k_tc_lowest, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, state_d, c->N, c->t0, c->dt, (int)LVX_FRAME_LIDAR, n, t_d, (const int*)c->d_ord.p, head); }))) return rc;
   PtCov g{};
   g.state = state_d; g.N = c->N; g.t0 = c->t0; g.dt = c->dt; g.t_map = c->t_map; g.n = n; g.pt = pt_d; g.xyzi = xyzi_d; g.t = t_d; g.dir = dir_d;
-  g.s = PtAccess{(const int*)c->d_ord.p, (const double*)so.SigB, (const double*)w.Z, w.ldz, c->nb, c->nbd, (const double*)w.S, (const double*)w.scale};
-  g.info = (const int*)w.info; g.force_bad = c->sw.test_bad_pivot ? 1 : 0; g.hub = (PtHub*)c->d_ptcov.p;
+  g.v = sigma_view(c, w, so.SigB, SI_BD); g.hub = (PtHub*)c->d_ptcov.p;
   g.point = o.point; g.cov = o.cov; g.sigma = o.sigma; g.sigma_max = o.sigma_max; g.var_dir = o.var_dir; g.wcov = o.window_cov; g.widx = o.window_idx; g.valid = o.valid;
   g.flag = flags; g.bad = flags + 1;
   const size_t lds = (size_t)(PC_NT / 64) * 16 * PC_TS * 8;   // the wavefronts' tiles of the MFMA product
@@ -1957,24 +1951,15 @@ static int pt_cov_enqueue(lvx_ctx* c, const lvx_point_cov_options* opt, int n, c
   return LVX_OK;
 }
 static int pt_cov_args(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const void* pt, const double* t, const lvx_point_cov* out) {
-  if (!c) return LVX_E_ARG;
-  if (!opt || !pt || !t || !out || !out->valid || n <= 0 || !(opt->radius > 0) || opt->reserved != 0)
-    return fail(c, LVX_E_ARG, "lvx_map_point_covariance: n <= 0, radius <= 0, reserved != 0 or a required pointer is NULL");
-  if (!(c->last_what & LVX_EVAL_NORMAL_EQ) || !c->last_state_d) return fail(c, LVX_E_STATE, "lvx_map_point_covariance needs a preceding LVX_EVAL_NORMAL_EQ evaluation");
-  if (is_joint(c)) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: the context takes part in a joint solve");
-  if ((c->surf.n <= 0 && c->cs.n <= 0) || c->n_hub <= 0) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: no surfel / camera-surfel family has set t_map");
-  LVX_HIP(c, hipSetDevice(c->device));
-  return check_last_eval(c);
+  const bool no_hub = c && ((c->surf.n <= 0 && c->cs.n <= 0) || c->n_hub <= 0);
+  return cov_common_args(c, "lvx_map_point_covariance", opt && pt && t && out && out->valid, opt ? opt->radius : 0.0, opt ? &opt->reserved : nullptr, n,
+                         nullptr, no_hub ? "no surfel / camera-surfel family has set t_map" : nullptr);
 }
 static int pt_cov_d(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt_d, const float* xyzi_d, const double* t_d, const double* dir_d, const lvx_point_cov* out_d) {
   int rc = pt_cov_args(c, opt, n, pt_d ? (const void*)pt_d : (const void*)xyzi_d, t_d, out_d);
-  if (rc) return rc;
-  if (!c->d_tj[3].p) {   // the flag words of the _d trajectory queries (lvx_traj.hip)
-    if ((rc = dev_alloc(c, c->d_tj[3], 16))) return rc;
-    LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
-  }
-  c->tcov_d_unchecked = true;
-  return pt_cov_enqueue(c, opt, n, pt_d, xyzi_d, t_d, dir_d, *out_d, (int*)c->d_tj[3].p + 1);
+  int* flags;
+  if (rc || (rc = cov_d_flags(c, &flags))) return rc;
+  return pt_cov_enqueue(c, opt, n, pt_d, xyzi_d, t_d, dir_d, *out_d, flags);
 }
 int lvx_map_point_covariance_d(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt3_d, const double* t_d, const double* dir3_d, const lvx_point_cov* out_d) {
   return pt_cov_d(c, opt, n, pt3_d, nullptr, t_d, dir3_d, out_d);
@@ -1985,45 +1970,15 @@ int lvx_map_point_covariance_xyzi_d(lvx_ctx* c, const lvx_point_cov_options* opt
 int lvx_map_point_covariance(lvx_ctx* c, const lvx_point_cov_options* opt, int n, const double* pt_lidar3, const double* t, const double* dir3, lvx_point_cov* out) {
   int rc = pt_cov_args(c, opt, n, pt_lidar3, t, out);
   if (rc) return rc;
-  hipStream_t st = c->stream;
-  // device and pinned images (lvx_trajectory_covariance's): [points | t | dir | point | cov | sigma | sigma_max | var_dir | window_cov | window_idx | valid | flags (2 ints)]
   const size_t nn = (size_t)n, W2 = (size_t)LVX_PT_COV_W * LVX_PT_COV_W;
-  const bool vd = dir3 && out->var_dir;
-  enum { NIN = 3, NARR = 11 };
-  size_t off[NARR + 1]; size_t cur = 0;
-  const size_t bytes[NARR] = {nn * 24, nn * 8, vd ? nn * 24 : 0, out->point ? nn * 24 : 0, out->cov ? nn * 72 : 0, out->sigma ? nn * 24 : 0, out->sigma_max ? nn * 8 : 0, vd ? nn * 8 : 0,
-                              out->window_cov ? nn * W2 * 8 : 0, out->window_idx ? nn * LVX_PT_COV_W * 4 : 0, nn};
-  for (int k = 0; k < NARR; ++k) { off[k] = cur; cur += (bytes[k] + 15) & ~(size_t)15; }
-  off[NARR] = cur; cur += 16;
-  if ((rc = dev_alloc(c, c->d_tcov_io, cur))) return rc;
-  if (c->h_tcov_cap < cur) {
-    if (c->h_tcov) { (void)hipHostFree(c->h_tcov); c->h_tcov = nullptr; c->h_tcov_cap = 0; }
-    LVX_HIP(c, hipHostMalloc(&c->h_tcov, cur, hipHostMallocDefault));
-    c->h_tcov_cap = cur;
-  }
-  char* d = (char*)c->d_tcov_io.p; char* h = (char*)c->h_tcov;
-  std::memcpy(h + off[0], pt_lidar3, bytes[0]); std::memcpy(h + off[1], t, bytes[1]);
-  if (vd) std::memcpy(h + off[2], dir3, bytes[2]);
-  LVX_HIP(c, hipMemcpyAsync(d, h, off[NIN], hipMemcpyHostToDevice, st));
-  LVX_HIP(c, hipMemsetAsync(d + off[NARR], 0, 16, st));
-  auto at = [&](int k) { return bytes[k] ? (void*)(d + off[k]) : nullptr; };
-  lvx_point_cov od;
-  od.point = (double*)at(3); od.cov = (double*)at(4); od.sigma = (double*)at(5); od.sigma_max = (double*)at(6); od.var_dir = (double*)at(7); od.window_cov = (double*)at(8);
-  od.window_idx = (int32_t*)at(9); od.valid = (uint8_t*)at(10);
-  if ((rc = pt_cov_enqueue(c, opt, n, (const double*)(d + off[0]), nullptr, (const double*)(d + off[1]), vd ? (const double*)(d + off[2]) : nullptr, od, (int*)(d + off[NARR])))) return rc;
-  LVX_HIP(c, hipMemcpyAsync(h + off[NIN], d + off[NIN], cur - off[NIN], hipMemcpyDeviceToHost, st));
-  LVX_HIP(c, hipMemcpyAsync(c->pin + 48, (const double*)c->d_scal.p + 32, 16, hipMemcpyDeviceToHost, st));   // the pivot codes (SolveWork::info), for the message
-  LVX_HIP(c, hipStreamSynchronize(st));   // the one host stop
-  int fl[2]; std::memcpy(fl, h + off[NARR], 8);
-  if (fl[1] == 2) return fail(c, LVX_E_STATE, "lvx_map_point_covariance: a free scalar of the pose at t_map is a band position of the factor (its cross terms are off the pattern)");
-  if (fl[1]) {
-    int info[4]; std::memcpy(info, c->pin + 48, 16); double dv; std::memcpy(&dv, info + 2, 8);
-    return fail(c, LVX_E_NOTPD, "damped normal equations not positive definite (band pivot code " + std::to_string(info[0]) + ", first border pivot " + std::to_string(info[1]) + " value " + std::to_string(dv) + ")");
-  }
-  void* dst[NARR] = {nullptr, nullptr, nullptr, out->point, out->cov, out->sigma, out->sigma_max, out->var_dir, out->window_cov, out->window_idx, out->valid};
-  for (int k = NIN; k < NARR; ++k) if (dst[k] && bytes[k]) std::memcpy(dst[k], h + off[k], bytes[k]);
-  if (fl[0]) return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
-  return LVX_OK;
+  const bool vd = dir3 && out->var_dir;   // the directions travel only when their variances are asked for, and the reverse
+  CovStage s;
+  if ((rc = cov_stage(c, {{(void*)pt_lidar3, nn * 24}, {(void*)t, nn * 8}, {vd ? (void*)dir3 : nullptr, nn * 24}},
+                      {{out->point, nn * 24}, {out->cov, nn * 72}, {out->sigma, nn * 24}, {out->sigma_max, nn * 8}, {vd ? out->var_dir : nullptr, nn * 8}, {out->window_cov, nn * W2 * 8},
+                       {out->window_idx, nn * LVX_PT_COV_W * 4}, {out->valid, nn}}, &s))) return rc;
+  const lvx_point_cov od{(double*)s.d[3], (double*)s.d[4], (double*)s.d[5], (double*)s.d[6], (double*)s.d[7], (double*)s.d[8], (int32_t*)s.d[9], (uint8_t*)s.d[10]};
+  if ((rc = pt_cov_enqueue(c, opt, n, (const double*)s.d[0], nullptr, (const double*)s.d[1], (const double*)s.d[2], od, s.flags))) return rc;
+  return cov_finish(c, s, "lvx_map_point_covariance: a free scalar of the pose at t_map is a band position of the factor (its cross terms are off the pattern)");
 }
 
 // The covariance of the JOINT problem: lvx_solve_step_shared's front half (the diagonal collective puts the joint diagonal at the shared slots and withholds their

@@ -177,6 +177,15 @@ int traj_check_d(lvx_ctx* c) {
   return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
 }
 
+// flag words (d_tj[3]), created on first use: [0] the host-array calls (cleared per call), [1 .. 2] the _d calls (kept until lvx_synchronize looks)
+int traj_flag_words(lvx_ctx* c) {
+  if (c->d_tj[3].p) return LVX_OK;
+  int rc = dev_alloc(c, c->d_tj[3], 16);
+  if (rc) return rc;
+  LVX_HIP(c, hipMemsetAsync(c->d_tj[3].p, 0, 16, c->stream));
+  return LVX_OK;
+}
+
 }  // namespace lvx
 
 using namespace lvx;
@@ -185,14 +194,11 @@ namespace {
 
 enum { TJ_STATE = 0, TJ_IN = 1, TJ_OUT = 2, TJ_FLAG = 3, TJ_WORK = 4 };
 
-// flag words: [0] the host-array calls (cleared per call), [1] the _d calls (kept until lvx_synchronize looks); pinned mirror of the small results
+// the flag words and the pinned mirror of the small results
 int traj_prepare(lvx_ctx* c) {
   LVX_HIP(c, hipSetDevice(c->device));
-  if (!c->d_tj[TJ_FLAG].p) {
-    int rc = dev_alloc(c, c->d_tj[TJ_FLAG], 16);
-    if (rc) return rc;
-    LVX_HIP(c, hipMemsetAsync(c->d_tj[TJ_FLAG].p, 0, 16, c->stream));
-  }
+  int rc = traj_flag_words(c);
+  if (rc) return rc;
   if (!c->h_tj) { LVX_HIP(c, hipHostMalloc((void**)&c->h_tj, 32 * 8, hipHostMallocDefault)); std::memset(c->h_tj, 0, 32 * 8); }
   return LVX_OK;
 }

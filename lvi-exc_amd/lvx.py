@@ -485,11 +485,22 @@ class Context:
                     info_eig=np.array(r.info_eig[:nf]), info_vec=np.array(r.info_vec).reshape(N_CALIB, N_CALIB)[:nf, :nf].copy(), scale=np.array(r.scale),
                     radius=r.radius, sweeps=r.sweeps, n_hub_eliminated=r.n_hub_eliminated)
 
-    def _traj_cov_options(self, radius, jacobi_scaling):
-        opt = TrajCovOptions()
-        self._l.lvx_traj_cov_default_options(C.byref(opt))
+    @staticmethod
+    def _cov_options(struct_cls, default_fn, radius, jacobi_scaling):
+        opt = struct_cls()
+        default_fn(C.byref(opt))
         opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
         return opt
+
+    def _cov_result(self, rc, out, valid):
+        """The host forms' tail: valid as bool into the dict; E_NONUNIT_QUAT carries the dict as `partial`; any other failure raises as usual."""
+        out["valid"] = valid.astype(bool)
+        if rc == E_NONUNIT_QUAT:
+            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
+            e.partial = out
+            raise e
+        self._ck(rc)
+        return out
 
     def trajectory_covariance(self, t, frame=0, radius=1e8, jacobi_scaling=True, window=False):
         """Covariance of the pose at times t in `frame` (FRAME_TRAJECTORY / FRAME_LIDAR / FRAME_CAMERA) in the DAMPED system of the last evaluate(normal_eq=True), at the
@@ -505,28 +516,16 @@ class Context:
         valid = np.zeros(n, np.uint8)
         r = TrajCov(out["cov"].ctypes.data, out["sigma"].ctypes.data, out["window_cov"].ctypes.data if window else None, out["window_idx"].ctypes.data if window else None,
                     valid.ctypes.data)
-        opt = self._traj_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(TrajCovOptions, self._l.lvx_traj_cov_default_options, radius, jacobi_scaling)
         rc = self._l.lvx_trajectory_covariance(self._h, C.byref(opt), C.c_int(frame), C.c_int(n), _p(t), C.byref(r))
-        out["valid"] = valid.astype(bool)
-        if rc == E_NONUNIT_QUAT:
-            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
-            e.partial = out
-            raise e
-        self._ck(rc)
-        return out
+        return self._cov_result(rc, out, valid)
 
     def trajectory_covariance_d(self, t_d_ptr, n, out_d_ptrs, valid_d_ptr, frame=0, radius=1e8, jacobi_scaling=True):
         """lvx_trajectory_covariance_d: device addresses; out_d_ptrs maps "cov" / "sigma" / "window_cov" / "window_idx" to addresses (absent: not computed).  Only
         enqueues; synchronize() reports a lost pivot or a non-unit quaternion."""
         r = TrajCov(*[out_d_ptrs.get(f) for f in ("cov", "sigma", "window_cov", "window_idx")], valid_d_ptr)
-        opt = self._traj_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(TrajCovOptions, self._l.lvx_traj_cov_default_options, radius, jacobi_scaling)
         self._ck(self._l.lvx_trajectory_covariance_d(self._h, C.byref(opt), C.c_int(frame), C.c_int(n), C.c_void_p(t_d_ptr), C.byref(r)))
-
-    def _landmark_cov_options(self, radius, jacobi_scaling):
-        opt = LandmarkCovOptions()
-        self._l.lvx_landmark_cov_default_options(C.byref(opt))
-        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
-        return opt
 
     def landmark_covariance(self, radius=1e8, jacobi_scaling=True, ids=None, window=True):
         """Uncertainty of the landmarks `ids` (default: all, in order) in the DAMPED system of the last evaluate(normal_eq=True), at the state of that evaluation
@@ -543,28 +542,16 @@ class Context:
         valid = np.zeros(n, np.uint8)
         r = LandmarkCov(out["var_rho"].ctypes.data, out["sigma_rho"].ctypes.data, out["point"].ctypes.data, out["point_cov"].ctypes.data,
                         out["window_cov"].ctypes.data if window else None, out["window_idx"].ctypes.data if window else None, valid.ctypes.data)
-        opt = self._landmark_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(LandmarkCovOptions, self._l.lvx_landmark_cov_default_options, radius, jacobi_scaling)
         rc = self._l.lvx_landmark_covariance(self._h, C.byref(opt), C.c_int(n), _p(ids) if ids is not None else None, C.byref(r))
-        out["valid"] = valid.astype(bool)
-        if rc == E_NONUNIT_QUAT:
-            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
-            e.partial = out
-            raise e
-        self._ck(rc)
-        return out
+        return self._cov_result(rc, out, valid)
 
     def landmark_covariance_d(self, ids_d_ptr, n, out_d_ptrs, valid_d_ptr, radius=1e8, jacobi_scaling=True):
         """lvx_landmark_covariance_d: device addresses (ids_d_ptr 0 / None: landmarks 0 .. n - 1); out_d_ptrs maps "var_rho" / "sigma_rho" / "point" / "point_cov" /
         "window_cov" / "window_idx" to addresses (absent: not computed).  Only enqueues; synchronize() reports a lost pivot or a non-unit quaternion."""
         r = LandmarkCov(*[out_d_ptrs.get(f) for f in ("var_rho", "sigma_rho", "point", "point_cov", "window_cov", "window_idx")], valid_d_ptr)
-        opt = self._landmark_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(LandmarkCovOptions, self._l.lvx_landmark_cov_default_options, radius, jacobi_scaling)
         self._ck(self._l.lvx_landmark_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(ids_d_ptr) if ids_d_ptr else None, C.byref(r)))
-
-    def _point_cov_options(self, radius, jacobi_scaling):
-        opt = PointCovOptions()
-        self._l.lvx_point_cov_default_options(C.byref(opt))
-        opt.radius, opt.jacobi_scaling = float(radius), 1 if jacobi_scaling else 0
-        return opt
 
     def map_point_covariance(self, points, t, dirs=None, radius=1e8, jacobi_scaling=True, window=False):
         """Uncertainty of LiDAR points [n, 3] measured at times t [n] once carried into the map frame (the LiDAR frame at t_map), in the DAMPED system of the last
@@ -588,22 +575,16 @@ class Context:
             out["window_idx"] = np.full((n, PT_COV_W), -1, np.int32)
         valid = np.zeros(n, np.uint8)
         r = PointCov(*[out[k].ctypes.data if k in out else None for k in ("point", "cov", "sigma", "sigma_max", "var_dir", "window_cov", "window_idx")], valid.ctypes.data)
-        opt = self._point_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(PointCovOptions, self._l.lvx_point_cov_default_options, radius, jacobi_scaling)
         rc = self._l.lvx_map_point_covariance(self._h, C.byref(opt), C.c_int(n), _p(points), _p(t), _p(dirs), C.byref(r))
-        out["valid"] = valid.astype(bool)
-        if rc == E_NONUNIT_QUAT:
-            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
-            e.partial = out
-            raise e
-        self._ck(rc)
-        return out
+        return self._cov_result(rc, out, valid)
 
     def map_point_covariance_d(self, points_d_ptr, t_d_ptr, n, out_d_ptrs, valid_d_ptr, dirs_d_ptr=None, xyzi=False, radius=1e8, jacobi_scaling=True):
         """lvx_map_point_covariance_d (xyzi=True: lvx_map_point_covariance_xyzi_d, points as [n, 4] float32 in the scan buffers' layout, no directions): device
         addresses; out_d_ptrs maps "point" / "cov" / "sigma" / "sigma_max" / "var_dir" / "window_cov" / "window_idx" to addresses (absent: not computed).  Only
         enqueues; synchronize() reports a lost pivot, a t_map window off the border or a non-unit quaternion."""
         r = PointCov(*[out_d_ptrs.get(f) for f in ("point", "cov", "sigma", "sigma_max", "var_dir", "window_cov", "window_idx")], valid_d_ptr)
-        opt = self._point_cov_options(radius, jacobi_scaling)
+        opt = self._cov_options(PointCovOptions, self._l.lvx_point_cov_default_options, radius, jacobi_scaling)
         if xyzi:
             self._ck(self._l.lvx_map_point_covariance_xyzi_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(points_d_ptr), C.c_void_p(t_d_ptr), C.byref(r)))
         else:

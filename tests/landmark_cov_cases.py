@@ -70,7 +70,7 @@ def selinv_wide(Lb, Z, S, nb, bw, nbd, lowest=0):
 
 
 def sigma_at(pa, pb, sigw, zb, cc):
-    """lc_sigma: the scaled inverse between two positions (>= 0 band, < 0 border slot -1 - o)"""
+    """lvx_selinv.h's sigma_at over the wide band store: the scaled inverse between two positions (>= 0 band, < 0 border slot -1 - o)"""
     if pa >= 0 and pb >= 0:
         lo, d = min(pa, pb), abs(pa - pb)
         return sigw[lo, d] if d < sigw.shape[1] else 0.0

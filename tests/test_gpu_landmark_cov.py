@@ -282,11 +282,11 @@ def test_errors_are_codes_and_a_lost_pivot_writes_nothing():
         assert e.value.code == lvx.E_ARG, kw
     var, valid = np.full(L, 7.0), np.full(L, 7, np.uint8)
     rec = lvx.LandmarkCov(var.ctypes.data, None, None, None, None, None, valid.ctypes.data)
-    opt = g._landmark_cov_options(1e8, True)
+    opt = g._cov_options(lvx.LandmarkCovOptions, g._l.lvx_landmark_cov_default_options, 1e8, True)
     assert g._l.lvx_landmark_covariance(None, C.byref(opt), C.c_int(L), None, C.byref(rec)) == lvx.E_ARG
     assert _raw(g, None, L, None, rec) == lvx.E_ARG and _raw(g, opt, L, None, None) == lvx.E_ARG
     assert _raw(g, opt, L, None, lvx.LandmarkCov(var.ctypes.data, None, None, None, None, None, None)) == lvx.E_ARG
-    bad = g._landmark_cov_options(1e8, True); bad.reserved = 1
+    bad = g._cov_options(lvx.LandmarkCovOptions, g._l.lvx_landmark_cov_default_options, 1e8, True); bad.reserved = 1
     assert _raw(g, bad, L, None, rec) == lvx.E_ARG
     assert (var == 7.0).all() and (valid == 7).all()
     seen = []

@@ -314,11 +314,11 @@ def test_errors_are_codes_and_a_failed_call_writes_nothing():
     assert e.value.code == lvx.E_ARG
     n = len(t)
     cov, valid = np.full((n, 9), 7.0), np.full(n, 7, np.uint8)
-    opt = g._point_cov_options(1e8, True)
+    opt = g._cov_options(lvx.PointCovOptions, g._l.lvx_point_cov_default_options, 1e8, True)
     args = lambda rec, o=opt, pp=pts, tt=t: (g._h, C.byref(o), C.c_int(n), pp.ctypes.data_as(C.c_void_p) if pp is not None else None,
                                              tt.ctypes.data_as(C.c_void_p) if tt is not None else None, None, C.byref(rec))
     rec = lvx.PointCov(None, cov.ctypes.data, None, None, None, None, None, valid.ctypes.data)
-    bad_opt = g._point_cov_options(1e8, True); bad_opt.reserved = 1
+    bad_opt = g._cov_options(lvx.PointCovOptions, g._l.lvx_point_cov_default_options, 1e8, True); bad_opt.reserved = 1
     assert g._l.lvx_map_point_covariance(*args(rec, o=bad_opt)) == lvx.E_ARG
     assert g._l.lvx_map_point_covariance(*args(rec, pp=None)) == lvx.E_ARG and g._l.lvx_map_point_covariance(*args(rec, tt=None)) == lvx.E_ARG
     assert g._l.lvx_map_point_covariance(*args(lvx.PointCov(None, cov.ctypes.data, None, None, None, None, None, None))) == lvx.E_ARG
@@ -374,7 +374,7 @@ def test_no_hub_and_a_hub_window_in_the_band_are_state_errors():
     n = 3
     cov, valid = np.full((n, 9), 7.0), np.full(n, 7, np.uint8)
     rec = lvx.PointCov(None, cov.ctypes.data, None, None, None, None, None, valid.ctypes.data)
-    opt = g._point_cov_options(1e8, True)
+    opt = g._cov_options(lvx.PointCovOptions, g._l.lvx_point_cov_default_options, 1e8, True)
     rc = g._l.lvx_map_point_covariance(g._h, C.byref(opt), C.c_int(n), pts.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), None, C.byref(rec))
     assert rc == lvx.E_STATE and (cov == 7.0).all() and (valid == 7).all()
     dev = torch.device("cuda:0")

@@ -235,7 +235,7 @@ def test_errors_are_codes_and_a_lost_pivot_writes_nothing():
     n = len(t)
     cov, sigma, valid = np.full((n, 36), 7.0), np.full((n, 6), 7.0), np.full(n, 7, np.uint8)
     rec = lvx.TrajCov(cov.ctypes.data, sigma.ctypes.data, None, None, valid.ctypes.data)
-    opt = g._traj_cov_options(1e8, True)
+    opt = g._cov_options(lvx.TrajCovOptions, g._l.lvx_traj_cov_default_options, 1e8, True)
     import ctypes as C
     rc = g._l.lvx_trajectory_covariance(g._h, C.byref(opt), C.c_int(0), C.c_int(n), t.ctypes.data_as(C.c_void_p), C.byref(rec))
     assert rc == lvx.E_NOTPD and (cov == 7.0).all() and (sigma == 7.0).all() and (valid == 7).all()
