@@ -275,7 +275,9 @@ int lvx_synchronize(lvx_ctx* ctx);
 #define LVX_KERNEL_LIDAR_POS 17     /* the per-segment kernel over the LiDAR-pose blocks: beyond LVX_NUM_KERNELS, read with lvx_get_kernel_ms_ext */
 #define LVX_KERNEL_POSE_COV 18      /* k_pose_cov of lvx_trajectory_covariance (the selected inverse in front of it is not part of the record) */
 #define LVX_KERNEL_POINT_COV 19     /* k_pt_hub + k_point_cov of lvx_map_point_covariance (likewise) */
-#define LVX_NUM_KERNELS_EXT 20
+#define LVX_KERNEL_PROJ_HUB 20      /* k_proj_poses + k_proj_hub of lvx_projection_covariance (likewise) */
+#define LVX_KERNEL_PROJ_COV 21      /* k_proj_cov of lvx_projection_covariance */
+#define LVX_NUM_KERNELS_EXT 22
 /* enable: 0 off | 1 every launch | 2 + k: only the launches of kernel k (e.g. 2 + LVX_FAM_SURFEL: the dominant kernel — two event
  * records per pass instead of ~20, which cost ~5 % of a config-4 pass).  While profiling is on, passes are issued launch by launch (no graph replay). */
 int lvx_set_profiling(lvx_ctx* ctx, int enable);
@@ -456,6 +458,56 @@ int lvx_map_point_covariance(lvx_ctx* ctx, const lvx_point_cov_options* opt, int
 int lvx_map_point_covariance_d(lvx_ctx* ctx, const lvx_point_cov_options* opt, int n, const double* pt3_d, const double* t_d, const double* dir3_d, const lvx_point_cov* out_d);
 /* the same for points in the scan buffers' layout: xyzi4_d [n][4] float (x, y, z, intensity), 16-byte aligned; no directions */
 int lvx_map_point_covariance_xyzi_d(lvx_ctx* ctx, const lvx_point_cov_options* opt, int n, const float* xyzi4_d, const double* t_d, const lvx_point_cov* out_d);
+
+/* PIXEL uncertainty of LiDAR map points in the images, in the same damped system: how many pixels the uncertainty of the trajectory and of both sensors' extrinsics
+ * and time offsets leaves where a map point lands in an image.  A map point x is given in the LiDAR frame at the context's t_map, as lvx_render_map_d takes it; its
+ * pixel in the image taken at image_t is RenderMap's chain (LIinitializer::RenderMap, lvi-exc_amd/csrc/lvx_render.h):
+ *   pt_G = R_L0 x + p_L0          (R_L0, p_L0): LVX_FRAME_LIDAR pose at t_map (+ tau_L)
+ *   pt_C = R_C^T (pt_G - p_C)     (R_C, p_C):   LVX_FRAME_CAMERA pose at image_t (+ tau_C)
+ *   uv   = radtan projection of pt_C (k1, k2, k3, p1, p2; no rolling-shutter row time, as RenderMap)
+ * The map point is TAKEN AS GIVEN: its own uncertainty (lvx_map_point_covariance) correlates with the image pose off the factor's pattern and is not part of this
+ * call.  What is propagated is the joint covariance of the two poses, cross terms included (band window x hub knots x both sensors' scalars: all on the pattern).
+ *   window_idx[k][0..23]: the four knots of the camera pose at image_t + tau_C, [24..30]: the camera's theta (3), p (3), tau (1), [31..54]: the four knots of the LiDAR
+ *     pose at t_map + tau_L, [55..61]: the LiDAR's theta, p, tau; -1 constant.  An image whose window shares knots with the window of t_map repeats indices: the
+ *     window is gathered by index, so that is exact.
+ *   window_cov[k] = Sigma over those 62 scalars (zero rows / columns at -1): rows 0..30 are lvx_trajectory_covariance's LVX_FRAME_CAMERA window at image_t, rows 31..61
+ *     its LVX_FRAME_LIDAR window at t_map, bit for bit.
+ *   pose_cov[k] = J12 window_cov[k] J12^T (12 x 12) over (camera dp, dphi; LiDAR dp, dphi) in lvx_trajectory_covariance's pose-error convention (world frame).
+ *   cov[i] = A pose_cov A^T (2 x 2, px^2), A (2 x 12) the derivative of uv by those pose errors for this point (lvi-exc_amd/csrc/lvx_projcov.h); sigma = sqrt of its
+ *     diagonal; sigma_max = sqrt of its largest eigenvalue.  For an image near t_map the pose-level terms cancel (the rig's relative pose is what is left).
+ * Several images: lvx_render_map_d's rule and its very decisions (the same functions): a point's record refers to the lowest-index image whose pose is valid and in
+ * which the point is in depth range [z_min, z_max] and inside the image.  status 0: skipped (a NaN coordinate, out of depth range in every valid image), 1: in depth
+ * range somewhere but outside every image, 2: projected; for 0 and 1 the numeric outputs are zero and image = -1.
+ * Contract of lvx_map_point_covariance word for word: the last LVX_EVAL_NORMAL_EQ evaluation at its state, its error word read first, copies only, one host stop in the
+ * host form, always the sequential factor, all sums in a fixed order (a point's record is the same bits alone, in any batch and at any position), LVX_E_STATE without
+ * an evaluation, on a context of a joint solve, without a camera, without t_map, or when a free knot scalar of the t_map window stands in the band; LVX_E_NOTPD writes
+ * nothing; LVX_E_NONUNIT_QUAT returns with the rest filled.  LVX_E_ARG: NULL context / options / points (host form) / image_t / img / img->valid / out / out->status,
+ * n <= 0, n_images outside 1 .. LVX_RENDER_MAX_IMAGES, radius <= 0, reserved != 0, z_min > z_max, and the LDS limits of lvx_trajectory_covariance. */
+#define LVX_PROJ_COV_W 62
+typedef struct lvx_proj_cov_options { double radius; int32_t jacobi_scaling; int32_t reserved; double z_min, z_max; } lvx_proj_cov_options; /* 1e8, 1, 0, 0.1, 15 */
+typedef struct lvx_proj_cov_images {   /* per image; any array but valid may be NULL */
+  double* pose_cov;    /* [n_images][144] */
+  double* window_cov;  /* [n_images][62 * 62] */
+  int32_t* window_idx; /* [n_images][62] */
+  int32_t* valid;      /* [n_images]; 0: image_t outside the spline (not an error), zeros, indices -1 */
+} lvx_proj_cov_images;
+typedef struct lvx_proj_cov {          /* per point; any array but status may be NULL */
+  double* uv;          /* [n][2] */
+  double* cov;         /* [n][4] row-major, px^2 */
+  double* sigma;       /* [n][2] sqrt of the diagonal (a diagonal entry below zero by rounding counts as zero) */
+  double* sigma_max;   /* [n] sqrt of the largest eigenvalue, px */
+  int32_t* image;      /* [n] */
+  uint8_t* status;     /* [n] */
+} lvx_proj_cov;
+int lvx_proj_cov_default_options(lvx_proj_cov_options* opt);
+/* map_xyzi4 [n][4] float (x, y, z, intensity), image_t [n_images] */
+int lvx_projection_covariance(lvx_ctx* ctx, const lvx_proj_cov_options* opt, int n, const float* map_xyzi4, int n_images, const double* image_t, const lvx_proj_cov_images* img,
+                              const lvx_proj_cov* out);
+/* DEVICE addresses (map_xyzi4_d 16-byte aligned); only enqueues on the context's stream.  A lost pivot or a t_map window off the border (nothing written) or a non-unit
+ * quaternion is reported by the next lvx_synchronize.  map_xyzi4_d == NULL: the de-skewed scans of the last data association, as lvx_render_map_d (n is ignored;
+ * LVX_E_STATE before any association). */
+int lvx_projection_covariance_d(lvx_ctx* ctx, const lvx_proj_cov_options* opt, int n, const float* map_xyzi4_d, int n_images, const double* image_t_d,
+                                const lvx_proj_cov_images* img_d, const lvx_proj_cov* out_d);
 
 /* x (+) delta with ceres::EigenQuaternionParameterization::Plus on quaternion blocks */
 int lvx_plus(lvx_ctx* ctx, const double* state, const double* delta, double* state_out);

@@ -123,7 +123,7 @@ void lvx_destroy(lvx_ctx* c) {
   handoff_destroy(c);
   traj_destroy(c);
   rotinit_destroy(c);
-  for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv, &c->d_ccov, &c->d_tcov, &c->d_cov_io, &c->d_lcov, &c->d_ptcov}) if (b->p) (void)hipFree(b->p);
+  for (DevBuf* b : {&c->d_bcrD, &c->d_bcrG, &c->d_bcrInfo, &c->d_Y2, &c->d_gram, &c->d_bcrLinv, &c->d_ccov, &c->d_tcov, &c->d_cov_io, &c->d_lcov, &c->d_ptcov, &c->d_projcov}) if (b->p) (void)hipFree(b->p);
   if (c->h_cov) (void)hipHostFree(c->h_cov);
   for (auto& e : c->graphs) (void)hipGraphExecDestroy((hipGraphExec_t)e.exec);
   for (auto e : c->ev_pool) (void)hipEventDestroy(e);

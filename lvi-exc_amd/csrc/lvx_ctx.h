@@ -163,6 +163,7 @@ struct lvx_ctx {
   lvx::DevBuf d_cov_io; void* h_cov = nullptr; size_t h_cov_cap = 0;   // the staging the host forms of the three covariance queries share (cov_stage): [inputs | outputs | flag words] and its pinned mirror
   lvx::DevBuf d_lcov;         // lvx_landmark_covariance: the wide band store of the selected inverse, SigW [nb][TB + 1]
   lvx::DevBuf d_ptcov;        // lvx_map_point_covariance: the record k_pt_hub leaves for k_point_cov (lvx::PtHub)
+  lvx::DevBuf d_projcov;      // lvx_projection_covariance: the table k_proj_poses and k_proj_hub leave for k_proj_cov (lvx::ProjTable)
   lvx::DevBuf d_bcrD, d_bcrG, d_bcrInfo, d_Y2, d_gram, d_bcrLinv; bool bcr_linv = false;   // d_bcrLinv: inverses of the factors' 16 x 16 diagonal triangles (k_potrf_batched -> k_trsm_reg)
   void* blas = nullptr;
   int bcr_b = 0, bcr_nblk = 0, bcr_nreal = 0;
@@ -281,6 +282,10 @@ int handoff_fetch_ids(lvx_ctx* c);   // surf.id0 of a device-origin family, fetc
 void traj_destroy(lvx_ctx* c);    // lvx_traj.hip
 void rotinit_destroy(lvx_ctx* c); // lvx_rotinit.hip
 int traj_check_d(lvx_ctx* c);      // lvx_traj.hip: the non-unit-quaternion flag of the _d trajectory queries (lvx_synchronize)
+// lvx_render.hip (built without FP contraction, as k_render_map): the two launches of lvx_projection_covariance around k_proj_hub (lvx_solver.hip).  tab: lvx::ProjTable
+int proj_poses_enqueue(lvx_ctx* c, const double* state_d, double t_map, int n_images, const double* image_t_d, void* tab);
+int proj_cov_enqueue(lvx_ctx* c, long long n, const float* xyzi4_d, const void* tab, double z_min, double z_max, double* uv, double* cov, double* sigma, double* sigma_max, int32_t* image,
+                     uint8_t* status);
 int traj_flag_words(lvx_ctx* c);   // lvx_traj.hip: creates the flag words d_tj[3] of the trajectory queries on first use (the _d covariance queries of lvx_solver.hip share them)
 // leaves + separators elimination (lvx_nd.h): nd_plan decides from the column profile whether it applies (nd_active afterwards) and sizes its buffers
 int nd_plan(lvx_ctx* c, int nrhs);

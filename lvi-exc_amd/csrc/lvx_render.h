@@ -58,17 +58,28 @@ LVX_HD v3 render_to_camera(const float xyz[3], const RenderPose& L0, const Rende
 
 // One map point in one image (:749-793).  rec must be all zero on entry of the FIRST image and is only ever written with the point's xyz / colour, so calling this for
 // image after image until it returns RENDER_COLORED leaves the record of the lowest-index image that colours the point.
+// The decisions of one map point in one image (:752-784), shared by render_point and by lvx_projection_covariance's chain (lvx_projcov.h: proj_point_images), so that
+// the two cannot drift apart: RENDER_SKIPPED (a NaN coordinate, out of depth range; nothing is written), RENDER_OUTSIDE (pt_C and, when the projection is finite, uv
+// are written) or RENDER_COLORED (pt_C, uv and the pixel iu, iv).
+LVX_HD int render_point_pixel(const float xyz[3], const RenderPose& L0, const RenderPose& C, const lvx_pinhole& cam, double z_min, double z_max, v3* pt_C, double uv[2], int* iu,
+                              int* iv) {
+  if (xyz[0] != xyz[0] || xyz[1] != xyz[1] || xyz[2] != xyz[2]) return RENDER_SKIPPED;   // pcl_isnan (:752)
+  const v3 pc = render_to_camera(xyz, L0, C);
+  if (pc.z < z_min || pc.z > z_max) return RENDER_SKIPPED;   // :757
+  *pt_C = pc;
+  render_project(cam, pc, uv);
+  if (!render_trunc(uv[0], iu) || !render_trunc(uv[1], iv)) return RENDER_OUTSIDE;
+  if (*iu < 0 || *iv < 0 || *iu > cam.cols - 1 || *iv > cam.rows - 1) return RENDER_OUTSIDE;   // :781-784: on int(uv), so uv in (-1, 0) truncates to 0 and is INSIDE
+  return RENDER_COLORED;
+}
+
 LVX_HD int render_point(const float xyz[3], const RenderPose& L0, const RenderPose& C, const lvx_pinhole& cam, const uint8_t* image, int pitch, double z_min, double z_max,
                         lvx_point_xyzrgb* rec) {
-  if (xyz[0] != xyz[0] || xyz[1] != xyz[1] || xyz[2] != xyz[2]) return RENDER_SKIPPED;   // pcl_isnan (:752)
-  const v3 pt_C = render_to_camera(xyz, L0, C);
-  if (pt_C.z < z_min || pt_C.z > z_max) return RENDER_SKIPPED;   // :757
+  v3 pt_C; double uv[2]; int iu = 0, iv = 0;
+  const int s = render_point_pixel(xyz, L0, C, cam, z_min, z_max, &pt_C, uv, &iu, &iv);
+  if (s == RENDER_SKIPPED) return s;
   rec->x = xyz[0]; rec->y = xyz[1]; rec->z = xyz[2];             // :759-762
-  double uv[2];
-  render_project(cam, pt_C, uv);
-  int iu, iv;
-  if (!render_trunc(uv[0], &iu) || !render_trunc(uv[1], &iv)) return RENDER_OUTSIDE;
-  if (iu < 0 || iv < 0 || iu > cam.cols - 1 || iv > cam.rows - 1) return RENDER_OUTSIDE;   // :781-784: on int(uv), so uv in (-1, 0) truncates to 0 and is INSIDE
+  if (s == RENDER_OUTSIDE) return s;
   const uint8_t g = image[(size_t)iv * (size_t)pitch + (size_t)iu];                        // img.at<u_char>(int(uv[1]), int(uv[0])) (:785)
   rec->b = g; rec->g = g; rec->r = g; rec->a = 255;
   return RENDER_COLORED;

@@ -9,6 +9,7 @@
 
 #include "lvx_ctx.h"
 #include "lvx_pose.h"
+#include "lvx_projcov.h"
 #include "lvx_render.h"
 
 namespace lvx {
@@ -110,6 +111,58 @@ __global__ __launch_bounds__(256) void k_overlay(const double* state, int N, dou
   if (px >= 0) mask[(size_t)blockIdx.y * (size_t)cam.rows * (size_t)cam.cols + (size_t)px] = 1;
 }
 
+
+// lvx_projection_covariance, the launches around k_proj_hub (lvx_selinv.h).  They stand here because this translation unit is built without FP contraction: the
+// poses are k_render_poses' bits and uv, the depth test and the bounds test round as k_render_map's, so a point's status IS lvx_render_map_d's decision.
+// k_proj_poses: lane i < n_images the camera pose at image_t[i], lane n_images the LiDAR pose at t_map.  One workgroup of 64.
+static_assert(sizeof(ProjTable) % 8 == 0 && sizeof(ProjImage) % 8 == 0 && offsetof(ProjTable, img) % 8 == 0, "table layout");
+__global__ __launch_bounds__(64) void k_proj_poses(const double* state, int N, double t0, double dt, double t_map, int n_images, const double* __restrict__ image_t, ProjTable* tab) {
+  const int i = threadIdx.x;
+  quat q; v3 p;
+  if (i < n_images) {
+    const bool ok = camera_pose_dev(state, N, t0, dt, image_t[i], &q, &p);
+    tab->img[i].valid = ok ? 1 : 0; tab->img[i].pad = 0;
+    if (ok) tab->img[i].C = render_pose(q, p);
+  } else if (i == n_images) {
+    const bool ok = lidar_pose_dev(state, N, t0, dt, t_map, &q, &p);
+    tab->map_valid = ok ? 1 : 0; tab->n_images = n_images; tab->status = 0; tab->pad = 0;
+    if (ok) tab->L0 = render_pose(q, p);
+  }
+}
+// A lane per point, 256 per workgroup, grid-stride.  The table (the LiDAR pose and per image the camera pose and the 78 entries of pose_cov: 112 + 728 n_images
+// bytes) is staged in LDS once per workgroup; neighbouring lanes almost always stop at the same image, so its reads are broadcasts.  Per point one 16-byte load and
+// 77 bytes of plain vector stores (uv 16, cov 32, sigma 16, sigma_max 8, image 4: 76, and the status byte), each array only where it was asked for.  A failed call (status 1 / 2 of
+// k_proj_hub) writes nothing.
+#define LVX_PROJ_BLOCK 256
+struct ProjOut { double* uv; double* cov; double* sigma; double* sigma_max; int32_t* image; uint8_t* status; };
+__global__ __launch_bounds__(LVX_PROJ_BLOCK) void k_proj_cov(const float4* __restrict__ pts, long long n, const ProjTable* __restrict__ tab_g, lvx_pinhole cam, double z_min, double z_max, ProjOut o) {
+  __shared__ ProjTable tab;
+  const int st = tab_g->status;
+  if (st == 1 || st == 2) return;
+  const int nw = (int)((offsetof(ProjTable, img) + (size_t)tab_g->n_images * sizeof(ProjImage)) / 8);
+  for (int e = threadIdx.x; e < nw; e += LVX_PROJ_BLOCK) ((double*)&tab)[e] = ((const double*)tab_g)[e];
+  __syncthreads();
+  const long long stride = (long long)gridDim.x * LVX_PROJ_BLOCK;
+  for (long long i = (long long)blockIdx.x * LVX_PROJ_BLOCK + threadIdx.x; i < n; i += stride) {
+    const float4 p = pts[i];
+    const float xyz[3] = {p.x, p.y, p.z};
+    ProjRecord r;
+    proj_point_images(xyz, tab, cam, z_min, z_max, &r);
+    if (o.uv) { o.uv[2 * i] = r.uv[0]; o.uv[2 * i + 1] = r.uv[1]; }   // (8-byte stores: the caller's arrays need no more than a double's alignment)
+    if (o.cov) { o.cov[4 * i] = r.cov[0]; o.cov[4 * i + 1] = r.cov[1]; o.cov[4 * i + 2] = r.cov[2]; o.cov[4 * i + 3] = r.cov[3]; }
+    if (o.sigma) { o.sigma[2 * i] = r.sigma[0]; o.sigma[2 * i + 1] = r.sigma[1]; }
+    if (o.sigma_max) o.sigma_max[i] = r.sigma_max;
+    if (o.image) o.image[i] = r.image;
+    o.status[i] = (uint8_t)r.status;
+  }
+}
+
+int proj_poses_enqueue(lvx_ctx* c, const double* state_d, double t_map, int n_images, const double* image_t_d, void* tab) {
+  hipLaunchKernelGGL(k_proj_poses, dim3(1), dim3(64), 0, c->stream, state_d, c->N, c->t0, c->dt, t_map, n_images, image_t_d, (ProjTable*)tab);
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+
 }  // namespace lvx
 
 using namespace lvx;
@@ -159,6 +212,19 @@ int render_run(lvx_ctx* c, const double* state, double map_time, long long n, co
   *n_colored = (int64_t)back.count;
   return LVX_OK;
 }
+
+}  // namespace
+
+int lvx::proj_cov_enqueue(lvx_ctx* c, long long n, const float* xyzi4_d, const void* tab, double z_min, double z_max, double* uv, double* cov, double* sigma, double* sigma_max,
+                          int32_t* image, uint8_t* status) {
+  const long long blocks = std::min<long long>((n + LVX_PROJ_BLOCK - 1) / LVX_PROJ_BLOCK, (long long)c->n_cu * 8);   // the loop takes the rest, the table is staged once per workgroup
+  hipLaunchKernelGGL(k_proj_cov, dim3((unsigned)blocks), dim3(LVX_PROJ_BLOCK), 0, c->stream, (const float4*)xyzi4_d, n, (const ProjTable*)tab, pinhole_of(c->cam), z_min, z_max,
+                     ProjOut{uv, cov, sigma, sigma_max, image, status});
+  LVX_HIP(c, hipGetLastError());
+  return LVX_OK;
+}
+
+namespace {
 
 int render_args(lvx_ctx* c, const double* state, int n, int n_images, const uint8_t* images, int pitch, const double* image_t, const void* out, const int32_t* image_valid, const int64_t* n_colored) {
   if (!c) return LVX_E_ARG;

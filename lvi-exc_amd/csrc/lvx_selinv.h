@@ -1,7 +1,8 @@
 // lvx_selinv.h — selected inverse of the damped LM system from its sequential factor, and the three queries that read it.  In file order: the selected inverse
 // (k_border_inv, k_band_selinv); what the queries share (SigmaView and its accessors, the window of a pose's scalars, J W J^T); then what each adds — pose covariances
 // (lvx_trajectory_covariance: nothing but the pose Jacobian), landmark covariances (lvx_landmark_covariance: the eliminated landmark's row) and LiDAR map point
-// covariances (lvx_map_point_covariance: a lane per point, two pose windows and their cross block).
+// covariances (lvx_map_point_covariance: a lane per point, two pose windows and their cross block); last, the pixel covariance of map points in the images
+// (lvx_projection_covariance: k_proj_hub, one wavefront per image, the camera's and the LiDAR's pose windows with their cross block).
 // Included by lvx_solver.hip (its translation unit holds the factor's kernels).
 //
 // reduce_to_border(force_seq) leaves   Lb[j (bw + 1) + d] = L(j + d, j)   (band Cholesky),   Z[r ldz + j] = (L^-1 A_bc)(j, r)   and   S = A_cc - Zc^T Zc (unfactored),
@@ -20,6 +21,7 @@
 #pragma once
 #include "lvx_chol16.h"
 #include "lvx_lmcov.h"
+#include "lvx_projcov.h"
 #include "lvx_ptcov.h"
 
 namespace lvx {
@@ -266,8 +268,8 @@ __device__ __forceinline__ void window_sandwich(const double (*J)[W], const doub
     T[r][b] = s;
   }
   __syncthreads();
-  if (lane < R * R) {
-    const int r = lane / R, s2 = lane % R;
+  for (int e = lane; e < R * R; e += 64) {   // (one pass for R * R <= 64; lvx_projection_covariance has R = 12)
+    const int r = e / R, s2 = e % R;
     if (r >= s2) {
       double s = 0.0;
       for (int b = 0; b < W; ++b) s += T[r][b] * J[s2][b];
@@ -693,6 +695,77 @@ __global__ __launch_bounds__(PC_NT) void k_point_cov(PtCov g) {
     if (g.widx) for (int c = 0; c < PCOV_W; ++c) g.widx[i * PCOV_W + c] = -1;
     if (g.wcov) for (int e = 0; e < (int)W2; ++e) g.wcov[i * W2 + e] = 0.0;
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// lvx_projection_covariance (lvx_projcov.h has the algebra): the pixel covariance of map points in the images.  Three launches behind the selected inverse:
+//   k_proj_poses  (lvx_render.hip) the table's poses: the camera pose of every image and the LiDAR pose at t_map, by the functions and in the translation unit of
+//                 k_render_poses — the same bits, so that the decisions below are lvx_render_map_d's.
+//   k_proj_hub    here: one wavefront per image.  Lane 0 evaluates the two 6 x 31 pose Jacobians (camera frame at image_t + tau_C, LiDAR frame at t_map + tau_L); the
+//                 shared pieces gather the 62 x 62 window — the image's band window, band x border (the knots at t_map are hub slots) and border x border — and
+//                 form pose_cov = J12 W J12^T (12 x 12, J12 block-diagonal).  It makes k_pt_hub's status decisions (every workgroup reaches the same ones; the
+//                 first writes them) and leaves validity and the 78 unique entries of pose_cov in the image's record.
+//   k_proj_cov    (lvx_render.hip, built without FP contraction as k_render_map is: uv and the depth / bounds tests round as there) a lane per point.
+// ---------------------------------------------------------------------------------------------------------
+struct ProjHub {
+  const double* state; int N; double t0, dt, t_map; int n_images; const double* image_t; SigmaView v; ProjTable* tab;
+  double* pose_cov; double* wcov; int32_t* widx; int32_t* valid; int* flag; int* bad;
+};
+__global__ __launch_bounds__(64) void k_proj_hub(ProjHub g) {
+  __shared__ double JC[6][TCOV_W], JL[6][TCOV_W], J[12][PJ_W], W[PJ_W][PJ_W + 1], T[12][PJ_W], sc[PJ_W], Cv[12][12];
+  __shared__ int idxc[TCOV_W], idxl[TCOV_W], idx[PJ_W], pos[PJ_W], st_map, st_cam;
+  const int lane = threadIdx.x, i = blockIdx.x;
+  ProjTable* tab = g.tab;
+  if (sigma_lost(g.v)) { if (lane == 0 && i == 0) { tab->status = 1; *g.bad = 1; } return; }   // a lost pivot: nothing is written
+  if (lane == 0) {
+    const SplineRef sp{g.t0, g.dt, g.N, g.state, g.state + 3 * (size_t)g.N};
+    const double* ss = g.state + 7 * (size_t)g.N + 16;
+    SensorCal lid, cam;
+    lid.q = load_q(ss); lid.p = load_v3(ss + 4); lid.tau = ss[7];
+    cam.q = load_q(ss + 8); cam.p = load_v3(ss + 12); cam.tau = ss[15];
+    int sm = traj_pose_jacobian(sp, 1, lid, g.t_map + lid.tau, JL, idxl);
+    if (sm == RES_OK && !tab->map_valid) sm = RES_NONUNIT;   // (k_proj_poses' verdict on the same pose)
+    st_map = sm;
+    int sk = RES_RANGE;
+    if (sm == RES_OK) {
+      sk = traj_pose_jacobian(sp, 2, cam, g.image_t[i] + cam.tau, JC, idxc);
+      if (sk == RES_NONUNIT) *g.flag = RES_NONUNIT;
+      if (sk == RES_OK && !tab->img[i].valid) sk = RES_RANGE;
+    }
+    st_cam = sk;
+  }
+  __syncthreads();
+  if (st_map == RES_RANGE) { if (lane == 0 && i == 0) { tab->status = 2; *g.bad = 2; } return; }   // t_map + tau_L has left the trajectory
+  const size_t W2 = (size_t)PJ_W * PJ_W;
+  bool ok = st_map == RES_OK && st_cam == RES_OK;
+  if (st_map == RES_OK) {
+    // the LiDAR half of the window decides the call: a free knot scalar of the t_map window in the band is off the factor's pattern
+    if (lane < TCOV_W) idx[31 + lane] = idxl[lane];
+    if (lane < TCOV_W) idx[lane] = ok ? idxc[lane] : -1;
+    __syncthreads();
+    window_scalars<PJ_W>(g.v, idx, 0, lane, pos, sc, nullptr);
+    __syncthreads();
+    if (__any(lane >= 31 && lane < 55 && pos[lane] != LVX_DEAD && pos[lane] >= 0)) { if (lane == 0 && i == 0) { tab->status = 2; *g.bad = 2; } return; }
+  } else if (lane == 0 && i == 0) *g.flag = RES_NONUNIT;   // a non-unit control quaternion at t_map: every image is invalid, every point skipped
+  if (lane == 0 && i == 0) tab->status = st_map == RES_OK ? 0 : 3;
+  if (!ok) {   // image_t outside the spline (not an error), or a non-unit quaternion: zeros, indices -1
+    if (lane == 0) { g.valid[i] = 0; tab->img[i].valid = 0; }
+    if (lane < PJ_W && g.widx) g.widx[(size_t)i * PJ_W + lane] = -1;
+    if (g.wcov) for (int e = lane; e < (int)W2; e += 64) g.wcov[(size_t)i * W2 + e] = 0.0;
+    if (g.pose_cov) for (int e = lane; e < 144; e += 64) g.pose_cov[(size_t)i * 144 + e] = 0.0;
+    return;
+  }
+  if (lane < PJ_W && g.widx) g.widx[(size_t)i * PJ_W + lane] = pos[lane] != LVX_DEAD ? idx[lane] : -1;
+  for (int e = lane; e < 12 * PJ_W; e += 64) {
+    const int r = e / PJ_W, c = e % PJ_W;
+    J[r][c] = (r < 6 && c < 31) ? JC[r][c] : ((r >= 6 && c >= 31) ? JL[r - 6][c - 31] : 0.0);
+  }
+  window_gather<PJ_W>(g.v, pos, sc, lane, W, g.wcov ? g.wcov + (size_t)i * W2 : nullptr);
+  __syncthreads();
+  window_sandwich<12, PJ_W>(J, W, lane, T, Cv);
+  if (g.pose_cov) for (int e = lane; e < 144; e += 64) g.pose_cov[(size_t)i * 144 + e] = Cv[e / 12][e % 12];
+  for (int e = lane; e < 144; e += 64) { const int r = e / 12, c = e % 12; if (r >= c) tab->img[i].pc[r * (r + 1) / 2 + c] = Cv[r][c]; }
+  if (lane == 0) g.valid[i] = 1;
 }
 
 }  // namespace lvx

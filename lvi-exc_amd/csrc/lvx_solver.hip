@@ -1981,6 +1981,71 @@ int lvx_map_point_covariance(lvx_ctx* c, const lvx_point_cov_options* opt, int n
   return cov_finish(c, s, "lvx_map_point_covariance: a free scalar of the pose at t_map is a band position of the factor (its cross terms are off the pattern)");
 }
 
+// lvx_projection_covariance.  The selected inverse down to the lowest band position an image's camera window holds (k_tc_lowest in the camera frame; the window of
+// t_map stands in the border), the table's poses, k_proj_hub with a wavefront per image, then k_proj_cov with a lane per point.  xyzi_d [n][4] float, image_t_d and
+// the arrays of img / o are device addresses; flags as pt_cov_enqueue's.
+int lvx_proj_cov_default_options(lvx_proj_cov_options* o) {
+  const int rc = cov_default_options(o);
+  if (rc) return rc;
+  o->z_min = 0.1; o->z_max = 15.0;   // lvx_render_default_options'
+  return LVX_OK;
+}
+static int proj_cov_enqueue_all(lvx_ctx* c, const lvx_proj_cov_options* opt, long long n, const float* xyzi_d, int n_images, const double* image_t_d, const lvx_proj_cov_images& img,
+                                const lvx_proj_cov& o, int* flags) {
+  int rc;
+  SolveWork w; SelInvOut so;
+  hipStream_t st = c->stream;
+  const double* state_d = c->last_state_d;
+  if ((rc = dev_alloc(c, c->d_projcov, sizeof(ProjTable)))) return rc;
+  if ((rc = selinv_enqueue(c, "lvx_projection_covariance", opt->radius, opt->jacobi_scaling, false, w, &so, [&](int* head) {
+        hipLaunchKernelGGL(k_tc_lowest, dim3(1), dim3(64), 0, st, state_d, c->N, c->t0, c->dt, (int)LVX_FRAME_CAMERA, n_images, image_t_d, (const int*)c->d_ord.p, head); }))) return rc;
+  ProjTable* tab = (ProjTable*)c->d_projcov.p;
+  ProjHub g{state_d, c->N, c->t0, c->dt, c->t_map, n_images, image_t_d, sigma_view(c, w, so.SigB, SI_BD), tab, img.pose_cov, img.window_cov, img.window_idx, img.valid, flags, flags + 1};
+  {
+    ProfScope ps(c, LVX_KERNEL_PROJ_HUB);
+    if ((rc = proj_poses_enqueue(c, state_d, c->t_map, n_images, image_t_d, tab))) return rc;
+    hipLaunchKernelGGL(k_proj_hub, dim3((unsigned)n_images), dim3(64), 0, st, g);
+  }
+  LVX_HIP(c, hipGetLastError());
+  ProfScope ps(c, LVX_KERNEL_PROJ_COV);
+  return proj_cov_enqueue(c, n, xyzi_d, tab, opt->z_min, opt->z_max, o.uv, o.cov, o.sigma, o.sigma_max, o.image, o.status);
+}
+static int proj_cov_args(lvx_ctx* c, const lvx_proj_cov_options* opt, int n, bool cloud_ok, int n_images, const double* image_t, const lvx_proj_cov_images* img, const lvx_proj_cov* out) {
+  const bool no_hub = c && ((c->surf.n <= 0 && c->cs.n <= 0) || c->n_hub <= 0);
+  const bool no_cam = c && (c->cam.rows <= 0 || c->cam.cols <= 0);
+  const char* own_arg = (n_images < 1 || n_images > LVX_RENDER_MAX_IMAGES) ? "1 .. 32 images per call" : (opt && opt->z_min > opt->z_max ? "z_min > z_max" : nullptr);
+  return cov_common_args(c, "lvx_projection_covariance", opt && cloud_ok && image_t && img && img->valid && out && out->status, opt ? opt->radius : 0.0, opt ? &opt->reserved : nullptr, n,
+                         own_arg, no_cam ? "lvx_set_camera has not been called" : (no_hub ? "no surfel / camera-surfel family has set t_map" : nullptr));
+}
+int lvx_projection_covariance_d(lvx_ctx* c, const lvx_proj_cov_options* opt, int n, const float* map_xyzi4_d, int n_images, const double* image_t_d, const lvx_proj_cov_images* img_d,
+                                const lvx_proj_cov* out_d) {
+  int rc = proj_cov_args(c, opt, map_xyzi4_d ? n : 1, true, n_images, image_t_d, img_d, out_d);
+  if (rc) return rc;
+  long long np = n;
+  if (!map_xyzi4_d) {   // the cloud the last association left on the device, as lvx_render_map_d
+    np = (long long)c->da_S * c->da_H * c->da_W;
+    if (np == 0 || !c->d_da[4].p || c->d_da[4].bytes < (size_t)np * 16) return fail(c, LVX_E_STATE, "lvx_projection_covariance_d: lvx_data_association has not been called");
+    map_xyzi4_d = (const float*)c->d_da[4].p;
+  }
+  int* flags;
+  if ((rc = cov_d_flags(c, &flags))) return rc;
+  return proj_cov_enqueue_all(c, opt, np, map_xyzi4_d, n_images, image_t_d, *img_d, *out_d, flags);
+}
+int lvx_projection_covariance(lvx_ctx* c, const lvx_proj_cov_options* opt, int n, const float* map_xyzi4, int n_images, const double* image_t, const lvx_proj_cov_images* img,
+                              const lvx_proj_cov* out) {
+  int rc = proj_cov_args(c, opt, n, map_xyzi4 != nullptr, n_images, image_t, img, out);
+  if (rc) return rc;
+  const size_t nn = (size_t)n, ni = (size_t)n_images, W2 = (size_t)LVX_PROJ_COV_W * LVX_PROJ_COV_W;
+  CovStage s;
+  if ((rc = cov_stage(c, {{(void*)map_xyzi4, nn * 16}, {(void*)image_t, ni * 8}},
+                      {{img->pose_cov, ni * 144 * 8}, {img->window_cov, ni * W2 * 8}, {img->window_idx, ni * LVX_PROJ_COV_W * 4}, {img->valid, ni * 4},
+                       {out->uv, nn * 16}, {out->cov, nn * 32}, {out->sigma, nn * 16}, {out->sigma_max, nn * 8}, {out->image, nn * 4}, {out->status, nn}}, &s))) return rc;
+  const lvx_proj_cov_images id{(double*)s.d[2], (double*)s.d[3], (int32_t*)s.d[4], (int32_t*)s.d[5]};
+  const lvx_proj_cov od{(double*)s.d[6], (double*)s.d[7], (double*)s.d[8], (double*)s.d[9], (int32_t*)s.d[10], (uint8_t*)s.d[11]};
+  if ((rc = proj_cov_enqueue_all(c, opt, n, (const float*)s.d[0], n_images, (const double*)s.d[1], id, od, s.flags))) return rc;
+  return cov_finish(c, s, "lvx_projection_covariance: a free scalar of the pose at t_map is a band position of the factor (its cross terms are off the pattern)");
+}
+
 // The covariance of the JOINT problem: lvx_solve_step_shared's front half (the diagonal collective puts the joint diagonal at the shared slots and withholds their
 // damping), the elimination down to the border system from copies, then k_joint_cov_local -> ONE sum over the ranks -> k_joint_cov_shared.  Two collectives per call;
 // every failure is voted in the collective that follows it, so all ranks leave together.  With RCCL everything behind the diagonal collective is queued on the stream

@@ -172,8 +172,8 @@ int traj_check_d(lvx_ctx* c) {
   LVX_HIP(c, hipMemcpy(w, flag, 8, hipMemcpyDeviceToHost));
   if (!w[0] && !w[1]) return LVX_OK;
   LVX_HIP(c, hipMemset(flag, 0, 8));
-  if (w[1] == 2) return fail(c, LVX_E_STATE, "lvx_map_point_covariance_d: a free scalar of the pose at t_map is a band position (nothing was written)");
-  if (w[1]) return fail(c, LVX_E_NOTPD, "lvx_trajectory_covariance_d / lvx_landmark_covariance_d: damped normal equations not positive definite (nothing was written)");
+  if (w[1] == 2) return fail(c, LVX_E_STATE, "lvx_map_point_covariance_d / lvx_projection_covariance_d: a free scalar of the pose at t_map is a band position (nothing was written)");
+  if (w[1]) return fail(c, LVX_E_NOTPD, "lvx_trajectory_covariance_d / lvx_landmark_covariance_d / lvx_projection_covariance_d: damped normal equations not positive definite (nothing was written)");
   return fail(c, LVX_E_NONUNIT_QUAT, "logq: only implemented for unit quaternions");
 }
 

@@ -302,6 +302,41 @@ inline std::string FormatMapPointUncertainty(const MapPointUncertainty& r) {
                 r.valid.size(), r.radius);
   return buf;
 }
+// lvx_projection_covariance over map points [n][4] float (x, y, z, intensity; the LiDAR frame at t_map, as lvx_render_map takes them) and the images taken at
+// image_times: per point uv [n][2], cov [n][4] (px^2), sigma [n][2], sigma_max [n] (px), image [n] (-1: none), status [n] (0 skipped, 1 outside every image, 2
+// projected); per image pose_cov [n_images][144] over (camera dp, dphi; LiDAR dp, dphi) and image_valid.  The map point is taken as given (lvx.h).
+struct PixelUncertainty {
+  double radius = 0; std::vector<double> uv, cov, sigma, sigma_max, pose_cov; std::vector<int32_t> image, image_valid; std::vector<uint8_t> status;
+};
+inline PixelUncertainty ProjectionCovariance(lvx_ctx* ctx, const std::vector<float>& map_xyzi, const std::vector<double>& image_times, const lvx_proj_cov_options* opts = nullptr) {
+  if (map_xyzi.size() % 4 != 0) throw std::invalid_argument("ProjectionCovariance: four floats per map point");
+  const size_t n = map_xyzi.size() / 4, ni = image_times.size();
+  PixelUncertainty r;
+  lvx_proj_cov_options o; lvx_proj_cov_default_options(&o);
+  if (opts) o = *opts;
+  r.radius = o.radius;
+  if (n == 0) return r;
+  r.uv.assign(2 * n, 0.0); r.cov.assign(4 * n, 0.0); r.sigma.assign(2 * n, 0.0); r.sigma_max.assign(n, 0.0); r.image.assign(n, -1); r.status.assign(n, 0);
+  r.pose_cov.assign(144 * ni, 0.0); r.image_valid.assign(ni, 0);
+  const lvx_proj_cov_images img{r.pose_cov.data(), nullptr, nullptr, r.image_valid.data()};
+  const lvx_proj_cov out{r.uv.data(), r.cov.data(), r.sigma.data(), r.sigma_max.data(), r.image.data(), r.status.data()};
+  ThrowOnError(ctx, lvx_projection_covariance(ctx, &o, (int)n, map_xyzi.data(), (int)ni, image_times.data(), &img, &out));
+  return r;
+}
+// What a user reads off it, one line: the median, the 95 % quantile and the largest sigma_max over the projected points, in pixels
+//   [Map] pixel std (px): median a, 95 % b, max c at point i (n projected of m, k images, radius r)
+inline std::string FormatProjectionUncertainty(const PixelUncertainty& r) {
+  std::vector<double> s; std::vector<size_t> at;
+  for (size_t i = 0; i < r.status.size(); ++i) if (r.status[i] == 2) { s.push_back(r.sigma_max[i]); at.push_back(i); }
+  if (s.empty()) return "[Map] no projected point\n";
+  const size_t w = (size_t)(std::max_element(s.begin(), s.end()) - s.begin());
+  const double worst = s[w];
+  std::sort(s.begin(), s.end());
+  char buf[240];
+  std::snprintf(buf, sizeof buf, "[Map] pixel std (px): median %.4g, 95 %% %.4g, max %.4g at point %zu (%zu projected of %zu, %zu images, radius %g)\n", s[s.size() / 2],
+                s[(size_t)(0.95 * (double)(s.size() - 1))], worst, at[w], at.size(), r.status.size(), r.image_valid.size(), r.radius);
+  return buf;
+}
 // What a user reads off it, one line: the median and the largest relative depth sigma, sigma_rho / |rho| (to first order the relative sigma of the depth 1 / rho), over
 // the valid landmarks, and which landmark is the worst.  Without LandmarkUncertainty::rho the sigmas of the inverse depth themselves.
 //   [Landmarks] relative depth std: median a, max b at landmark l (n valid of m, radius r)
@@ -602,6 +637,24 @@ class Calibrator {
       if (index_in_scan) index_in_scan->push_back((int32_t)k);
     }
     return lvx_host::MapPointCovariance(ctx_, pts, t, {}, opts);
+  }
+  // lvx_projection_covariance over the map cloud — the de-skewed scans of the last data association (lvx_get_scans_in_map), every `step`-th cell that holds a point —
+  // in the images taken at image_times, at the normal equations and the state of the context's last LVX_EVAL_NORMAL_EQ evaluation; index_in_map[i] = the cell of entry
+  // i.  The host route: not the hot path (lvx_projection_covariance_d reads the resident cloud).
+  PixelUncertainty ProjectionUncertainty(const std::vector<double>& image_times, std::vector<int32_t>* index_in_map = nullptr, int step = 1, const lvx_proj_cov_options* opts = nullptr) {
+    if (step < 1) throw std::invalid_argument("ProjectionUncertainty: step < 1");
+    const size_t np = n_scans_ * (size_t)in_.H * in_.W;
+    std::vector<float> cloud(4 * np);
+    check(lvx_get_scans_in_map(ctx_, cloud.data()));
+    std::vector<float> pts;
+    if (index_in_map) index_in_map->clear();
+    for (size_t k = 0; k < np; k += (size_t)step) {
+      const float* p = &cloud[4 * k];
+      if (!std::isfinite(p[0]) || !std::isfinite(p[1]) || !std::isfinite(p[2])) continue;
+      pts.insert(pts.end(), p, p + 4);
+      if (index_in_map) index_in_map->push_back((int32_t)k);
+    }
+    return lvx_host::ProjectionCovariance(ctx_, pts, image_times, opts);
   }
   const std::vector<lvx_surfel_plane>& planes() const { return planes_; }
   const std::vector<AssociationRecord>& associations() const { return assoc_history_; }

@@ -32,7 +32,8 @@ KERNEL_NAMES = ["gyro", "accel", "prior", "surfel", "reproj", "camsurf", "fold",
 FAM_LIDAR_POS = 6       # LiDAR odometry position blocks (set_lidar_poses): not one of the six families of FAMILY_NAMES / family_rows()
 KERNEL_LIDAR_POS = 17   # beyond KERNEL_NAMES: kernel_ms_ext() returns it
 KERNEL_POSE_COV, KERNEL_POINT_COV = 18, 19   # k_pose_cov of trajectory_covariance; k_pt_hub + k_point_cov of map_point_covariance
-KERNEL_NAMES_EXT = KERNEL_NAMES + ["lidar_pos", "pose_cov", "point_cov"]
+KERNEL_PROJ_HUB, KERNEL_PROJ_COV = 20, 21   # k_proj_poses + k_proj_hub, k_proj_cov of projection_covariance
+KERNEL_NAMES_EXT = KERNEL_NAMES + ["lidar_pos", "pose_cov", "point_cov", "proj_hub", "proj_cov"]
 JAC_WIDTH = 64
 
 
@@ -137,6 +138,23 @@ class PointCov(C.Structure):
     """lvx_point_cov: host or device addresses; a NULL member (but valid) is not computed."""
     _fields_ = [("point", C.c_void_p), ("cov", C.c_void_p), ("sigma", C.c_void_p), ("sigma_max", C.c_void_p), ("var_dir", C.c_void_p), ("window_cov", C.c_void_p),
                 ("window_idx", C.c_void_p), ("valid", C.c_void_p)]
+
+
+PROJ_COV_W = 62   # window of lvx_projection_covariance: the four knots at image_t + tau_C, the camera's theta, p, tau, the four knots at t_map + tau_L, the LiDAR's theta, p, tau
+
+
+class ProjCovOptions(C.Structure):
+    _fields_ = [("radius", C.c_double), ("jacobi_scaling", C.c_int32), ("reserved", C.c_int32), ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
+class ProjCovImages(C.Structure):
+    """lvx_proj_cov_images: host or device addresses; a NULL member (but valid) is not computed."""
+    _fields_ = [("pose_cov", C.c_void_p), ("window_cov", C.c_void_p), ("window_idx", C.c_void_p), ("valid", C.c_void_p)]
+
+
+class ProjCov(C.Structure):
+    """lvx_proj_cov: host or device addresses; a NULL member (but status) is not computed."""
+    _fields_ = [("uv", C.c_void_p), ("cov", C.c_void_p), ("sigma", C.c_void_p), ("sigma_max", C.c_void_p), ("image", C.c_void_p), ("status", C.c_void_p)]
 
 
 N_SHARED = 14   # the shared extrinsic scalars of a joint solve: canonical slot k = c - 8
@@ -590,6 +608,54 @@ class Context:
         else:
             self._ck(self._l.lvx_map_point_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(points_d_ptr), C.c_void_p(t_d_ptr),
                                                        C.c_void_p(dirs_d_ptr) if dirs_d_ptr else None, C.byref(r)))
+
+    def _proj_options(self, radius, jacobi_scaling, z_min, z_max):
+        opt = self._cov_options(ProjCovOptions, self._l.lvx_proj_cov_default_options, radius, jacobi_scaling)
+        if z_min is not None:
+            opt.z_min = float(z_min)
+        if z_max is not None:
+            opt.z_max = float(z_max)
+        return opt
+
+    def projection_covariance(self, map_xyzi, image_t, radius=1e8, jacobi_scaling=True, window=False, lean=False, z_min=None, z_max=None):
+        """Pixel uncertainty of map points [n, 4] float32 (x, y, z, intensity; LiDAR frame at t_map, as render_map takes them) in the images taken at image_t
+        [n_images], in the DAMPED system of the last evaluate(normal_eq=True) at the state of that evaluation (lvx_projection_covariance).  Returns a dict: per point
+        uv [n, 2], cov [n, 2, 2] (px^2), sigma [n, 2], sigma_max [n] (px), image [n] (-1: none), status [n] (0 skipped, 1 outside every image, 2 projected); per image
+        pose_cov [n_images, 12, 12] over (camera dp, dphi; LiDAR dp, dphi), image_valid [n_images] bool and, with window=True, window_cov [n_images, 62, 62] and
+        window_idx [n_images, 62] (tangent index, -1 constant).  lean=True: status, image and image_valid only.  A non-unit control quaternion raises
+        LvxError(E_NONUNIT_QUAT) whose `partial` attribute is that dict."""
+        pts = np.ascontiguousarray(map_xyzi, dtype=np.float32).reshape(-1, 4)
+        image_t = _d(np.atleast_1d(image_t))
+        n, ni = len(pts), len(image_t)
+        out = dict(image=np.full(n, -1, np.int32), status=np.zeros(n, np.uint8))
+        if not lean:
+            out.update(uv=np.zeros((n, 2)), cov=np.zeros((n, 2, 2)), sigma=np.zeros((n, 2)), sigma_max=np.zeros(n), pose_cov=np.zeros((ni, 12, 12)))
+        if window:
+            out["window_cov"] = np.zeros((ni, PROJ_COV_W, PROJ_COV_W))
+            out["window_idx"] = np.full((ni, PROJ_COV_W), -1, np.int32)
+        valid = np.zeros(ni, np.int32)
+        img = ProjCovImages(*[out[k].ctypes.data if k in out else None for k in ("pose_cov", "window_cov", "window_idx")], valid.ctypes.data)
+        r = ProjCov(*[out[k].ctypes.data if k in out else None for k in ("uv", "cov", "sigma", "sigma_max", "image", "status")])
+        opt = self._proj_options(radius, jacobi_scaling, z_min, z_max)
+        rc = self._l.lvx_projection_covariance(self._h, C.byref(opt), C.c_int(n), _p(pts), C.c_int(ni), _p(image_t), C.byref(img), C.byref(r))
+        out["image_valid"] = valid.astype(bool)
+        if rc == E_NONUNIT_QUAT:
+            e = LvxError(rc, self._l.lvx_last_error(self._h).decode())
+            e.partial = out
+            raise e
+        self._ck(rc)
+        return out
+
+    def projection_covariance_d(self, map_d_ptr, n, image_t_d_ptr, n_images, img_d_ptrs, image_valid_d_ptr, out_d_ptrs, status_d_ptr, radius=1e8, jacobi_scaling=True,
+                                z_min=None, z_max=None):
+        """lvx_projection_covariance_d: device addresses (map_d_ptr 0 / None: the de-skewed scans of the last data association); img_d_ptrs maps "pose_cov" /
+        "window_cov" / "window_idx", out_d_ptrs "uv" / "cov" / "sigma" / "sigma_max" / "image" to addresses (absent: not computed).  Only enqueues; synchronize() reports
+        a lost pivot, a t_map window off the border or a non-unit quaternion."""
+        img = ProjCovImages(*[img_d_ptrs.get(f) for f in ("pose_cov", "window_cov", "window_idx")], image_valid_d_ptr)
+        r = ProjCov(*[out_d_ptrs.get(f) for f in ("uv", "cov", "sigma", "sigma_max", "image")], status_d_ptr)
+        opt = self._proj_options(radius, jacobi_scaling, z_min, z_max)
+        self._ck(self._l.lvx_projection_covariance_d(self._h, C.byref(opt), C.c_int(n), C.c_void_p(map_d_ptr) if map_d_ptr else None, C.c_int(n_images), C.c_void_p(image_t_d_ptr),
+                                                     C.byref(img), C.byref(r)))
 
     def lm_solve(self, state, max_iterations=50, **kw):
         """TrajectoryEstimator::Solve(max_iterations) equivalent.  Returns (state, summary dict with per-iteration history)."""
